@@ -19,10 +19,14 @@ bit emission) over the workload.  value = input bytes of all ranks / max-over-ra
 already in HBM when the timed region starts; "host_path" on the same line is the drop-in entry point zada_deflate on host
 buffers (PCIe both ways included), measured after the timed region.
 
-Also on the JSON line:
+A plain run sets up, warms up, times the K steps and prints the line: metric, value, unit, higher_is_better, dtype, ms_per_step
+and the roofline below, which comes from the timed steps themselves.  --dump-outputs DIR also writes what the last timed step
+computed (dump_outputs).  Everything else on the line is measured or checked only with --full, after the timed region:
   roofline     dominant kernel: algorithmic bytes per launch = N_in + N_out / its duration measured with HIP
                events on the encoder's own stream; "bound2": the resource that really bounds it, from the committed SQ
-               counter passes (profiles/).
+               counter passes (profiles/).  --full adds the measured copy bandwidth of the box (peak_measured_copy).
+  host_path    (--full, N = 1) the same input through zada_deflate on pageable host buffers; deflate_on_silesia_mix_v1 beside it.
+  bzip2, lzma  (--full, N = 1) the secondary legs: BZip2_3 of 256 MiB and a batch of LZMA_3 entries plus one LZMA_3 stream.
   cpu_baseline the oracle (single-threaded C port of the reference encoder, kind "port") on a bounded sample of the same
                stream on this box's host cores: one core, all cores (one stream per hardware thread), and libz tuned to
                the reference's IZ_10 row as a second anchor.
@@ -50,7 +54,24 @@ CORPUS_NAME = "silesia_mix_v2"
 
 
 def mix(za, nbytes, offset=0, version=None):
-    return za.silesia_mix(nbytes, seed=SEED, offset=offset, version=CORPUS if version is None else version)
+    """The benchmark stream's bytes [offset, offset + nbytes).  Large requests are filled in 64 MiB pieces on up to 16 host threads
+    (the generator is positional: a piece at its offset is the same bytes as the whole, and ctypes releases the GIL)."""
+    from concurrent.futures import ThreadPoolExecutor
+    import numpy as np
+    version = CORPUS if version is None else version
+    piece = 64 << 20
+    if nbytes <= piece:
+        return za.silesia_mix(nbytes, seed=SEED, offset=offset, version=version)
+    L = za.load_library()
+    gen = L.zada_silesia_mix_v2 if version >= 2 else L.zada_silesia_mix
+    b = np.empty(nbytes, dtype=np.uint8)
+    base = b.ctypes.data
+
+    def fill(o):
+        gen(SEED, 0x1F, offset + o, min(piece, nbytes - o), base + o)
+    with ThreadPoolExecutor(min(16, host_cpus()[0])) as ex:
+        list(ex.map(fill, range(0, nbytes, piece)))
+    return b
 
 
 def host_cpus():
@@ -417,6 +438,35 @@ def lzma_leg(za, enc, entries, kib, with_cpu, with_checks, one_mib=4):
     return out
 
 
+DUMP_HEAD = 1 << 20            # --dump-outputs: bytes of the stream written whole from its start
+DUMP_SAMPLE = 1 << 21          # ... bytes at seeded positions behind them
+DUMP_CHUNK = 1 << 20           # ... and the CRC-32 of every piece of this size, so that no byte goes uncompared
+
+
+def dump_outputs(dirpath, result, stream):
+    """--dump-outputs DIR: what the timed path returned in its last step, as .npy files (every value is exact in its type):
+      result.npy              float64, the numbers the entry point returns (see the callers)
+      stream.npy              float32, the compressed stream's bytes, when it is at most DUMP_HEAD + DUMP_SAMPLE bytes long; else
+      stream_head.npy         float32, its first DUMP_HEAD bytes,
+      stream_sample_pos.npy   float64, DUMP_SAMPLE positions behind them drawn with a fixed seed (sorted),
+      stream_sample.npy       float32, the bytes at those positions
+      stream_chunk_crc32.npy  float64, CRC-32 of every DUMP_CHUNK bytes of the whole stream (the last piece may be shorter)
+    About 28 MiB at most (plus 8 bytes per MiB of stream)."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    s = stream.cpu().numpy() if hasattr(stream, "cpu") else np.frombuffer(stream, dtype=np.uint8)
+    np.save(os.path.join(dirpath, "result.npy"), np.asarray(result, dtype=np.float64))
+    if len(s) <= DUMP_HEAD + DUMP_SAMPLE:
+        np.save(os.path.join(dirpath, "stream.npy"), s.astype(np.float32))
+    else:
+        np.save(os.path.join(dirpath, "stream_head.npy"), s[:DUMP_HEAD].astype(np.float32))
+        pos = np.sort(np.random.default_rng(SEED).integers(DUMP_HEAD, len(s), DUMP_SAMPLE))
+        np.save(os.path.join(dirpath, "stream_sample_pos.npy"), pos.astype(np.float64))
+        np.save(os.path.join(dirpath, "stream_sample.npy"), s[pos].astype(np.float32))
+    crcs = [zlib.crc32(s[o:o + DUMP_CHUNK]) for o in range(0, len(s), DUMP_CHUNK)]
+    np.save(os.path.join(dirpath, "stream_chunk_crc32.npy"), np.asarray(crcs, dtype=np.float64))
+
+
 def bzip2_main(args, za, sharding, enc, torch, dist, rank, world, dev, emulate):
     """BASELINE config 5: ONE BZip2_3 stream of world x mib MiB, the blocks sharded over the GPUs (sharding.bzip2_stream_rank):
     same contract as the Deflate line (W warm-up steps, K timed steps between barriers, max over ranks, one JSON line)."""
@@ -472,6 +522,9 @@ def bzip2_main(args, za, sharding, enc, torch, dist, rank, world, dev, emulate):
         return
     res = state["res"]
     nbytes = (res["total_bits"] + 7) // 8
+    if args.dump_outputs:
+        # result.npy: [inefficient (0 / 1), stream bytes, stream bits]
+        dump_outputs(args.dump_outputs, [int(bool(res["inefficient"])), nbytes, res["total_bits"]], state["stream"][:nbytes])
     out = {"metric": "BZip2_3 encode MB/s (one stream, blocks sharded over the GPUs; bit-exact with the CPU restatement of the reference, Ada parity unpinned)",
            "value": round(total * args.steps / dt / 1e6, 2), "unit": "MB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
@@ -549,7 +602,14 @@ def main():
     ap.add_argument("--lzma-entries", type=int, default=4096, help="entries of the secondary LZMA_3 batch measurement at one GPU (0 = skip)")
     ap.add_argument("--lzma-kib", type=int, default=16, help="KiB per entry of the LZMA_3 batch")
     ap.add_argument("--lzma-one-mib", type=int, default=4, help="MiB of the ONE LZMA_3 stream measured beside the batch (BASELINE config 4's shape)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline figure, after the timed region: the copy probe, "
+                    "the host-buffer path, the CPU baselines, the checks, the silesia_mix_v1 run and the BZip2 / LZMA legs (each --no-* option above still "
+                    "leaves its part out); without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed to DIR/*.npy (dump_outputs)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_copy_probe = args.no_cpu_baseline = args.no_checks = args.no_host_path = args.no_v1 = True
+        args.bzip2_mib = args.lzma_entries = 0
 
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be at least 1")
@@ -699,6 +759,10 @@ def main():
 
     if rank == 0:
         rc, out_len, crc = last["rc"], last["out_len"], last["crc"]
+        if args.dump_outputs:
+            # result.npy: [rc (0, or 1 = inefficient), stream bytes, CRC-32 register as returned (the Zip CRC is its complement)]
+            got = d_out[:out_len] if world == 1 else (state["stream"][:out_len] if state["stream"] is not None else b"")
+            dump_outputs(args.dump_outputs, [rc, out_len, crc], got)
         ms_per_step = dt * 1e3 / args.steps
         value = total * args.steps / dt / 1e6
         # dominant kernel = the single-kernel phase with the largest time (each of these phases is ONE launch per shard)
@@ -757,7 +821,7 @@ def main():
                                 "entry": "zada_deflate (pageable host buffers in and out, PCIe both ways included), the same %d steps" % args.steps}
             res["value_host_buffers"] = res["host_path"]["value"]
             stream = hout[:ol_h].tobytes()
-        else:
+        elif not args.no_checks:
             stream = bytes(state["stream"].cpu().numpy()) if state["stream"] is not None else b""
         ref = None
         if not args.no_cpu_baseline:

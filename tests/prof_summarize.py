@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Turns the raw rocprofv3 output of tests/prof_bench.sh <tag> (under gpurun_out/) into the small summaries
+"""Turns the raw rocprofv3 output of tests/prof_bench.sh <tag> (under $PROF_OUT, default prof_out/) into the small summaries
 committed under profiles/<round>/:  bench_1gib.json, bench_1gib_kernel_stats.csv, pmc_fetch_write_by_kernel.json.
 
     python tests/prof_summarize.py <tag> <round>       e.g.  r1d r1
@@ -7,7 +7,7 @@ committed under profiles/<round>/:  bench_1gib.json, bench_1gib_kernel_stats.csv
 import csv, glob, json, os, shutil, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag, rnd = sys.argv[1], sys.argv[2]
-G = os.path.join(ROOT, "gpurun_out")
+G = os.environ.get("PROF_OUT", os.path.join(ROOT, "prof_out"))
 P = os.path.join(ROOT, "profiles", rnd)
 os.makedirs(P, exist_ok=True)
 shutil.copy(os.path.join(G, tag + "_bench.json"), os.path.join(P, "bench_1gib.json"))
@@ -20,7 +20,7 @@ def norm(kernel_name):
 
 
 def newest(pattern):
-    """The files of the LAST run of a pass only: gpurun merges a call's output into gpurun_out/ next to what earlier calls left there, and two
+    """The files of the LAST run of a pass only: an output directory may still hold what earlier runs left there, and two
     runs' counters must not be added up."""
     fs = sorted(glob.glob(pattern), key=os.path.getmtime)
     return fs[-1:]

@@ -222,7 +222,7 @@ def test_bench_bzip2_multi_rank_path_on_one_gpu():
     env = dict(os.environ, BENCH_EMULATE="1", MASTER_ADDR="127.0.0.1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):                     # the plain form: bench.py starts its own ranks (bench.launch_ranks)
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "3", "--method", "bzip2", "--steps", "1", "--warmup", "1", "--mib", "40"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "3", "--method", "bzip2", "--steps", "1", "--warmup", "1", "--mib", "40"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -44,7 +44,7 @@ def test_bench_on_every_visible_gpu_runs_on_the_nccl_backend():
     n = min(_gpus(), 8)
     if n < 2:
         pytest.skip("one GPU visible: the nccl path between peers needs two")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--mib", "256", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(n), "--mib", "256", "--steps", "2", "--warmup", "1"],
                        env=_env(), capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -199,7 +199,8 @@ def test_bench_multi_rank_path_on_one_gpu(tmp_path):
     env = dict(os.environ, BENCH_EMULATE="1", MASTER_ADDR="127.0.0.1")
     # the driver's plain form: bench.py starts its own ranks when no launcher has (bench.launch_ranks)
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "3", "--steps", "2", "--warmup", "1", "--mib", "48", "--cpu-sample-mib", "8"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "3", "--steps", "2", "--warmup", "1", "--mib", "48", "--cpu-sample-mib", "8",
+           "--dump-outputs", str(tmp_path / "dump")]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -212,6 +213,44 @@ def test_bench_multi_rank_path_on_one_gpu(tmp_path):
     assert 0 < res["rank_ms_per_step"]["min"] <= res["rank_ms_per_step"]["max"] <= res["ms_per_step"] * 1.05
     assert set(res["exchange_ms_per_step"]) == {"all_gather_state", "boundary_atoms", "carry_chain", "spans", "gather_stitch"}
     assert all(v["max"] >= v["rank0"] >= 0 for v in res["exchange_ms_per_step"].values())
+    # --dump-outputs on rank 0: the stitched stream of the last timed step
+    rc, nbytes, _ = np.load(tmp_path / "dump" / "result.npy").tolist()
+    assert rc == 0 and abs(nbytes / (3 * (48 << 20)) - res["config"]["compression_ratio"]) <= 5e-5
+    assert len(np.load(tmp_path / "dump" / "stream_chunk_crc32.npy")) == (int(nbytes) + (1 << 20) - 1) >> 20
+
+
+def test_bench_plain_run_dumps_its_last_step(tmp_path):
+    """A plain bench.py run (no --full) prints the headline line and nothing that --full measures; --dump-outputs writes what its last timed
+    step computed: the result numbers, the stream's head, its seeded sample and the CRC-32 of every MiB, all equal to the oracle's stream of
+    the same input."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "BENCH_EMULATE")}
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--mib", "16", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert res["steps"] == 2 and res["warmup"] == 1 and res["ms_per_step"] > 0 and res["unit"] == "MB/s" and res["dtype"] == "u8"
+    assert res["higher_is_better"] is True and res["value"] > 0 and res["config"]["rc"] == 0
+    assert not {"checks", "cpu_baseline", "host_path", "deflate_on_silesia_mix_v1", "bzip2", "lzma"} & set(res), sorted(res)
+    d = silesia_mix(16 << 20, version=2)
+    rc, ref, _ = oracle_deflate(d, 10)
+    assert rc == 0
+    got = {f: np.load(out / f) for f in os.listdir(out)}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert sum(v.nbytes for v in got.values()) < 64e6
+    g_rc, g_len, g_crc = (int(x) for x in got["result.npy"])
+    assert g_rc == 0 and g_len == len(ref) and (g_crc ^ 0xFFFFFFFF) == zlib.crc32(d)
+    ref_a = np.frombuffer(ref, dtype=np.uint8)
+    assert np.array_equal(got["stream_head.npy"], ref_a[:1 << 20].astype(np.float32))
+    pos = got["stream_sample_pos.npy"].astype(np.int64)
+    assert len(pos) == 1 << 21 and pos.min() >= 1 << 20 and pos.max() < len(ref)
+    assert np.array_equal(got["stream_sample.npy"], ref_a[pos].astype(np.float32))
+    assert got["stream_chunk_crc32.npy"].tolist() == [zlib.crc32(ref[o:o + (1 << 20)]) for o in range(0, len(ref), 1 << 20)]
 
 
 def test_spans_on_one_context(encoder):
