@@ -40,7 +40,35 @@ enum {
   ZADA_LZMA_0 = 15,         /* LZMA, no LZ77: literals and short repeats only (lzma-encoding.adb:118-122) */
   ZADA_LZMA_1 = 16,         /* LZMA, Info-Zip matcher level 6, matches written as they come */
   ZADA_LZMA_2 = 17,         /* LZMA, Info-Zip matcher level 10, simple comparison of the ways to write a match */
-  ZADA_LZMA_3 = 18          /* LZMA, BT4 matcher, dictionary = the entry's size (up to 256 MiB), all comparisons incl. splitting */
+  ZADA_LZMA_3 = 18,         /* LZMA, BT4 matcher, dictionary = the entry's size (up to 256 MiB), all comparisons incl. splitting */
+  /* LZMA with the parameters of a data type (zip-compress-lzma_e.adb:121-143): (lc, lp, pb, level).  lc + lp >= 4: the literal table of
+   * 0x300 << (lc + lp) probabilities (24 KiB .. 6 MiB, zada_lzma_lit_table_bytes) lives in device memory, one per entry in flight */
+  ZADA_LZMA_2_FOR_ZIP_IN_ZIP = 19,   /* (8, 4, 0, 2) */
+  ZADA_LZMA_3_FOR_ZIP_IN_ZIP = 20,   /* (8, 4, 0, 3) */
+  ZADA_LZMA_2_FOR_SOURCE = 21,       /* (3, 0, 0, 2) */
+  ZADA_LZMA_3_FOR_SOURCE = 22,       /* (3, 0, 0, 3) */
+  ZADA_LZMA_FOR_JPEG = 23,           /* (8, 0, 0, 2) */
+  ZADA_LZMA_FOR_ARW = 24,            /* (8, 4, 4, 2) */
+  ZADA_LZMA_FOR_ORF = 25,            /* (8, 0, 0, 0) */
+  ZADA_LZMA_FOR_MP3 = 26,            /* (8, 4, 4, 2) */
+  ZADA_LZMA_FOR_MP4 = 27,            /* (8, 4, 4, 2) */
+  ZADA_LZMA_FOR_PGM = 28,            /* (8, 0, 0, 0) */
+  ZADA_LZMA_FOR_PPM = 29,            /* (4, 0, 0, 2) */
+  ZADA_LZMA_FOR_PNG = 30,            /* (8, 0, 2, 2) */
+  ZADA_LZMA_FOR_GIF = 31,            /* (0, 0, 0, 1) */
+  ZADA_LZMA_FOR_WAV = 32,            /* (0, 1, 1, 2) */
+  ZADA_LZMA_FOR_AU = 33,             /* (0, 2, 2, 2) */
+  /* Multi_Method (zip-compress.ads:118-120): a single method per entry, chosen from its type and size (zada_preselect) */
+  ZADA_PRESELECTION_1 = 34,          /* not too slow: Deflate_3, LZMA_2* */
+  ZADA_PRESELECTION_2 = 35           /* can be very slow on large data: Deflate_3, LZMA_2*, LZMA_3*, BZip2_3 */
+};
+
+/* Data_Content_Type'Pos (zip-compress.ads:151-160): the content hint of Preselection. */
+enum {
+  ZADA_HINT_NEUTRAL = 0, ZADA_HINT_SOURCE_CODE = 1, ZADA_HINT_TEXT_FORMATTED_TEXT_OR_DNA = 2, ZADA_HINT_TEXT_DATA = 3,
+  ZADA_HINT_JPEG = 4, ZADA_HINT_ARW_RW2 = 5, ZADA_HINT_ORF_CR2 = 6, ZADA_HINT_ZIP_IN_ZIP = 7,
+  ZADA_HINT_GIF = 8, ZADA_HINT_PNG = 9, ZADA_HINT_PGM = 10, ZADA_HINT_PPM = 11,
+  ZADA_HINT_WAV = 12, ZADA_HINT_AU = 13, ZADA_HINT_MP3 = 14, ZADA_HINT_MP4 = 15
 };
 
 /* Return codes.  1 and 2 mirror the reference's two non-error outcomes:
@@ -123,12 +151,21 @@ int zada_deflate_batch(zada_ctx *ctx, int method, int count,
                        uint8_t *const *out, const uint64_t *cap,
                        uint64_t *out_len, uint32_t *crc, int *rc);
 
-/* Zip.Compress.Compress_Data for one unencrypted Deflate method (zip-compress.adb:142-241):
+/* Zip.Compress.Compress_Data for one unencrypted Deflate, BZip2 or LZMA method (zip-compress.adb:142-241):
  * CRC Init/Final around zada_deflate, Store fallback when compression_ok = False.
- * zip_type: 8 (deflate) or 0 (store).  crc_out is the final CRC-32. */
+ * zip_type: 8 (deflate), 12 (bzip2), 14 (lzma) or 0 (store).  crc_out is the final CRC-32.  Preselection: zada_compress_data_hint. */
 int zada_compress_data(zada_ctx *ctx, int method, const uint8_t *in, uint64_t n,
                        uint8_t *out, uint64_t cap, uint64_t *out_len,
                        uint32_t *crc_out, uint16_t *zip_type);
+/* Zip.Compress.Guess_Type_from_Name (zip-compress.adb:330-424): the ZADA_HINT_* of an entry name, by the text after its last dot, case ignored
+ * (no dot, or NULL: ZADA_HINT_NEUTRAL).  Pure host code, no context. */
+int zada_guess_type_from_name(const char *name);
+/* The single method Compress_Data uses for `method` (zip-compress.adb:243-327): ZADA_PRESELECTION_1 / _2 by content_hint and, when
+ * input_size_known, input_size; any other method is returned as it is.  ZADA_E_INVALID for a hint or method out of range.  Pure host code. */
+int zada_preselect(int method, int content_hint, int input_size_known, uint64_t input_size);
+/* zada_compress_data with Preselection: the method is zada_preselect (method, content_hint, 1, n); *method_used (may be NULL) = that method. */
+int zada_compress_data_hint(zada_ctx *ctx, int method, int content_hint, const uint8_t *in, uint64_t n, uint8_t *out,
+                            uint64_t cap, uint64_t *out_len, uint32_t *crc_out, uint16_t *zip_type, int *method_used);
 
 /* ---- One stream over several contexts (GPUs) -------------------------------------------------------------------
  * The reference compresses an entry as ONE sequential stream (a 32 KiB window, a lazy-match state machine, a flush of the
@@ -217,9 +254,9 @@ int zada_bzip2_device(zada_ctx *ctx, int method, const void *d_in, uint64_t n, v
 int zada_bzip2_batch(zada_ctx *ctx, int method, int count, const uint8_t *const *in, const uint64_t *n, uint8_t *const *out,
                      const uint64_t *cap, uint64_t *out_len, uint32_t *crc, int *rc);
 /* ---------------------------------------------------------------------------------------------------------------
- * LZMA.  Replaces the body of Zip.Compress.LZMA_E (zip_lib/zip-compress-lzma_e.ads, .adb:29-184) for the
- * methods LZMA_0 .. LZMA_3, i.e. LZMA.Encoding.Encode (zip_lib/lzma-encoding.adb:59-1563) with lc = 3, lp = 0, pb = 2, an end
- * marker and dictionary_size = the input's size (zip-compress-lzma_e.adb:121-126, 160-165).  Conventions as zada_deflate:
+ * LZMA.  Replaces the body of Zip.Compress.LZMA_E (zip_lib/zip-compress-lzma_e.ads, .adb:29-184) for all
+ * nineteen LZMA methods 15 .. 33, i.e. LZMA.Encoding.Encode (zip_lib/lzma-encoding.adb:59-1563) with the method's lc, lp, pb and level, an end
+ * marker and dictionary_size = the input's size (zip-compress-lzma_e.adb:121-143, 160-165).  Conventions as zada_deflate:
  * method = Compression_Method'Pos, crc_inout = the running Zip CRC-32 register, return ZADA_OK / ZADA_INEFFICIENT / < 0.
  * The output is the Zip payload: the four bytes 16, 2, 5, 0 (:155-158), the 5-byte LZMA header, the range-coded stream.
  * The coder of a stream is one chain of dependent steps (adaptive probabilities): one workgroup codes it; entries are what runs in
@@ -232,8 +269,11 @@ int zada_bzip2_batch(zada_ctx *ctx, int method, int count, const uint8_t *const 
  * LZMA_3 can also return ZADA_E_REFERENCE (see the enum: an entry on which the reference's own matcher leaves the format -- not with the dictionary
  * Zip.Compress.LZMA_E asks for unless the entry is beyond 256 MiB; per entry in zada_lzma_batch's rc array).
  * Limits: entries below 2 GiB - 64 KiB, and for LZMA_3 below what the producer's memory allows (see above) (ZADA_E_TOO_LARGE beyond: the shim
- * Stores such an entry or raises); only the
- * (lc, lp, pb) = (3, 0, 2) methods LZMA_0 .. LZMA_3, not the data-specific LZMA_for_* variants (ZADA_E_INVALID).
+ * Stores such an entry or raises).
+ * Device memory: a method with lc + lp >= 4 (LZMA_*_for_Zip_in_Zip, _for_JPEG, ARW, ORF, MP3, MP4, PGM, PPM, PNG) keeps its literal table in the
+ * context's workspace, zada_lzma_lit_table_bytes (method) per entry in flight: 384 KiB for lc = 8, lp = 0, 6 MiB for lc = 8, lp = 4, 24 KiB for PPM.
+ * zada_lzma_batch runs such a batch in launch groups of at most "lzma_lit_mib" MiB of tables (knob, default 12288: 2 048 tables of 6 MiB, the coder's workgroups in flight; the same bytes either way).
+ * The state of a stream of such a method is not exported (zada_lzma_export_state: ZADA_E_INVALID); bounded launches, feedback and abort work as ever.
  * --------------------------------------------------------------------------------------------------------------- */
 int zada_lzma(zada_ctx *ctx, int method, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout,
               zada_feedback_fn fb, void *user);
@@ -247,11 +287,13 @@ int zada_lzma_device(zada_ctx *ctx, int method, const void *d_in, uint64_t n, vo
  * (the bytes before are the export's).  The match sets of LZMA_3 are a function of the input alone: the resumed call makes them again.  This is
  * Feedback / User_abort (zip-compress-lzma_e.adb:78-92) turned into a checkpoint: a stream that takes longer than one call may run is coded in two.
  * A state is spent by the next zada_lzma / zada_lzma_device call whatever comes of it, and it is checked before the coder takes it: a blob that is not
- * a stopped stream's (length, phase) is refused by zada_lzma_import_state, one whose stream length, method level, dictionary or counters do not fit the
+ * a stopped stream's (length, phase) is refused by zada_lzma_import_state, one whose stream length, method level, (lc, lp, pb), dictionary or counters do not fit the
  * call it meets by that call (ZADA_E_INVALID both times).  What cannot be checked is the input's CONTENT: the same bytes are the caller's to hand over. */
 int zada_lzma_export_state(zada_ctx *ctx, uint8_t *state, uint64_t state_cap, uint64_t *state_len, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes,
                            uint64_t *positions);
 int zada_lzma_import_state(zada_ctx *ctx, const uint8_t *state, uint64_t state_len);
+/* bytes of device memory the literal table of one entry of `method` takes (0: it is in the coder's LDS, or not an LZMA method).  Pure host code. */
+uint64_t zada_lzma_lit_table_bytes(int method);
 /* Many entries, one launch of the coder for all of them.  Arrays as for zada_deflate_batch; rc[i] is zada_lzma's return code
  * for entry i.  Returns the worst rc. */
 int zada_lzma_batch(zada_ctx *ctx, int method, int count, const uint8_t *const *in, const uint64_t *n, uint8_t *const *out,

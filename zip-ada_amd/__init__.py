@@ -21,15 +21,59 @@ LIB_PATH = os.environ.get("ZADA_LIB", os.path.join(_HERE, "libzada_hip.so"))   #
 
 
 class Method:
-    """Compression_Method'Pos, zip-compress.ads:59-122 (Deflation_Method subset)."""
+    """Compression_Method'Pos, zip-compress.ads:59-122.  Shrink, Reduce and Deflate_R are not implemented; the Preselection methods pick
+    one of the others per entry (preselect)."""
     Store = 0
+    Shrink_1 = 1
+    Reduce_1, Reduce_2, Reduce_3, Reduce_4 = 2, 3, 4, 5
     Deflate_Fixed = 6
     Deflate_0 = 7
     Deflate_1 = 8
     Deflate_2 = 9
     Deflate_3 = 10
+    Deflate_R = 11
     BZip2_1, BZip2_2, BZip2_3 = 12, 13, 14
     LZMA_0, LZMA_1, LZMA_2, LZMA_3 = 15, 16, 17, 18
+    LZMA_2_for_Zip_in_Zip, LZMA_3_for_Zip_in_Zip = 19, 20
+    LZMA_2_for_Source, LZMA_3_for_Source = 21, 22
+    LZMA_for_JPEG, LZMA_for_ARW, LZMA_for_ORF, LZMA_for_MP3, LZMA_for_MP4 = 23, 24, 25, 26, 27
+    LZMA_for_PGM, LZMA_for_PPM, LZMA_for_PNG, LZMA_for_GIF, LZMA_for_WAV, LZMA_for_AU = 28, 29, 30, 31, 32, 33
+    Preselection_1, Preselection_2 = 34, 35
+
+
+class ContentType:
+    """Data_Content_Type'Pos, zip-compress.ads:151-160: the content hint of the Preselection methods."""
+    neutral = 0
+    source_code = 1
+    text_formatted_text_or_dna = 2
+    text_data = 3
+    JPEG = 4
+    ARW_RW2 = 5
+    ORF_CR2 = 6
+    Zip_in_Zip = 7
+    GIF, PNG, PGM, PPM = 8, 9, 10, 11
+    WAV = 12
+    AU = 13
+    MP3, MP4 = 14, 15
+
+
+def _zip_type(method):
+    """The Zip format code of a single method (zip.ads:496-503): BZip2 12, LZMA 14, Deflate 8, Store 0."""
+    return 0 if method == Method.Store else 12 if Method.BZip2_1 <= method <= Method.BZip2_3 else 14 if Method.LZMA_0 <= method <= Method.LZMA_for_AU else 8
+
+
+def guess_type_from_name(name):
+    """Zip.Compress.Guess_Type_from_Name (zip-compress.adb:330-424): the ContentType of an entry name (zada_guess_type_from_name)."""
+    return int(load_library().zada_guess_type_from_name(name.encode("utf-8") if isinstance(name, str) else bytes(name)))
+
+
+def preselect(method, content_hint=ContentType.neutral, input_size=None):
+    """The single method Compress_Data uses for `method` (zip-compress.adb:243-327; zada_preselect): Preselection_1 / _2 by the content
+    hint and, when known, the input size; a single method is returned as it is."""
+    m = load_library().zada_preselect(int(method), int(content_hint), 0 if input_size is None else 1, 0 if input_size is None else int(input_size))
+    if m < 0:
+        raise ZadaError("zada_preselect: method %d or content hint %d out of range" % (method, content_hint))
+    return int(m)
 
 
 E_REFERENCE = -6     # zada.h ZADA_E_REFERENCE: LZMA_3, the reference's own matcher reports a match that is none on this entry
@@ -114,6 +158,12 @@ def load_library():
     L.zada_lzma_import_state.argtypes = [vp, vp, u64]
     L.zada_lzma_batch.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.zada_lzma_match_sets.argtypes = [vp, vp, u64, vp, vp, vp, i32]
+    if hasattr(L, "zada_preselect"):                 # (an older library under ZADA_LIB, for an A/B of what both have, lacks these)
+        L.zada_lzma_lit_table_bytes.restype = ctypes.c_uint64
+        L.zada_lzma_lit_table_bytes.argtypes = [i32]
+        L.zada_guess_type_from_name.argtypes = [ctypes.c_char_p]
+        L.zada_preselect.argtypes = [i32, i32, i32, u64]
+        L.zada_compress_data_hint.argtypes = [vp, i32, i32, vp, u64, vp, u64, u64p, u32p, vp, vp]
     L.zada_bz2_last_blocks.restype = ctypes.c_uint64
     L.zada_bz2_last_blocks.argtypes = [vp, vp, u64]
     L.zada_crc32_combine.restype = ctypes.c_uint32
@@ -239,7 +289,7 @@ class Encoder:
         return [(int(rcs[i]), bytes(mv[int(offs[i]):int(offs[i]) + int(ols[i])]) if rcs[i] >= 0 and ols[i] <= caps[i] else None, int(crcs[i])) for i in range(cnt)]
 
     def lzma(self, data, method=18, crc=0xFFFFFFFF, cap=None, feedback=None):
-        """Zip.Compress.LZMA_E (method 15 .. 18 = LZMA_0 .. LZMA_3).  Returns (rc, Zip payload, running CRC register); rc 1 = not
+        """Zip.Compress.LZMA_E (method 15 .. 33 = LZMA_0 .. LZMA_for_AU, Method).  Returns (rc, Zip payload, running CRC register); rc 1 = not
         smaller than the input (the payload is still returned when it fits `cap`, default len(data) * 9 // 8 + 4096).
         feedback(percent) is called between the launches of the stream; a true return raises UserAbort."""
         n = len(data)
@@ -277,8 +327,8 @@ class Encoder:
             self._err(rc, "zada_lzma_import_state")
 
     def lzma_batch(self, datas, method=18, crc=0xFFFFFFFF):
-        """Independent LZMA payloads (one per Zip entry) in one call: every entry is a workgroup of ONE launch of the coder.
-        Returns a list of (rc, payload or None, running CRC register)."""
+        """Independent LZMA payloads (one per Zip entry; method 15 .. 33) in one call: every entry is a workgroup of ONE launch of the coder
+        (methods whose literal table is in HBM: one launch per group of at most "lzma_lit_mib" MiB of tables).  Returns a list of (rc, payload or None, running CRC register)."""
         import numpy as np
         cnt = len(datas)
         if cnt == 0:
@@ -434,9 +484,10 @@ class Encoder:
             self._err(rc, "zada_deflate_device")
         return rc, ol.value, c.value
 
-    def compress_data(self, data, method=Method.Deflate_3):
-        """Zip.Compress.Compress_Data (single method, no password): returns
-        (payload bytes, final CRC-32, zip_type) with the Store fallback applied."""
+    def compress_data(self, data, method=Method.Deflate_3, content_hint=None):
+        """Zip.Compress.Compress_Data (no password): returns (payload bytes, final CRC-32, zip_type) with the Store fallback applied.
+        With a content_hint (ContentType) the method may be a Preselection method: the entry's method is then chosen by the content hint
+        and len(data) (zada_compress_data_hint, preselect).  Without one, a single method."""
         n = len(data)
         if method == Method.Store:
             import zlib  # CRC of stored data only; not on the Deflate path
@@ -445,8 +496,12 @@ class Encoder:
         ol = ctypes.c_uint64(0)
         c = ctypes.c_uint32(0)
         zt = ctypes.c_uint16(0)
-        rc = self.lib.zada_compress_data(self.ctx, method, _addr(data) if n else None, n, ctypes.addressof(out), n + 64,
-                                         ctypes.byref(ol), ctypes.byref(c), ctypes.byref(zt))
+        if content_hint is None:
+            rc = self.lib.zada_compress_data(self.ctx, method, _addr(data) if n else None, n, ctypes.addressof(out), n + 64,
+                                             ctypes.byref(ol), ctypes.byref(c), ctypes.byref(zt))
+        else:
+            rc = self.lib.zada_compress_data_hint(self.ctx, method, int(content_hint), _addr(data) if n else None, n, ctypes.addressof(out), n + 64,
+                                                  ctypes.byref(ol), ctypes.byref(c), ctypes.byref(zt), None)
         if rc != 0:
             self._err(rc, "zada_compress_data")
         return out.raw[:ol.value], c.value, zt.value
@@ -577,28 +632,45 @@ class ZipCreate:
     def _needs_zip64(csize, usize, offset):      # Needs_Local_Zip_64_Header_Extension, zip-headers.adb:197-210
         return csize >= 0xFFFFFFFF or usize >= 0xFFFFFFFF or offset >= 0xFFFFFFFF
 
+    def _presel(self):
+        return self.method in (Method.Preselection_1, Method.Preselection_2)
+
     def add_stream(self, name, data, file_time=None, unicode_name=True):
-        payload, crc, zt = self.enc.compress_data(data, self.method)
+        # (Preselection: the content hint is Guess_Type_from_Name of the entry's name, zip-create.adb:261)
+        hint = guess_type_from_name(name) if self._presel() else None
+        payload, crc, zt = self.enc.compress_data(data, self.method, content_hint=hint)
         return self.add_compressed(name, payload, crc, len(data), zt, file_time, unicode_name)
+
+    def _batch(self, datas, method):
+        if method == Method.Store:
+            return [(1, None, 0)] * len(datas)
+        if Method.BZip2_1 <= method <= Method.BZip2_3:
+            return self.enc.bzip2_batch(datas, method)
+        if Method.LZMA_0 <= method <= Method.LZMA_for_AU:
+            return self.enc.lzma_batch(datas, method)
+        return self.enc.deflate_batch(datas, method)
 
     def add_streams(self, names, datas, file_time=None, unicode_name=True):
         """Add_Stream for many entries at once: the entries are compressed as one batch (zada_deflate_batch: one launch
         sequence for all the small ones), with Compress_Data's Store fallback (zip-compress.adb:224-237) and CRC Init / Final
-        (:144, 218) per entry.  The archive is the one Add_Stream after Add_Stream writes."""
+        (:144, 218) per entry.  The archive is the one Add_Stream after Add_Stream writes.  Preselection: every entry's method is
+        preselect (method, Guess_Type_from_Name (name), size); the entries of one method go through its batch entry point together."""
         import zlib
-        if self.method == Method.Store:
-            res = [(1, None, 0)] * len(datas)
-        elif 12 <= self.method <= 14:
-            res = self.enc.bzip2_batch(datas, self.method)
-        elif 15 <= self.method <= 18:
-            res = self.enc.lzma_batch(datas, self.method)
+        names, datas = list(names), list(datas)
+        if self._presel():
+            methods = [preselect(self.method, guess_type_from_name(nm), len(d)) for nm, d in zip(names, datas)]
         else:
-            res = self.enc.deflate_batch(datas, self.method)
-        for name, data, (rc, payload, crc) in zip(names, datas, res):
+            methods = [self.method] * len(datas)
+        res = [None] * len(datas)
+        for m in sorted(set(methods)):
+            idx = [i for i, mi in enumerate(methods) if mi == m]
+            for i, r in zip(idx, self._batch([datas[i] for i in idx], m)):
+                res[i] = r
+        for name, data, m, (rc, payload, crc) in zip(names, datas, methods, res):
             if rc == 0:
-                self.add_compressed(name, payload, crc ^ 0xFFFFFFFF, len(data), 12 if 12 <= self.method <= 14 else 14 if 15 <= self.method <= 18 else 8, file_time, unicode_name)
+                self.add_compressed(name, payload, crc ^ 0xFFFFFFFF, len(data), _zip_type(m), file_time, unicode_name)
             else:
-                self.add_compressed(name, bytes(data), zlib.crc32(data) if self.method == Method.Store else crc ^ 0xFFFFFFFF, len(data), 0, file_time, unicode_name)
+                self.add_compressed(name, bytes(data), zlib.crc32(data) if m == Method.Store else crc ^ 0xFFFFFFFF, len(data), 0, file_time, unicode_name)
 
     def add_compressed(self, name, payload, crc, usize, zt, file_time=None, unicode_name=True):
         """Entry whose payload was compressed elsewhere (another rank / GPU): the bytes written

@@ -1105,6 +1105,7 @@ int zada_set_knob(zada_ctx *z, const char *name, int value) {
   else if (!strcmp(name, "lzma_pool")) { if (value < 0) return ZADA_E_INVALID; z->c.knob_lzma_pool = value; }
   else if (!strcmp(name, "lzma_pool_fixed")) { if (value < 0 || value > 1) return ZADA_E_INVALID; z->c.knob_lzma_pool_fixed = value; }
   else if (!strcmp(name, "lzma_waves")) { if (value != 0 && value != 1 && value != 4) return ZADA_E_INVALID; z->c.knob_lzma_waves = value; }
+  else if (!strcmp(name, "lzma_lit_mib")) { if (value < 1) return ZADA_E_INVALID; z->c.knob_lzma_lit_mib = value; }
   else if (!strcmp(name, "lzma_segment")) { if (value < -1 || (value > 0 && (value < 13 || value > 30))) return ZADA_E_INVALID; z->c.knob_lzma_segment = value; }
   else return ZADA_E_INVALID;
   return ZADA_OK;
@@ -1384,9 +1385,39 @@ static int lz_grow(Ctx *c, void **p, size_t *cap, size_t bytes) {
 static void lzma_free(Ctx *c) {
   if (c->lz_tab) hipFree(c->lz_tab);
   if (c->lz_save) hipFree(c->lz_save);
-  c->lz_tab = c->lz_save = nullptr; c->cap_lz_tab = c->cap_lz_save = 0;
+  if (c->lz_lit) hipFree(c->lz_lit);
+  c->lz_tab = c->lz_save = c->lz_lit = nullptr; c->cap_lz_tab = c->cap_lz_save = c->cap_lz_lit = 0;
   bt4_destroy(c);
 }
+// The LZMA methods, LZMA_Method'Pos 15 .. 33 (zip-compress.ads:59-122), with their parameters (zip-compress-lzma_e.adb:121-143).  The match
+// finding of a level does not depend on lc / lp / pb: only the coder's literal model and pos_state do (zada_lzma.hip, LM_*).
+struct LzmaParam { int lc, lp, pb, level; };
+static const LzmaParam LZMA_PARAM[ZADA_LZMA_FOR_AU - ZADA_LZMA_0 + 1] = {
+  {3, 0, 2, 0}, {3, 0, 2, 1}, {3, 0, 2, 2}, {3, 0, 2, 3},       // LZMA_0 .. LZMA_3
+  {8, 4, 0, 2}, {8, 4, 0, 3},                                   // LZMA_2_for_Zip_in_Zip, LZMA_3_for_Zip_in_Zip
+  {3, 0, 0, 2}, {3, 0, 0, 3},                                   // LZMA_2_for_Source, LZMA_3_for_Source
+  {8, 0, 0, 2}, {8, 4, 4, 2}, {8, 0, 0, 0},                     // LZMA_for_JPEG, _ARW, _ORF
+  {8, 4, 4, 2}, {8, 4, 4, 2},                                   // LZMA_for_MP3, _MP4
+  {8, 0, 0, 0}, {4, 0, 0, 2}, {8, 0, 2, 2},                     // LZMA_for_PGM, _PPM, _PNG
+  {0, 0, 0, 1}, {0, 1, 1, 2}, {0, 2, 2, 2},                     // LZMA_for_GIF, _WAV, _AU
+};
+static bool is_lzma_method(int method) { return method >= ZADA_LZMA_0 && method <= ZADA_LZMA_FOR_AU; }
+// where a method's literal table lives (zada_lzma.hip LM_*): LZMA_0 .. 3 their own instance, lc + lp <= 3 in LDS, the others in HBM
+static int lzma_lit_home(int method) {
+  const LzmaParam &p = LZMA_PARAM[method - ZADA_LZMA_0];
+  return method <= ZADA_LZMA_3 ? 0 : p.lc + p.lp <= 3 ? 1 : 2;
+}
+// bytes of a method's HBM literal table (0x300 << (lc + lp) probabilities of 2 bytes; 0: the table is in LDS)
+static uint64_t lzma_lit_bytes(int method) {
+  const LzmaParam &p = LZMA_PARAM[method - ZADA_LZMA_0];
+  return lzma_lit_home(method) == 2 ? 0x600ull << (p.lc + p.lp) : 0;
+}
+static void lzma_job_method(LzmaJob &J, int method) {
+  const LzmaParam &p = LZMA_PARAM[method - ZADA_LZMA_0];
+  J.level = p.level; J.lc = p.lc; J.lp = p.lp; J.pb = p.pb; J.lit_home = lzma_lit_home(method); J.lit_off = 0;
+}
+uint64_t zada_lzma_lit_table_bytes(int method) { return is_lzma_method(method) ? lzma_lit_bytes(method) : 0; }
+
 // One LZMA_3 stream in launches (budget > 0): log2 of the positions per segment of the BT4 producer, 32 = no segments.  The match sets of
 // segment k + 1 are found (stream2) while the coder -- one wave -- codes segment k: of all the producer's time, only segment 0's is waited for.
 static uint32_t lzma_segment_shift(const Ctx *c, uint64_t n) {
@@ -1414,16 +1445,28 @@ static int lzma_run(Ctx *c, std::vector<LzmaJob> &jobs, const uint8_t *d_in, uin
     }
     bt4 = bt4 || (j.level == 3 && j.n > 0);
   }
+  // the HBM literal tables (lc + lp >= 4): one per entry, filled with 1024 (initial_probability) before the first launch -- and again when the
+  // stream starts over; between the launches of one stream the table waits where it is, written by the entry's workgroup alone
+  const int lit_home = E ? jobs[0].lit_home : 0;
+  uint64_t lit_total = 0;
+  for (LzmaJob &j : jobs) {
+    if (j.lit_home != lit_home) { c->err = "LZMA: the jobs of one launch are of one method"; return ZADA_E_INVALID; }
+    if (lit_home == 2) { j.lit_off = lit_total / 2; lit_total += 0x600ull << (j.lc + j.lp); }
+  }
   // (a state from zada_lzma_import_state is for the next stream coded, whatever comes of it: it has to be the state of THIS stream -- one LZMA_3 stream in
   // launches, same length, dictionary and place -- or the call is refused; the kernel would take its counters as they are)
   std::vector<uint8_t> resume_blob;
   resume_blob.swap(c->lz_resume);
   if (!resume_blob.empty() && !(E == 1 && budget > 0 && resume_blob.size() == lzma_save_stride() && lzma_save_fits(resume_blob.data(), jobs[0]))) {
-    c->err = "LZMA: the imported state is not one of this stream (ONE LZMA_3 stream in launches, of the same length and dictionary)";
+    c->err = "LZMA: the imported state is not one of this stream (ONE LZMA_3 stream in launches, of the same length, dictionary, lc, lp and pb)";
     return ZADA_E_INVALID;
   }
+  if (!resume_blob.empty() && lit_home == 2) { c->err = "LZMA: a state of a method whose literal table is in HBM is not imported"; return ZADA_E_INVALID; }
   int rc = lz_grow(c, &c->lz_tab, &c->cap_lz_tab, (sizeof(LzmaJob) + 16 + 4) * (size_t)E + 192);
   if (rc) return rc;
+  if (lit_total && (rc = lz_grow(c, &c->lz_lit, &c->cap_lz_lit, lit_total))) return rc;
+  uint16_t *d_lit = lit_total ? (uint16_t *)c->lz_lit : nullptr;
+  auto fresh_lit = [&]() { if (lit_total) hipMemsetD16Async((hipDeviceptr_t)d_lit, 1024, lit_total / 2, c->stream); };
   Bt4Sets sets{nullptr, nullptr, nullptr, nullptr, nullptr};
   std::vector<uint32_t> weight;                                    // Level_3: what the producer found in each entry
   uint32_t seg_shift = bt4 && E == 1 && budget > 0 && jobs[0].in_off == 0 ? lzma_segment_shift(c, jobs[0].n) : 32, nseg = 0;
@@ -1443,7 +1486,8 @@ static int lzma_run(Ctx *c, std::vector<LzmaJob> &jobs, const uint8_t *d_in, uin
   if (d_apos && (rc = lzma_token_ranges(c, E, d_apos, T, d_ent_start, d_jobs))) return rc;   // token ranges of a batch, found on the device
   res.resize(2 * (size_t)E);
   if (budget == 0) {
-    if ((rc = lzma_launch(c, d_jobs, d_order, E, d_in, d_tok, d_out, sets, d_res))) return rc;
+    fresh_lit();
+    if ((rc = lzma_launch(c, d_jobs, d_order, E, d_in, d_tok, d_out, sets, d_res, nullptr, 0, ~0ull, 1, lit_home, d_lit))) return rc;
     hipMemcpyAsync(res.data(), d_res, 16 * (size_t)E, hipMemcpyDeviceToHost, c->stream);
     if (hip_check(c, hipStreamSynchronize(c->stream), "k_lzma_encode")) return ZADA_E_HIP;
   } else {
@@ -1455,6 +1499,7 @@ static int lzma_run(Ctx *c, std::vector<LzmaJob> &jobs, const uint8_t *d_in, uin
     auto fresh_state = [&]() {
       if (resume) hipMemcpyAsync(c->lz_save, resume_blob.data(), save_bytes, hipMemcpyHostToDevice, c->stream);
       else hipMemsetAsync(c->lz_save, 0, save_bytes, c->stream);
+      fresh_lit();
     };
     fresh_state();
     uint64_t total = 0;
@@ -1487,7 +1532,7 @@ static int lzma_run(Ctx *c, std::vector<LzmaJob> &jobs, const uint8_t *d_in, uin
       }
       uint64_t pos = 0;
       for (;;) {                                                     // the launches up to `cap`
-        if ((rc = lzma_launch(c, d_jobs, d_order, E, d_in, d_tok, d_out, sets, d_res, (uint8_t *)c->lz_save, budget, cap, waves))) return rc;
+        if ((rc = lzma_launch(c, d_jobs, d_order, E, d_in, d_tok, d_out, sets, d_res, (uint8_t *)c->lz_save, budget, cap, waves, lit_home, d_lit))) return rc;
         c->lzma_launches++;
         hipMemcpyAsync(res.data(), d_res, 16 * (size_t)E, hipMemcpyDeviceToHost, c->stream);
         if (hip_check(c, hipStreamSynchronize(c->stream), "k_lzma_encode")) return ZADA_E_HIP;
@@ -1536,10 +1581,11 @@ static uint64_t lzma_budget(const Ctx *c, int level) {
 }
 static int lzma_core(Ctx *c, int method, const uint8_t *d_in, uint64_t n, uint8_t *d_out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout,
                      zada_feedback_fn fb, void *user) {
-  if (method < ZADA_LZMA_0 || method > ZADA_LZMA_3) { c->err = "not an LZMA method"; return ZADA_E_INVALID; }
+  if (!is_lzma_method(method)) { c->err = "not an LZMA method"; return ZADA_E_INVALID; }
   // (BT4's positions are Integers that the reference re-bases at Integer'Last, lz77.adb:981-990, 1078-1083; the kernel does not)
   if (n >= (2ull << 30) - 65536) { c->err = "LZMA: entries of 2 GiB and more are not taken"; return ZADA_E_TOO_LARGE; }
-  const int level = method - ZADA_LZMA_0;
+  const int level = LZMA_PARAM[method - ZADA_LZMA_0].level;
+  c->lz_last_lit_hbm = lzma_lit_home(method) == 2;
   int rc;
   if (fb && fb(0, user)) return ZADA_ABORTED;                         // zip-compress-lzma_e.adb:78-92
   c->tbegin(); c->tmark("lzma:begin");
@@ -1550,7 +1596,8 @@ static int lzma_core(Ctx *c, int method, const uint8_t *d_in, uint64_t n, uint8_
   std::vector<LzmaJob> jobs(1);
   LzmaJob &J = jobs[0];
   memset(&J, 0, sizeof J);
-  J.n = n; J.cap = cap; J.level = level; J.zip_prefix = 1;
+  J.n = n; J.cap = cap; J.zip_prefix = 1;
+  lzma_job_method(J, method);
   const uint32_t *d_tok = nullptr;
   if ((level == 1 || level == 2) && n) {
     if ((rc = lzma_tokens(c, level, d_in, n, &J.ntok))) return rc;
@@ -1612,6 +1659,7 @@ int zada_lzma_export_state(zada_ctx *z, uint8_t *state, uint64_t state_cap, uint
   if (state_len) *state_len = sb;
   if (!state) return ZADA_OK;                                      // (the length only)
   if (!c->lz_save || c->cap_lz_save < sb || state_cap < sb) { c->err = "zada_lzma_export_state: no stopped stream, or the state buffer is too small"; return ZADA_E_INVALID; }
+  if (c->lz_last_lit_hbm) { c->err = "zada_lzma_export_state: the stream's method keeps its literal table in HBM (lc + lp >= 4); its state is not exported"; return ZADA_E_INVALID; }
   if (hipSetDevice(c->device) != hipSuccess) return ZADA_E_HIP;
   if (hipMemcpy(state, c->lz_save, sb, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return ZADA_E_HIP; }
   uint64_t pos = 0, olen = 0, n = 0;
@@ -1645,7 +1693,8 @@ int zada_lzma_match_sets(zada_ctx *z, const uint8_t *in, uint64_t n, uint8_t *cn
   std::vector<LzmaJob> jobs(1);
   LzmaJob &J = jobs[0];
   memset(&J, 0, sizeof J);
-  J.n = n; J.level = 3;
+  J.n = n;
+  lzma_job_method(J, ZADA_LZMA_3);
   J.sbs = lzma_string_buffer_size(3, c->knob_lzma_dict > 0 ? (uint64_t)c->knob_lzma_dict : n);
   J.hash4_size = lzma_hash4_size(J.sbs);
   Bt4Sets S;
@@ -1679,7 +1728,6 @@ int zada_lzma_match_sets(zada_ctx *z, const uint8_t *in, uint64_t n, uint8_t *cn
 static int lzma_batch_core(Ctx *c, int method, const int *idx, uint32_t E, const uint8_t *const *in, const uint64_t *n, uint8_t *const *out, const uint64_t *cap,
                            uint64_t *out_len, uint32_t *crc, int *rc_out) {
   hipStream_t st = c->stream;
-  const int level = method - ZADA_LZMA_0;
   std::vector<uint64_t> start(E), ostart(E); std::vector<uint32_t> start32(E + 1), len(E + 1), crc_in(E + 1);
   uint64_t total = 0, ototal = 0;
   for (uint32_t e = 0; e < E; e++) {
@@ -1706,7 +1754,8 @@ static int lzma_batch_core(Ctx *c, int method, const int *idx, uint32_t E, const
   for (uint32_t e = 0; e < E; e++) {
     LzmaJob &J = jobs[e];
     memset(&J, 0, sizeof J);
-    J.in_off = start[e]; J.n = len[e]; J.out_off = ostart[e]; J.cap = (len[e] + len[e] / 8 + 128ull); J.level = level; J.zip_prefix = 1;
+    J.in_off = start[e]; J.n = len[e]; J.out_off = ostart[e]; J.cap = (len[e] + len[e] / 8 + 128ull); J.zip_prefix = 1;
+    lzma_job_method(J, method);
   }
   c->tmark("lzma:tokens");
   std::vector<uint64_t> res;
@@ -1734,7 +1783,7 @@ static int lzma_batch_core(Ctx *c, int method, const int *idx, uint32_t E, const
 // 32 KiB slots, the segment table that ends every entry's searches at its own end), then one launch of the coder.
 static int lzma_batch_iz(Ctx *c, int method, const int *idx, uint32_t E, const uint8_t *const *in, const uint64_t *n, uint8_t *const *out, const uint64_t *cap,
                          uint64_t *out_len, uint32_t *crc, int *rc_out) {
-  const int level = method - ZADA_LZMA_0, iz_level = level == 1 ? 6 : 10;
+  const int level = LZMA_PARAM[method - ZADA_LZMA_0].level, iz_level = level == 1 ? 6 : 10;
   Workspace &W = c->ws;
   hipStream_t st = c->stream;
   std::vector<uint32_t> start(E + 1), len(E + 1), crc_in(E + 1);
@@ -1789,7 +1838,8 @@ static int lzma_batch_iz(Ctx *c, int method, const int *idx, uint32_t E, const u
   for (uint32_t e = 0; e < E; e++) {
     LzmaJob &J = jobs[e];
     memset(&J, 0, sizeof J);
-    J.in_off = start[e]; J.n = len[e]; J.out_off = ostart[e]; J.cap = len[e] + len[e] / 8 + 128ull; J.level = level; J.zip_prefix = 1;
+    J.in_off = start[e]; J.n = len[e]; J.out_off = ostart[e]; J.cap = len[e] + len[e] / 8 + 128ull; J.zip_prefix = 1;
+    lzma_job_method(J, method);
   }
   std::vector<uint64_t> res;
   uint8_t *d_out = c->ws.rin_own;
@@ -1813,28 +1863,30 @@ static int lzma_batch_iz(Ctx *c, int method, const int *idx, uint32_t E, const u
 }
 int zada_lzma_batch(zada_ctx *z, int method, int count, const uint8_t *const *in, const uint64_t *n, uint8_t *const *out, const uint64_t *cap, uint64_t *out_len,
                     uint32_t *crc, int *rc) {
-  if (!z || count < 0 || method < ZADA_LZMA_0 || method > ZADA_LZMA_3) return ZADA_E_INVALID;
+  if (!z || count < 0 || !is_lzma_method(method)) return ZADA_E_INVALID;
   int prc = prepare(z);
   if (prc) return prc;
   Ctx *c = &z->c;
   int worst = 0;
   std::vector<int> group;
-  uint64_t gbytes = 0;
+  uint64_t gbytes = 0, glit = 0;
+  const int level = LZMA_PARAM[method - ZADA_LZMA_0].level;
+  const uint64_t lit = lzma_lit_bytes(method), lit_cap = (uint64_t)c->knob_lzma_lit_mib << 20;   // (the HBM literal tables of a group: "lzma_lit_mib")
   auto flush_group = [&]() {
     if (group.empty()) return;
-    const bool iz = method == ZADA_LZMA_1 || method == ZADA_LZMA_2;
+    const bool iz = level == 1 || level == 2;
     int r = finish_call(c, iz ? lzma_batch_iz(c, method, group.data(), (uint32_t)group.size(), in, n, out, cap, out_len, crc, rc)
                               : lzma_batch_core(c, method, group.data(), (uint32_t)group.size(), in, n, out, cap, out_len, crc, rc));
     if (r < 0) { for (int i : group) rc[i] = r; worst = r; }
     else { for (int i : group) if (rc[i] < 0) worst = rc[i]; }
-    group.clear(); gbytes = 0;
+    group.clear(); gbytes = 0; glit = 0;
   };
   for (int i = 0; i < count; i++) {
     if (n[i] >= (2ull << 30) - 65536) { rc[i] = ZADA_E_TOO_LARGE; worst = rc[i]; continue; }
-    const bool iz_slots = method == ZADA_LZMA_1 || method == ZADA_LZMA_2;       // (whole 32 KiB segments of the LZ stage; 64-byte slots otherwise)
+    const bool iz_slots = level == 1 || level == 2;                              // (whole 32 KiB segments of the LZ stage; 64-byte slots otherwise)
     const uint64_t slot = iz_slots ? ((n[i] ? n[i] : 1) + 32767) & ~32767ull : ((n[i] ? n[i] : 1) + 63) & ~63ull;
-    if (gbytes + slot > (1ull << 30)) flush_group();
-    group.push_back(i); gbytes += slot;
+    if (gbytes + slot > (1ull << 30) || (lit && glit + lit > lit_cap)) flush_group();
+    group.push_back(i); gbytes += slot; glit += lit;
   }
   flush_group();
   return worst;
@@ -2037,7 +2089,7 @@ int zada_compress_data(zada_ctx *z, int method, const uint8_t *in, uint64_t n, u
                        uint32_t *crc_out, uint16_t *zip_type) {
   uint32_t crc = 0xFFFFFFFFu;                                   // Init, zip-compress.adb:144
   const bool bz = method >= ZADA_BZIP2_1 && method <= ZADA_BZIP2_3;                  // :204-209 (bzip2_code = 12, zip.ads:502)
-  const bool lz = method >= ZADA_LZMA_0 && method <= ZADA_LZMA_3;                    // :211-216 (lzma_code = 14, zip.ads:503)
+  const bool lz = is_lzma_method(method);                                            // :211-216 (lzma_code = 14, zip.ads:503)
   int rc = bz ? zada_bzip2(z, method, in, n, out, cap, out_len, &crc, nullptr, nullptr)
          : lz ? zada_lzma(z, method, in, n, out, cap, out_len, &crc, nullptr, nullptr)
               : zada_deflate(z, method, in, n, out, cap, out_len, &crc, nullptr, nullptr);
@@ -2051,6 +2103,82 @@ int zada_compress_data(zada_ctx *z, int method, const uint8_t *in, uint64_t n, u
   }
   *crc_out = crc;
   return ZADA_OK;
+}
+
+// Guess_Type_from_Name (zip-compress.adb:330-424): the lists in the reference's order -- HTM / HTML are source code because that list comes first
+int zada_guess_type_from_name(const char *name) {
+  if (!name) return ZADA_HINT_NEUTRAL;
+  const char *dot = strrchr(name, '.');
+  if (!dot) return ZADA_HINT_NEUTRAL;
+  char ext[8];                                                  // (no extension of the lists is longer than 5 letters)
+  const size_t len = strlen(dot + 1);
+  if (len >= sizeof ext) return ZADA_HINT_NEUTRAL;
+  for (size_t i = 0; i <= len; i++) { const char ch = dot[1 + i]; ext[i] = ch >= 'a' && ch <= 'z' ? (char)(ch - 'a' + 'A') : ch; }
+  auto in = [&](std::initializer_list<const char *> l) { for (const char *e : l) if (!strcmp(ext, e)) return true; return false; };
+  if (in({"JPG", "JPEG"})) return ZADA_HINT_JPEG;
+  if (in({"A", "ADA", "ADS", "ADB", "PRC", "PKG", "HAC", "GPR", "F", "FOR", "C", "H", "CPP", "HPP", "DEF", "ASM", "JAVA", "CS", "PAS", "INC", "LPR", "PP",
+          "M", "M4", "MAK", "IN", "SH", "BAT", "CMD", "PO", "XML", "XSL", "SGML", "AUP", "HTM", "HTML", "JS", "LSP", "SCM", "SQL", "PDB", "PL"}))
+    return ZADA_HINT_SOURCE_CODE;
+  if (in({"CFG", "INI", "LOG", "CSV", "SVG", "JSON"})) return ZADA_HINT_TEXT_DATA;
+  if (in({"TXT", "RTF", "HTM", "HTML", "GB", "FASTA"})) return ZADA_HINT_TEXT_FORMATTED_TEXT_OR_DNA;
+  if (in({"EPUB", "ZIP", "JAR", "ODB", "ODS", "ODT", "OTR", "OTS", "OTT", "CRX", "NTH", "DOCX", "PPTX", "XLSX", "XLSB", "XLSM"})) return ZADA_HINT_ZIP_IN_ZIP;
+  if (in({"ORF", "CR2", "RAF", "SRW"})) return ZADA_HINT_ORF_CR2;
+  if (in({"ARW", "RW2", "NEF", "DNG", "X3F"})) return ZADA_HINT_ARW_RW2;
+  if (in({"PGM"})) return ZADA_HINT_PGM;
+  if (in({"PPM"})) return ZADA_HINT_PPM;
+  if (in({"MP3"})) return ZADA_HINT_MP3;
+  if (in({"MTS", "MP4", "M4A", "M4P"})) return ZADA_HINT_MP4;
+  if (in({"PNG"})) return ZADA_HINT_PNG;
+  if (in({"GIF"})) return ZADA_HINT_GIF;
+  if (in({"WAV", "UAX"})) return ZADA_HINT_WAV;
+  if (in({"AU"})) return ZADA_HINT_AU;
+  return ZADA_HINT_NEUTRAL;
+}
+
+// Compress_Data's choice for the Preselection methods (zip-compress.adb:243-327); a single method goes through as it is
+int zada_preselect(int method, int content_hint, int input_size_known, uint64_t input_size) {
+  if (method < 0 || method > ZADA_PRESELECTION_2 || content_hint < ZADA_HINT_NEUTRAL || content_hint > ZADA_HINT_MP4) return ZADA_E_INVALID;
+  if (method < ZADA_PRESELECTION_1) return method;
+  const bool known = input_size_known != 0;
+  auto below = [&](uint64_t t) { return known && input_size < t; };
+  const bool fast = method == ZADA_PRESELECTION_1 || below(10000);                 // fast_presel_threshold
+  constexpr uint64_t bzip2_threshold = 15000;
+  switch (content_hint) {
+    case ZADA_HINT_NEUTRAL: case ZADA_HINT_TEXT_DATA:
+      return below(9000) ? ZADA_DEFLATE_3 : fast ? ZADA_LZMA_2 : ZADA_LZMA_3;
+    case ZADA_HINT_GIF:
+      return below(350) ? ZADA_DEFLATE_1 : ZADA_LZMA_FOR_GIF;
+    case ZADA_HINT_ZIP_IN_ZIP:
+      return below(1000) ? ZADA_DEFLATE_3 : fast ? ZADA_LZMA_2_FOR_ZIP_IN_ZIP : ZADA_LZMA_3_FOR_ZIP_IN_ZIP;
+    case ZADA_HINT_SOURCE_CODE:
+      return below(8000) ? ZADA_DEFLATE_3 : fast ? ZADA_LZMA_2_FOR_SOURCE : below(bzip2_threshold) ? ZADA_LZMA_3_FOR_SOURCE : ZADA_BZIP2_3;
+    case ZADA_HINT_TEXT_FORMATTED_TEXT_OR_DNA:
+      return below(9000) ? ZADA_DEFLATE_3 : fast ? ZADA_LZMA_2 : below(bzip2_threshold) ? ZADA_LZMA_3 : ZADA_BZIP2_3;
+    default: {                                                   // ARW_RW2 | ORF_CR2 | MP3 | MP4 | JPEG | PGM | PPM | PNG | WAV | AU: data_type_to_LZMA_method
+      if (below(2250)) return ZADA_DEFLATE_3;
+      switch (content_hint) {
+        case ZADA_HINT_JPEG: return ZADA_LZMA_FOR_JPEG;
+        case ZADA_HINT_ARW_RW2: return ZADA_LZMA_FOR_ARW;
+        case ZADA_HINT_ORF_CR2: return ZADA_LZMA_FOR_ORF;
+        case ZADA_HINT_MP3: return ZADA_LZMA_FOR_MP3;
+        case ZADA_HINT_MP4: return ZADA_LZMA_FOR_MP4;
+        case ZADA_HINT_PGM: return ZADA_LZMA_FOR_PGM;
+        case ZADA_HINT_PPM: return ZADA_LZMA_FOR_PPM;
+        case ZADA_HINT_PNG: return ZADA_LZMA_FOR_PNG;
+        case ZADA_HINT_WAV: return ZADA_LZMA_FOR_WAV;
+        default: return ZADA_LZMA_FOR_AU;
+      }
+    }
+  }
+}
+
+int zada_compress_data_hint(zada_ctx *z, int method, int content_hint, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len,
+                            uint32_t *crc_out, uint16_t *zip_type, int *method_used) {
+  if (!z || !out_len || !crc_out || !zip_type || (n && (!in || !out))) return ZADA_E_INVALID;
+  const int m = zada_preselect(method, content_hint, 1, n);
+  if (m < 0) { z->c.err = "zada_compress_data_hint: method or content hint out of range"; return ZADA_E_INVALID; }
+  if (method_used) *method_used = m;
+  return zada_compress_data(z, m, in, n, out, cap, out_len, crc_out, zip_type);
 }
 
 int zada_lz77_tokens(zada_ctx *z, int method, const uint8_t *in, uint64_t n, uint32_t *tokens, uint64_t cap, uint64_t *ntok) {

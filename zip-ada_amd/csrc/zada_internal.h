@@ -261,6 +261,10 @@ struct Ctx {
   void *bz = nullptr;                                // BZip2 state (zada_bz2.hip), made on first use
   void *lz_tab = nullptr; size_t cap_lz_tab = 0;     // LZMA (zada_lzma.hip): job table + results
   void *lz_save = nullptr; size_t cap_lz_save = 0;   // ... the coder's state between the launches of one stream
+  void *lz_lit = nullptr; size_t cap_lz_lit = 0;     // ... the HBM literal tables of the methods with lc + lp >= 4, one per entry of a launch group
+  bool lz_last_lit_hbm = false;                      // the last LZMA stream's literal table was in HBM (its state is not exported)
+  int knob_lzma_lit_mib = 12288;                     // LZMA, lc + lp >= 4: MiB of HBM literal tables one launch group of a batch may take (a larger batch: several
+                                                     // groups; 12 GiB: 2 048 tables of 6 MiB, as many entries as the coder has workgroups in flight)
   int lzma_launches = 0;                             // launches the last chunked LZMA call took
   std::vector<uint8_t> lz_resume;                    // zada_lzma_import_state: the coder's state the next zada_lzma call goes on from (one stream)
   uint64_t lz_last_n = 0, lz_last_out_off = 0;       // the last zada_lzma call: its input length and where its stream lies in the context's buffer (zada_lzma_export_state)
@@ -336,6 +340,9 @@ struct LzmaJob {
   uint64_t verify;                  // Level_3: 1 = the coder checks every match of the sets it reads against the text (bt4_reads_behind_a_gap, zada_bt4.h)
   uint32_t sbs, hash4_size;         // String_buffer_size (lzma-encoding.adb:137-149), BT4's hash4 size (lz77.adb:1019-1032)
   int32_t level, zip_prefix;        // 0 .. 3; 1: the four bytes of zip-compress-lzma_e.adb:155-158 go first
+  int32_t lc, lp, pb;               // the method's literal context bits, literal position bits, position bits (zip-compress-lzma_e.adb:121-143)
+  int32_t lit_home;                 // where the literal table lives (zada_lzma.hip LM_*): 0 (3, 0, 2), 1 LDS, 2 HBM; the same for every job of a launch
+  uint64_t lit_off;                 // lit_home 2: the entry's table, in probabilities from the launch's literal buffer
 };
 // The match sets the BT4 producer leaves in HBM (zada_bt4.hip), indexed by arena position p: cnt [p] matches; match i < 7 at slot
 // p * 8 + i of sl (length) / sd (distance); match i >= 7 at slot sd [p * 8 + 7] * 43 + (i - 7) of ol / od.
@@ -349,7 +356,7 @@ uint32_t lzma_string_buffer_size(int level, uint64_t dictionary_size);
 uint32_t lzma_hash4_size(uint32_t sbs);
 int lzma_token_ranges(Ctx *c, uint32_t E, const uint32_t *d_apos, uint32_t T, const uint32_t *d_ent_start, LzmaJob *d_jobs);
 int lzma_launch(Ctx *c, const LzmaJob *d_jobs, const uint32_t *d_order, uint32_t count, const uint8_t *d_in, const uint32_t *d_tok, uint8_t *d_out, const Bt4Sets &sets, uint64_t *d_result,
-                uint8_t *d_save = nullptr, uint64_t budget = 0, uint64_t pos_cap = ~0ull, int waves = 1);
+                uint8_t *d_save = nullptr, uint64_t budget = 0, uint64_t pos_cap = ~0ull, int waves = 1, int lit_home = 0, uint16_t *d_lit = nullptr);
 uint64_t lzma_save_stride();
 int lzma_save_info(const uint8_t *blob, uint64_t *pos, uint64_t *olen, uint64_t *n);
 int lzma_save_fits(const uint8_t *blob, const LzmaJob &J);

@@ -1,5 +1,5 @@
 // zada_lzma.hip -- LZMA encoding for gfx950: LZMA.Encoding.Encode (zip_lib/lzma-encoding.adb:59-1563) with the
-// parameters of Zip.Compress.LZMA_E's methods LZMA_0 .. LZMA_3 (zip-compress-lzma_e.adb:121-126: lc 3, lp 0, pb 2, end marker).
+// parameters of Zip.Compress.LZMA_E's nineteen methods (zip-compress-lzma_e.adb:121-143: lc, lp, pb, level; end marker).
 //
 // What is parallel and what is not.  The range coder (:964-1039) and the choice between the ways of writing a match (:349-946)
 // both read the adaptive bit probabilities, which every coded bit updates: a stream is one chain of dependent steps, and the
@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <type_traits>
 #include "../../include/zada.h"
 #include "zada_internal.h"
 #include "zada_bt4.h"
@@ -28,8 +29,8 @@
 namespace zada {
 namespace {
 
-constexpr int LZ_LIT = 0x300 << 3;             // lc = 3, lp = 0
-constexpr uint32_t LZ_PBM = 3;                 // pb = 2
+constexpr int LZ_LIT = 0x300 << 3;             // the literal table in LDS: lc + lp <= 3
+constexpr uint32_t LZ_PBM = 3;                 // pb = 2 of LZMA_0 .. LZMA_3
 constexpr int LZ_MAXM = BT4_SET + 2;           // matches of one position: BT4 finds at most 50 (zada_bt4.h), + 1 repeat match, (1 .. count)
 
 struct LenProbs { uint16_t c1, c2, low[16][8], mid[16][8], high[256]; };
@@ -52,6 +53,32 @@ struct MS {                                    // Machine_State :212-219 without
 // objects, so that every access is a ds_ instruction (through a pointer in a struct they were flat loads: 36 M of them per 64 KiB).
 __shared__ LzProbs s_P;
 __shared__ Matches s_MM[2];
+
+// The literal model's parameters and home: every function that reads or writes the model is a template of LM.
+//   LM_DEF: (lc, lp, pb) = (3, 0, 2) as constants, the table in s_P.lit (LZMA_0 .. LZMA_3: the code they always ran);
+//   LM_LDS: (lc, lp, pb) of the entry's method with lc + lp <= 3, the table in s_P.lit (0x300 << (lc + lp) of its LZ_LIT entries);
+//   LM_HBM: lc + lp >= 4, the table (0x300 << (lc + lp) probabilities, 24 KiB .. 6 MiB) in HBM, one per entry (LzmaJob::lit_off), filled with
+//           1024 by the host before the first launch and written by the entry's workgroup alone.  The rest of the model stays in LDS.
+// (s_L is set from the job at the start of every launch; it is not part of the saved state)
+enum { LM_DEF = 0, LM_LDS = 1, LM_HBM = 2 };
+struct LitCfg { uint32_t lc, lpm, pbm; uint16_t *lit; };
+__shared__ LitCfg s_L;
+typedef __attribute__((address_space(1))) const uint16_t gu16;
+template <int LM> __device__ __forceinline__ uint32_t pbm() { if constexpr (LM == LM_DEF) return LZ_PBM; else return s_L.pbm; }
+// Idx_for_Literal_prob :193-201: 0x300 * (((position and literal_pos_mask) << lc) + prev_byte >> (8 - lc))
+template <int LM> __device__ __forceinline__ int lit_idx(uint32_t prev_byte, uint64_t pos) {
+  if constexpr (LM == LM_DEF) return 0x300 * (int)(prev_byte >> 5);
+  else return 0x300 * (int)((((uint32_t)pos & s_L.lpm) << s_L.lc) + (prev_byte >> (8 - s_L.lc)));
+}
+// the model's literal probabilities, for reading (the HBM table through a global pointer: global_load, not flat) and for the coder's updates
+template <int LM> __device__ __forceinline__ auto lit_rd(int idx) {
+  if constexpr (LM == LM_HBM) return (gu16 *)s_L.lit + idx;
+  else return (const uint16_t *)s_P.lit + idx;
+}
+template <int LM> __device__ __forceinline__ uint16_t *lit_wr(int idx) {
+  if constexpr (LM == LM_HBM) return s_L.lit + idx;
+  else return s_P.lit + idx;
+}
 
 struct Enc {
   const uint8_t *in; uint64_t n;
@@ -118,8 +145,8 @@ __device__ inline double tq(uint16_t p, uint32_t sym) {
 }
 __device__ inline double scale11(double x, int factors) { return __builtin_ldexp(x, -11 * factors); }
 
-__device__ double test_simple_literal(uint32_t b, uint32_t b_match, int idx, const MS &sim) {   // :372-419
-  const uint16_t *prob = s_P.lit + idx;
+template <int LM> __device__ double test_simple_literal(uint32_t b, uint32_t b_match, int idx, const MS &sim) {   // :372-419
+  const auto *prob = lit_rd<LM>(idx);
   double pl = tq(s_P.match[sim.state][sim.pos_state], 0);
   uint32_t symb = b | 0x100;
   uint16_t pr[8];                                 // the eight probabilities first (their addresses do not depend on each other), then the products in order
@@ -146,13 +173,11 @@ __device__ inline double test_short_rep(const MS &sim) {           // :421-428
   return scale11(tq(P.match[sim.state][sim.pos_state], 1) * tq(P.rep[sim.state], 1) * tq(P.g0[sim.state], 0) * tq(P.rep0_long[sim.state][sim.pos_state], 0), 4);
 }
 
-__device__ inline int lit_idx(uint32_t prev_byte) { return 0x300 * (int)(prev_byte >> 5); }    // Idx_for_Literal_prob :193-201
-
 // Simulate_Literal_Byte :431-458; b_match = the byte at the last distance, Text_Buf ((R - rep_dist (0) - 1) and mask)
-__device__ __forceinline__ void sim_literal_bm(uint32_t b, uint32_t b_match, MS &sim, double &prob) {
-  const int idx = lit_idx(sim.prev_byte);
-  sim.pos_state = (uint32_t)sim.pos & LZ_PBM;
-  const double ltr = test_simple_literal(b, b_match, idx, sim);
+template <int LM> __device__ __forceinline__ void sim_literal_bm(uint32_t b, uint32_t b_match, MS &sim, double &prob) {
+  const int idx = lit_idx<LM>(sim.prev_byte, sim.pos);
+  sim.pos_state = (uint32_t)sim.pos & pbm<LM>();
+  const double ltr = test_simple_literal<LM>(b, b_match, idx, sim);
   bool srep = false;
   if (b == b_match && sim.pos > (uint64_t)(uint32_t)(sim.rep[0] + 1)) {
     const double srm = test_short_rep(sim);
@@ -160,16 +185,16 @@ __device__ __forceinline__ void sim_literal_bm(uint32_t b, uint32_t b_match, MS 
   }
   if (!srep) { sim.state = t_lit(sim.state); prob = prob * ltr; }
   sim.pos += 1;
-  sim.pos_state = (uint32_t)sim.pos & LZ_PBM;
+  sim.pos_state = (uint32_t)sim.pos & pbm<LM>();
   sim.prev_byte = b;
 }
-__device__ __forceinline__ void sim_literal(uint32_t b, MS &sim, double &prob) {
-  sim_literal_bm(b, TB((int64_t)sim.pos - (int64_t)sim.rep[0] - 1), sim, prob);
+template <int LM> __device__ __forceinline__ void sim_literal(uint32_t b, MS &sim, double &prob) {
+  sim_literal_bm<LM>(b, TB((int64_t)sim.pos - (int64_t)sim.rep[0] - 1), sim, prob);
 }
 
-__device__ inline double test_literal_byte(uint32_t b, const MS &sim) {          // :460-468
+template <int LM> __device__ inline double test_literal_byte(uint32_t b, const MS &sim) {          // :460-468
   MS v = sim; double prob = 1.0;
-  sim_literal(b, v, prob);
+  sim_literal<LM>(b, v, prob);
   return prob;
 }
 
@@ -259,7 +284,7 @@ __device__ __forceinline__ StrictRes strict_factors(uint32_t distance, int lengt
   return r;
 }
 // the state behind the strict code whose factors are r
-__device__ __forceinline__ void strict_apply(uint32_t distance, int length, const StrictRes &r, MS &sim) {
+template <int LM> __device__ __forceinline__ void strict_apply(uint32_t distance, int length, const StrictRes &r, MS &sim) {
   const uint32_t dist_ip = distance - 1;
   if (r.found >= 0) {
     const uint32_t r0 = sim.rep[0], r1 = sim.rep[1], r2 = sim.rep[2];             // rep (found) to the front, the ones before it one down
@@ -273,16 +298,16 @@ __device__ __forceinline__ void strict_apply(uint32_t distance, int length, cons
     sim.state = t_match(sim.state);
   }
   sim.pos += (uint64_t)length;
-  sim.pos_state = (uint32_t)sim.pos & LZ_PBM;
+  sim.pos_state = (uint32_t)sim.pos & pbm<LM>();
   sim.prev_byte = TB((int64_t)sim.pos - 1);
 }
-__device__ __forceinline__ void sim_strict(uint32_t distance, int length, MS &sim, double &prob) {
+template <int LM> __device__ __forceinline__ void sim_strict(uint32_t distance, int length, MS &sim, double &prob) {
   const StrictRes r = strict_factors(distance, length, sim);
   prob = prob * r.f1 * r.f2;
-  strict_apply(distance, length, r, sim);
+  strict_apply<LM>(distance, length, r, sim);
 }
 
-__device__ double test_expanded(uint32_t distance, int length, double give_up, const MS &sim) {   // :680-726
+template <int LM> __device__ double test_expanded(uint32_t distance, int length, double give_up, const MS &sim) {   // :680-726
   MS v = sim; double p = 1.0;
   const int64_t copy_start = (int64_t)sim.pos - (int64_t)distance;
   // The copied bytes and the bytes at the last distance (a literal does not change it) are two runs of consecutive bytes: eight of each
@@ -302,7 +327,7 @@ __device__ double test_expanded(uint32_t distance, int length, double give_up, c
       }
     }
     const uint32_t b = (uint32_t)(wb >> (8 * k)) & 255u;
-    sim_literal_bm(b, (uint32_t)(wm >> (8 * k)) & 255u, v, p);
+    sim_literal_bm<LM>(b, (uint32_t)(wm >> (8 * k)) & 255u, v, p);
     if (p < give_up) break;
     v.prev_byte = b;
   }
@@ -332,7 +357,7 @@ __device__ inline int cut_at(const Cuts &c, int k) { return k < c.n1 ? c.lo1 + k
 
 enum { W_STRICT = 0, W_LIT_DL = 1, W_DL_LIT = 2, W_EXPAND = 3, W_SPLIT = 4 };
 
-template <int R> __device__ void sim_any(uint32_t distance, int length, MS &sim, double &prob);   // Simulate_any_DL_Code, recursion_limit = R
+template <int LM, int R> __device__ void sim_any(uint32_t distance, int length, MS &sim, double &prob);   // Simulate_any_DL_Code, recursion_limit = R
 
 // The body of Generic_any_DL_Code (:740-832) up to its choice; NEW = new_recursion_limit.  The simulations it asks for nest at
 // most three deep (the limit goes down by one per level, :756-764), so the recursion of the reference unrolls into templates.
@@ -341,9 +366,9 @@ template <int R> __device__ void sim_any(uint32_t distance, int length, MS &sim,
 // Where the reference compares INDEPENDENT simulations -- literal + code against code + literal (:783-805), the cuts of
 // Test_Split_DL (:924-943) -- the lanes part: one simulation each, from their own copy of the state, nothing written but the
 // result; the results are then compared by all lanes in the reference's order.  Same doubles, a shorter critical path.
-__device__ int decide_with_helpers(uint32_t distance, int length, const MS &sim, int &best_cut);
-template <int NEW, bool PAR, bool HW = false> __device__ __forceinline__ int decide(uint32_t distance, int length, const MS &sim, int &best_cut, StrictRes &strict) {
-  if constexpr (PAR && HW) return decide_with_helpers(distance, length, sim, best_cut);
+template <int LM> __device__ int decide_with_helpers(uint32_t distance, int length, const MS &sim, int &best_cut);
+template <int LM, int NEW, bool PAR, bool HW = false> __device__ __forceinline__ int decide(uint32_t distance, int length, const MS &sim, int &best_cut, StrictRes &strict) {
+  if constexpr (PAR && HW) return decide_with_helpers<LM>(distance, length, sim, best_cut);
   double strict_dlc = 0.0, expanded_dlc = 0.0, soe = 0.0;
   [[maybe_unused]] const int lane = lane_id();
   if (s_E.cv >= 1) {
@@ -352,17 +377,17 @@ template <int NEW, bool PAR, bool HW = false> __device__ __forceinline__ int dec
 #endif
     strict = strict_factors(distance, length, sim);
     strict_dlc = strict.f1 * strict.f2;                                              // (Test_Strict_DL_Code starts from 1.0: 1.0 * f1 * f2)
-    expanded_dlc = test_expanded(distance, length, strict_dlc, sim);
+    expanded_dlc = test_expanded<LM>(distance, length, strict_dlc, sim);
     soe = strict_dlc > expanded_dlc ? strict_dlc : expanded_dlc;
 #ifdef ZADA_LZ_PROF
     if constexpr (PAR) { g_lzprof[7] += clock64() - prof_a; g_lzprof[0] += 1; }
 #endif
     if (length > 2) {
       const uint32_t b_head = TB((int64_t)sim.pos - (int64_t)distance);
-      const double head_lit = test_literal_byte(b_head, sim);
+      const double head_lit = test_literal_byte<LM>(b_head, sim);
       if (head_lit >= 0.875) return W_LIT_DL;                                      // Lit_then_DL_threshold :306
       MS after = sim;
-      after.state = t_lit(sim.state); after.pos = sim.pos + 1; after.pos_state = (uint32_t)after.pos & LZ_PBM; after.prev_byte = b_head;
+      after.state = t_lit(sim.state); after.pos = sim.pos + 1; after.pos_state = (uint32_t)after.pos & pbm<LM>(); after.prev_byte = b_head;
       const double malus_dtl = fmax0(0.135 - (double)distance * 1.0e-8 - (double)length * 1.0e-4);     // DL_code_then_Literal :869-889
       double dal, dtl;
       if constexpr (PAR) {
@@ -370,8 +395,8 @@ template <int NEW, bool PAR, bool HW = false> __device__ __forceinline__ int dec
         MS v = task == 0 ? after : sim;
         v.tw = 32;
         double p = task == 0 ? 1.0 : malus_dtl;
-        sim_any<NEW>(distance, length - 1, v, p);
-        if (task == 1) sim_literal(TB((int64_t)v.pos - (int64_t)distance), v, p);
+        sim_any<LM, NEW>(distance, length - 1, v, p);
+        if (task == 1) sim_literal<LM>(TB((int64_t)v.pos - (int64_t)distance), v, p);
         dal = __shfl(p, 0); dtl = __shfl(p, 32);
       } else if (sim.tw >= 2) {
         // the team that runs this simulation parts in two for the same pair (the halves run sim_any<NEW> in step, as the wave's halves do above)
@@ -379,16 +404,16 @@ template <int NEW, bool PAR, bool HW = false> __device__ __forceinline__ int dec
         MS v = task == 0 ? after : sim;
         v.tw = half;
         double p = task == 0 ? 1.0 : malus_dtl;
-        sim_any<NEW>(distance, length - 1, v, p);
-        if (task == 1) sim_literal(TB((int64_t)v.pos - (int64_t)distance), v, p);
+        sim_any<LM, NEW>(distance, length - 1, v, p);
+        if (task == 1) sim_literal<LM>(TB((int64_t)v.pos - (int64_t)distance), v, p);
         dal = __shfl(p, tb); dtl = __shfl(p, tb + half);
       } else {
         dal = 1.0;
-        sim_any<NEW>(distance, length - 1, after, dal);
+        sim_any<LM, NEW>(distance, length - 1, after, dal);
         MS v = sim;
         dtl = malus_dtl;
-        sim_any<NEW>(distance, length - 1, v, dtl);
-        sim_literal(TB((int64_t)v.pos - (int64_t)distance), v, dtl);
+        sim_any<LM, NEW>(distance, length - 1, v, dtl);
+        sim_literal<LM>(TB((int64_t)v.pos - (int64_t)distance), v, dtl);
       }
       if (head_lit * dal * fmax0(0.064 - (double)distance * 1.0e-9 - (double)length * 3.0e-5) > soe) return W_LIT_DL;
       if (dtl > soe) return W_DL_LIT;
@@ -412,9 +437,9 @@ template <int NEW, bool PAR, bool HW = false> __device__ __forceinline__ int dec
           double p = malus;
           MS v = sim;
           v.tw = tw;
-          sim_any<LOW>(distance, cut, v, p);
+          sim_any<LM, LOW>(distance, cut, v, p);
           pm = p; pf = p;
-          if (!(p <= soe)) { sim_any<LOW>(distance, length - cut, v, p); pf = p; }
+          if (!(p <= soe)) { sim_any<LM, LOW>(distance, length - cut, v, p); pf = p; }
         }
         for (int k = 0; k < nc; k++) {
           const double pmk = __shfl(pm, k * tw), pfk = __shfl(pf, k * tw);
@@ -434,9 +459,9 @@ template <int NEW, bool PAR, bool HW = false> __device__ __forceinline__ int dec
             double p = malus;
             MS v = sim;
             v.tw = 1;
-            sim_any<LOW>(distance, cut, v, p);
+            sim_any<LM, LOW>(distance, cut, v, p);
             pm = p; pf = p;
-            if (!(p <= soe)) { sim_any<LOW>(distance, length - cut, v, p); pf = p; }
+            if (!(p <= soe)) { sim_any<LM, LOW>(distance, length - cut, v, p); pf = p; }
           }
           for (int j = 0; j < tw && r * tw + j < nc; j++) {
             const double pmk = __shfl(pm, tb + j), pfk = __shfl(pf, tb + j);
@@ -449,9 +474,9 @@ template <int NEW, bool PAR, bool HW = false> __device__ __forceinline__ int dec
           if ((cut >= 4 && cut <= 9) || (rest >= 4 && rest <= 9)) {
             double p = malus;
             MS v = sim;
-            sim_any<LOW>(distance, cut, v, p);
+            sim_any<LM, LOW>(distance, cut, v, p);
             if (!(p <= soe)) {
-              sim_any<LOW>(distance, rest, v, p);
+              sim_any<LM, LOW>(distance, rest, v, p);
               if (p > best_prob) { best_prob = p; best_cut = cut; }
             }
           }
@@ -468,40 +493,40 @@ template <int NEW, bool PAR, bool HW = false> __device__ __forceinline__ int dec
 
 // (the state and the probability go in and come back BY VALUE -- 14 registers -- instead of through references into scratch)
 struct SimRes { MS sim; double prob; };
-template <int R> __device__ __noinline__ SimRes sim_any_impl(uint32_t distance, int length, MS sim, double prob) {
+template <int LM, int R> __device__ __noinline__ SimRes sim_any_impl(uint32_t distance, int length, MS sim, double prob) {
   if constexpr (R - 1 < 0) {
-    sim_strict(distance, length, sim, prob);
+    sim_strict<LM>(distance, length, sim, prob);
   } else {
     constexpr int NEW = R - 1;
     int cut = 2;
     StrictRes strict;
     const bool tested = s_E.cv >= 1;                                               // (Level_0 / Level_1 never come here: their codes are written strictly)
-    switch (decide<NEW, false>(distance, length, sim, cut, strict)) {
+    switch (decide<LM, NEW, false>(distance, length, sim, cut, strict)) {
       case W_LIT_DL:
-        sim_literal(TB((int64_t)sim.pos - (int64_t)distance), sim, prob);
-        sim_any<NEW>(distance, length - 1, sim, prob);
+        sim_literal<LM>(TB((int64_t)sim.pos - (int64_t)distance), sim, prob);
+        sim_any<LM, NEW>(distance, length - 1, sim, prob);
         break;
       case W_DL_LIT:
-        sim_any<NEW>(distance, length - 1, sim, prob);
-        sim_literal(TB((int64_t)sim.pos - (int64_t)distance), sim, prob);
+        sim_any<LM, NEW>(distance, length - 1, sim, prob);
+        sim_literal<LM>(TB((int64_t)sim.pos - (int64_t)distance), sim, prob);
         break;
       case W_EXPAND:
-        for (int x = 1; x <= length; x++) sim_literal(TB((int64_t)sim.pos - (int64_t)distance), sim, prob);
+        for (int x = 1; x <= length; x++) sim_literal<LM>(TB((int64_t)sim.pos - (int64_t)distance), sim, prob);
         break;
       case W_SPLIT:
-        sim_any<NEW>(distance, cut, sim, prob);
-        sim_any<NEW>(distance, length - cut, sim, prob);
+        sim_any<LM, NEW>(distance, cut, sim, prob);
+        sim_any<LM, NEW>(distance, length - cut, sim, prob);
         break;
       default:
-        if (tested) { prob = prob * strict.f1 * strict.f2; strict_apply(distance, length, strict, sim); }
-        else sim_strict(distance, length, sim, prob);
+        if (tested) { prob = prob * strict.f1 * strict.f2; strict_apply<LM>(distance, length, strict, sim); }
+        else sim_strict<LM>(distance, length, sim, prob);
     }
   }
   return SimRes{sim, prob};
 }
-template <int R> __device__ __forceinline__ void sim_any(uint32_t distance, int length, MS &sim, double &prob) {
-  if constexpr (R - 1 < 0) sim_strict(distance, length, sim, prob);      // limit used up (:761-764): no call in between
-  else { const SimRes r = sim_any_impl<R>(distance, length, sim, prob); sim = r.sim; prob = r.prob; }
+template <int LM, int R> __device__ __forceinline__ void sim_any(uint32_t distance, int length, MS &sim, double &prob) {
+  if constexpr (R - 1 < 0) sim_strict<LM>(distance, length, sim, prob);      // limit used up (:761-764): no call in between
+  else { const SimRes r = sim_any_impl<LM, R>(distance, length, sim, prob); sim = r.sim; prob = r.prob; }
 }
 
 // ---------------------------------------------------------------- range coder :964-1039
@@ -540,14 +565,14 @@ __device__ __forceinline__ void bit_tree_rev_encode(uint16_t *prob, int num_bits
 
 // ---------------------------------------------------------------- the machine :1045-1361
 
-__device__ __noinline__ void emit_literal(uint32_t b) {                   // LZ77_emits_literal_byte :1097-1130
+template <int LM> __device__ __noinline__ void emit_literal(uint32_t b) {                   // LZ77_emits_literal_byte :1097-1130
   PROF_T0;
   LzProbs &P = s_P;
   MS &S = s_E.ES;
-  const int idx = lit_idx(S.prev_byte);
+  const int idx = lit_idx<LM>(S.prev_byte, S.pos);
   const uint32_t b_match = TB((int64_t)S.pos - (int64_t)S.rep[0] - 1);
   if (b == b_match && S.pos > (uint64_t)(uint32_t)(S.rep[0] + 1) &&
-      (s_E.cv == 0 || test_short_rep(S) > test_simple_literal(b, b_match, idx, S))) {
+      (s_E.cv == 0 || test_short_rep(S) > test_simple_literal<LM>(b, b_match, idx, S))) {
     encode_bit(P.match[S.state][S.pos_state], 1);
     encode_bit(P.rep[S.state], 1);
     encode_bit(P.g0[S.state], 0);
@@ -555,7 +580,7 @@ __device__ __noinline__ void emit_literal(uint32_t b) {                   // LZ7
     S.state = t_srep(S.state);
   } else {
     encode_bit(P.match[S.state][S.pos_state], 0);
-    uint16_t *prob = P.lit + idx;
+    uint16_t *prob = lit_wr<LM>(idx);
     uint32_t symb = b | 0x100;
     if (S.state < 7) {
       do { encode_bit(prob[symb >> 8], (symb >> 7) & 1); symb <<= 1; } while (symb < 0x10000);
@@ -571,7 +596,7 @@ __device__ __noinline__ void emit_literal(uint32_t b) {                   // LZ7
     S.state = t_lit(S.state);
   }
   S.pos += 1;
-  S.pos_state = (uint32_t)S.pos & LZ_PBM;
+  S.pos_state = (uint32_t)S.pos & pbm<LM>();
   S.prev_byte = b;
   PROF_ADD(1);
 }
@@ -630,7 +655,7 @@ __device__ __noinline__ void write_repeat_match(int index_rm, uint32_t length) {
   S.state = t_rep(S.state);
 }
 
-__device__ __noinline__ void write_strict(uint32_t distance, int length) {   // Write_Strict_DL_Code :1288-1328
+template <int LM> __device__ __noinline__ void write_strict(uint32_t distance, int length) {   // Write_Strict_DL_Code :1288-1328
   MS &S = s_E.ES;
   const uint32_t dist_ip = distance - 1;
   int found = -1;
@@ -641,7 +666,7 @@ __device__ __noinline__ void write_strict(uint32_t distance, int length) {   // 
   else
     write_simple_match(dist_ip, (uint32_t)length);
   S.pos += (uint64_t)length;
-  S.pos_state = (uint32_t)S.pos & LZ_PBM;
+  S.pos_state = (uint32_t)S.pos & pbm<LM>();
   S.prev_byte = TB((int64_t)S.pos - 1);
 }
 
@@ -650,7 +675,7 @@ __device__ __noinline__ void write_strict(uint32_t distance, int length) {   // 
 // still to be written at `distance`, or the literal that follows a shortened match (:797-805).
 __shared__ uint16_t s_work[2 * 280];                                   // (every lane pushes and pops the same items: one copy in LDS, not 64 in scratch)
 // (inlined at its one call site, the kernel's main loop: as a function of its own it saved and restored 42 registers per call)
-template <bool HW> __device__ __forceinline__ void emit_dl(uint32_t distance, int length0) {
+template <int LM, bool HW> __device__ __forceinline__ void emit_dl(uint32_t distance, int length0) {
   PROF_T0;
   constexpr uint16_t POST_LIT = 0xFFFF;
   uint16_t *stack = s_work;
@@ -658,13 +683,13 @@ template <bool HW> __device__ __forceinline__ void emit_dl(uint32_t distance, in
   stack[sp++] = (uint16_t)length0;
   while (sp > 0) {
     const uint16_t it = stack[--sp];
-    if (it == POST_LIT) { emit_literal(TB((int64_t)s_E.ES.pos - (int64_t)distance)); continue; }
+    if (it == POST_LIT) { emit_literal<LM>(TB((int64_t)s_E.ES.pos - (int64_t)distance)); continue; }
     const int length = it;
     int cut = 2;
     StrictRes strict;
-    switch (decide<2, true, HW>(distance, length, s_E.ES, cut, strict)) {
+    switch (decide<LM, 2, true, HW>(distance, length, s_E.ES, cut, strict)) {
       case W_LIT_DL:
-        emit_literal(TB((int64_t)s_E.ES.pos - (int64_t)distance));
+        emit_literal<LM>(TB((int64_t)s_E.ES.pos - (int64_t)distance));
         stack[sp++] = (uint16_t)(length - 1);
         break;
       case W_DL_LIT:
@@ -672,14 +697,14 @@ template <bool HW> __device__ __forceinline__ void emit_dl(uint32_t distance, in
         stack[sp++] = (uint16_t)(length - 1);
         break;
       case W_EXPAND:
-        for (int x = 1; x <= length; x++) emit_literal(TB((int64_t)s_E.ES.pos - (int64_t)distance));
+        for (int x = 1; x <= length; x++) emit_literal<LM>(TB((int64_t)s_E.ES.pos - (int64_t)distance));
         break;
       case W_SPLIT:
         stack[sp++] = (uint16_t)(length - cut);
         stack[sp++] = (uint16_t)cut;
         break;
       default:
-        write_strict(distance, length);
+        write_strict<LM>(distance, length);
     }
   }
   PROF_ADD(2);
@@ -692,10 +717,10 @@ template <bool HW> __device__ __forceinline__ void emit_dl(uint32_t distance, in
 struct ScoreCtx { int old_index, last_pos_any; MS sim_new; double head_lit_prob; };
 __shared__ ScoreCtx s_S;
 
-__device__ double scoring2(MS state, int start);
+template <int LM> __device__ double scoring2(MS state, int start);
 
 // One candidate of Scoring (:1404-1468): the probability of the message that starts with match i of set m.
-template <int LEVEL> __device__ __forceinline__ double score_candidate(const MS &state, int start, int m, int i) {
+template <int LM, int LEVEL> __device__ __forceinline__ double score_candidate(const MS &state, int start, int m, int i) {
   const Matches &M = s_MM[m];
   const int old_index = s_S.old_index;
   const int mlen = M.len[i], last_pos_i = mlen + (m != old_index ? 1 : 0);
@@ -706,10 +731,10 @@ template <int LEVEL> __device__ __forceinline__ double score_candidate(const MS 
   if (m == old_index) trunc = mlen - start + 1;
   else if (start == 1) trunc = mlen;
   else trunc = mlen - start + 2;
-  if (trunc == 1) sim_literal(TB((int64_t)state.pos), t, p);
-  else sim_any<1>((uint32_t)M.dist[i], trunc, t, p);
+  if (trunc == 1) sim_literal<LM>(TB((int64_t)state.pos), t, p);
+  else sim_any<LM, 1>((uint32_t)M.dist[i], trunc, t, p);
   if constexpr (LEVEL < 2) {
-    if (last_pos_i < s_S.last_pos_any) p = p * scoring2(t, last_pos_i + 1);
+    if (last_pos_i < s_S.last_pos_any) p = p * scoring2<LM>(t, last_pos_i + 1);
   }
   return p;
 }
@@ -722,7 +747,7 @@ __device__ inline bool score2_takes(int m, int i, int start) {
   const int last_pos_i = s_MM[m].len[i] + (m != s_S.old_index ? 1 : 0);
   return last_pos_i >= start && last_pos_i >= s_S.last_pos_any;
 }
-__device__ __noinline__ double scoring2(MS state, int start) {
+template <int LM> __device__ __noinline__ double scoring2(MS state, int start) {
   const int tw = state.tw, lane = lane_id(), tl = lane & (tw - 1);
   const int c0 = s_MM[0].count, total = c0 + s_MM[1].count;
   int nq = 0;
@@ -740,7 +765,7 @@ __device__ __noinline__ double scoring2(MS state, int start) {
         if (score2_takes(k < c0 ? 0 : 1, (k < c0 ? k : k - c0) + 1, start)) { if (seen == mine) km = k; seen++; }
       MS st = state;
       st.tw = stw;
-      p = score_candidate<2>(st, start, km < c0 ? 0 : 1, (km < c0 ? km : km - c0) + 1);
+      p = score_candidate<LM, 2>(st, start, km < c0 ? 0 : 1, (km < c0 ? km : km - c0) + 1);
     }
     for (int off = stw; off < tw; off <<= 1) { const double o = __shfl_xor(p, off); p = o > p ? o : p; }     // (the lanes of a sub-team hold the same p)
     if (p > best) best = p;
@@ -775,7 +800,7 @@ __shared__ double s_Hp[2 * LZ_MAXM + 2][2];      // decide: [0] / [1] the pair, 
 constexpr int HELP_WAVES = ZADA_HELP_WAVES;
 
 // the cuts [k0, k1) of the posted decision, a team each
-__device__ void help_cuts(int k0, int k1) {
+template <int LM> __device__ void help_cuts(int k0, int k1) {
   const int n = k1 - k0, lane = lane_id();
   if (n <= 0) return;
   const int tw = team_width(n), task = lane / tw;
@@ -784,16 +809,16 @@ __device__ void help_cuts(int k0, int k1) {
     double p = s_H.malus;
     MS v = s_H.sim;
     v.tw = tw;
-    sim_any<1>(s_H.distance, cut, v, p);
+    sim_any<LM, 1>(s_H.distance, cut, v, p);
     const double pm = p;
     // (the reference goes on only if pm > the strict / expanded probability, :933: that one is still being worked out by wave 0 -- both parts
     // here, the test when wave 0 collects)
-    sim_any<1>(s_H.distance, s_H.length - cut, v, p);
+    sim_any<LM, 1>(s_H.distance, s_H.length - cut, v, p);
     if ((lane & (tw - 1)) == 0) { s_Hp[2 + k0 + task][0] = pm; s_Hp[2 + k0 + task][1] = p; }
   }
 }
 // wave w's share of the posted decision: with a pair, waves 1 and 2 take its two simulations and waves 0 and 3 the cuts; without, all four the cuts
-__device__ void help_decide(int w) {
+template <int LM> __device__ void help_decide(int w) {
   const int nc = s_H.nc;
   if (s_H.pair) {
     if (w == 1 || w == 2) {
@@ -801,17 +826,17 @@ __device__ void help_decide(int w) {
       MS v = t == 0 ? s_H.after : s_H.sim;
       v.tw = 64;
       double p = t == 0 ? 1.0 : s_H.malus_dtl;
-      sim_any<2>(s_H.distance, s_H.length - 1, v, p);
-      if (t == 1) sim_literal(TB((int64_t)v.pos - (int64_t)s_H.distance), v, p);
+      sim_any<LM, 2>(s_H.distance, s_H.length - 1, v, p);
+      if (t == 1) sim_literal<LM>(TB((int64_t)v.pos - (int64_t)s_H.distance), v, p);
       if (lane_id() == 0) s_Hp[t][0] = p;
     } else {
       const int j = w == 0 ? 0 : w - 2, m = HELP_WAVES - 2;            // (the waves that are not at the pair)
-      help_cuts(nc * j / m, nc * (j + 1) / m);
+      help_cuts<LM>(nc * j / m, nc * (j + 1) / m);
     }
-  } else help_cuts(nc * w / HELP_WAVES, nc * (w + 1) / HELP_WAVES);
+  } else help_cuts<LM>(nc * w / HELP_WAVES, nc * (w + 1) / HELP_WAVES);
 }
 // wave w's share of Scoring's candidates: w, w + 4, ...
-__device__ void help_score(int w) {
+template <int LM> __device__ void help_score(int w) {
   const int lane = lane_id(), c0 = s_MM[0].count, total = s_H.total;
   const int mine = total > w ? (total - w + HELP_WAVES - 1) / HELP_WAVES : 0;
   if (mine == 0) return;
@@ -822,17 +847,17 @@ __device__ void help_score(int w) {
     const int idx = base + lane / tw;
     if (idx < mine) {
       const int k = w + HELP_WAVES * idx;
-      const double p = score_candidate<1>(st, 1, k < c0 ? 0 : 1, (k < c0 ? k : k - c0) + 1);
+      const double p = score_candidate<LM, 1>(st, 1, k < c0 ? 0 : 1, (k < c0 ? k : k - c0) + 1);
       if ((lane & (tw - 1)) == 0) s_Hp[k][0] = p;
     }
   }
 }
-__device__ void helper_loop(int w) {
+template <int LM> __device__ void helper_loop(int w) {
   for (;;) {
     __syncthreads();                                                   // (A) a fork is posted
     const int cmd = s_H.cmd;
     if (cmd == 0) return;
-    if (cmd == 1) help_decide(w); else help_score(w);
+    if (cmd == 1) help_decide<LM>(w); else help_score<LM>(w);
     __syncthreads();                                                   // (B) the shares are done
   }
 }
@@ -844,15 +869,15 @@ template <bool HW> __device__ __forceinline__ void helpers_release() {          
 }
 
 // decide <2, true> of the wave that walks the chain, its independent simulations on the helpers
-__device__ int decide_with_helpers(uint32_t distance, int length, const MS &sim, int &best_cut) {
+template <int LM> __device__ int decide_with_helpers(uint32_t distance, int length, const MS &sim, int &best_cut) {
   const bool pair = length > 2;
   double head_lit = 0.0, malus_dtl = 0.0;
   MS after = sim;
   if (pair) {
     const uint32_t b_head = TB((int64_t)sim.pos - (int64_t)distance);
-    head_lit = test_literal_byte(b_head, sim);
+    head_lit = test_literal_byte<LM>(b_head, sim);
     if (head_lit >= 0.875) return W_LIT_DL;                                          // Lit_then_DL_threshold :306
-    after.state = t_lit(sim.state); after.pos = sim.pos + 1; after.pos_state = (uint32_t)after.pos & LZ_PBM; after.prev_byte = b_head;
+    after.state = t_lit(sim.state); after.pos = sim.pos + 1; after.pos_state = (uint32_t)after.pos & pbm<LM>(); after.prev_byte = b_head;
     malus_dtl = fmax0(0.135 - (double)distance * 1.0e-8 - (double)length * 1.0e-4);  // DL_code_then_Literal :869-889
   }
   const double malus = fmax0(0.27 - (double)distance * 2.0e-6);                      // Test_Split_DL :901-944
@@ -869,10 +894,10 @@ __device__ int decide_with_helpers(uint32_t distance, int length, const MS &sim,
   // the strict and the expanded code (:661-726) on this wave while the helpers are at the pair
   const StrictRes strict = strict_factors(distance, length, sim);
   const double strict_dlc = strict.f1 * strict.f2;
-  const double expanded_dlc = test_expanded(distance, length, strict_dlc, sim);
+  const double expanded_dlc = test_expanded<LM>(distance, length, strict_dlc, sim);
   const double soe = strict_dlc > expanded_dlc ? strict_dlc : expanded_dlc;
   if (fork) {
-    help_decide(0);
+    help_decide<LM>(0);
     __syncthreads();                                                   // (B)
   }
   const bool split = !(malus < soe);
@@ -893,11 +918,11 @@ __device__ int decide_with_helpers(uint32_t distance, int length, const MS &sim,
 }
 
 // scoring_top of the wave that walks the chain, the candidates dealt over the four waves
-__device__ void scoring_with_helpers(const MS &state, int &index, int &match_set) {
+template <int LM> __device__ void scoring_with_helpers(const MS &state, int &index, int &match_set) {
   const int c0 = s_MM[0].count, total = c0 + s_MM[1].count;
   if (lane_id() == 0) { s_H.cmd = 2; s_H.sim = state; s_H.total = total; }
   __syncthreads();                                                     // (A)
-  help_score(0);
+  help_score<LM>(0);
   __syncthreads();                                                     // (B)
   double prob = 0.0;
   for (int kk = 0; kk < total; kk++) {
@@ -908,8 +933,8 @@ __device__ void scoring_with_helpers(const MS &state, int &index, int &match_set
 
 // Scoring at level 1, start 1, called from the chain (all lanes in step): every match of both sets is a candidate (their
 // last positions are >= 1), a team of lanes each; the best is then picked by all lanes in the reference's order (first strict maximum).
-template <bool HW> __device__ __forceinline__ void scoring_top(const MS &state, int &index, int &match_set) {
-  if constexpr (HW) { scoring_with_helpers(state, index, match_set); return; }
+template <int LM, bool HW> __device__ __forceinline__ void scoring_top(const MS &state, int &index, int &match_set) {
+  if constexpr (HW) { scoring_with_helpers<LM>(state, index, match_set); return; }
   const int lane = lane_id(), c0 = s_MM[0].count, total = c0 + s_MM[1].count;
   const int tw = team_width(total), per_round = 64 / tw;                           // a team of tw lanes per candidate
   MS st = state;
@@ -918,7 +943,7 @@ template <bool HW> __device__ __forceinline__ void scoring_top(const MS &state, 
   for (int base = 0; base < total; base += per_round) {
     const int k = base + lane / tw;
     double p = 0.0;
-    if (k < total) p = score_candidate<1>(st, 1, k < c0 ? 0 : 1, (k < c0 ? k : k - c0) + 1);
+    if (k < total) p = score_candidate<LM, 1>(st, 1, k < c0 ? 0 : 1, (k < c0 ? k : k - c0) + 1);
     const int cnt = total - base < per_round ? total - base : per_round;
     for (int j = 0; j < cnt; j++) {
       const double pj = __shfl(p, j * tw);
@@ -928,7 +953,7 @@ template <bool HW> __device__ __forceinline__ void scoring_top(const MS &state, 
   }
 }
 
-template <bool HW> __device__ void estimate_dl_codes(int old_index, uint32_t prefix1, int &best_index, int &best_set) {
+template <int LM, bool HW> __device__ void estimate_dl_codes(int old_index, uint32_t prefix1, int &best_index, int &best_set) {
   PROF_T0;
   int last_pos_any = 0;
   for (int m = 0; m <= 1; m++)
@@ -938,12 +963,12 @@ template <bool HW> __device__ void estimate_dl_codes(int old_index, uint32_t pre
     }
   MS sim_new = s_E.ES;
   double head_lit_prob = 1.0;
-  sim_literal(prefix1, sim_new, head_lit_prob);
+  sim_literal<LM>(prefix1, sim_new, head_lit_prob);
   s_S.old_index = old_index; s_S.last_pos_any = last_pos_any; s_S.sim_new = sim_new; s_S.head_lit_prob = head_lit_prob;
   chain_sync<HW>();
   best_index = 1; best_set = old_index;
   const MS sim_old = s_E.ES;
-  scoring_top<HW>(sim_old, best_index, best_set);
+  scoring_top<LM, HW>(sim_old, best_index, best_set);
   PROF_ADD(3);
 }
 
@@ -1122,7 +1147,7 @@ __device__ __forceinline__ Symbol lz_send_dl(int distance, int length) {        
 __device__ __forceinline__ Symbol lz_send_literal() { s_B.readAhead--; return Symbol{0, 0u, s_B.cur_literal}; }
 __device__ inline void lz_skip(int len) { PROF_T0; s_B.readAhead += len; bt_skip(len); PROF_ADD(5); }
 
-template <bool HW> __device__ __forceinline__ Symbol lz_next_symbol() {       // Get_Next_Symbol :1605-1796
+template <int LM, bool HW> __device__ __forceinline__ Symbol lz_next_symbol() {       // Get_Next_Symbol :1605-1796
   constexpr int hurdle = 40;
   if (s_B.readAhead == -1) lz_read_one<HW>(s_B.cur);
   s_B.cur_literal = BUF(s_B.readPos);
@@ -1163,7 +1188,7 @@ template <bool HW> __device__ __forceinline__ Symbol lz_next_symbol() {       //
       lz_reduce(s_B.cur);
       lz_supplement(s_B.cur);
       int idx = 1, set = 1 - s_B.cur;
-      estimate_dl_codes<HW>(1 - s_B.cur, s_B.cur_literal, idx, set);
+      estimate_dl_codes<LM, HW>(1 - s_B.cur, s_B.cur_literal, idx, set);
       if (set == 1 - s_B.cur) { main_len = s_MM[set].len[idx]; main_dist = s_MM[set].dist[idx]; }
       else return lz_send_literal();
     }
@@ -1206,6 +1231,12 @@ struct LzSave {
 constexpr uint64_t LZ_SAVE_STRIDE = (sizeof(LzSave) + 63) & ~63ull;
 static_assert(sizeof(ScoreCtx) % 4 == 0 && sizeof(LzProbs) % 4 == 0 && sizeof(Matches) % 4 == 0 && sizeof(Enc) % 4 == 0 && sizeof(BT4) % 4 == 0, "word copies");
 
+// the props byte lc + 9 lp + 45 pb (lzma-encoding.adb Write_LZMA_header); 93 = (3, 0, 2)
+template <int LM> __device__ __forceinline__ uint32_t props(const LzmaJob &J) {
+  if constexpr (LM == LM_DEF) return 93u;
+  else return (uint32_t)(J.lc + 9 * J.lp + 45 * J.pb);
+}
+
 template <typename T> __device__ inline void words_out(T *dst, const T &src) {
   const uint32_t *s = (const uint32_t *)&src; uint32_t *d = (uint32_t *)dst;
   for (uint32_t i = threadIdx.x; i < sizeof(T) / 4; i += 64) d[i] = s[i];
@@ -1215,14 +1246,17 @@ template <typename T> __device__ inline void words_in(T &dst, const T *src) {
   for (uint32_t i = threadIdx.x; i < sizeof(T) / 4; i += 64) d[i] = s[i];
 }
 
-template <bool HW> __global__ void __launch_bounds__(HW ? 64 * HELP_WAVES : 64, 2) k_lzma_encode(const LzmaJob *jobs, const uint32_t *order, const uint8_t *in_base, const uint32_t *tok_base, uint8_t *out_base,
-                                                    Bt4Sets sets, uint64_t *result, uint8_t *save_base, uint64_t budget, uint64_t pos_cap) {
+template <bool HW, int LM> __global__ void __launch_bounds__(HW ? 64 * HELP_WAVES : 64, 2) k_lzma_encode(const LzmaJob *jobs, const uint32_t *order, const uint8_t *in_base, const uint32_t *tok_base, uint8_t *out_base,
+                                                    Bt4Sets sets, uint64_t *result, uint8_t *save_base, uint64_t budget, uint64_t pos_cap, uint16_t *lit_base) {
   LzProbs &P = s_P;
   const uint32_t job = order ? order[blockIdx.x] : blockIdx.x;      // the longest entries first: workgroups start in index order
   const LzmaJob J = jobs[job];
   LzSave *S = save_base ? (LzSave *)(save_base + job * LZ_SAVE_STRIDE) : nullptr;
   const uint32_t phase = S ? S->phase : 0u;
   if (phase == 2) return;                                           // (coded by an earlier launch of this call)
+  if constexpr (LM != LM_DEF) {                                     // (before the barrier of either branch below)
+    if (threadIdx.x == 0) { s_L.lc = (uint32_t)J.lc; s_L.lpm = (1u << J.lp) - 1u; s_L.pbm = (1u << J.pb) - 1u; s_L.lit = LM == LM_HBM ? lit_base + J.lit_off : nullptr; }
+  }
   uint64_t iter = 0;
   bool running = false;
   if (phase == 1) {
@@ -1241,7 +1275,7 @@ template <bool HW> __global__ void __launch_bounds__(HW ? 64 * HELP_WAVES : 64, 
     __syncthreads();
   }
   // (the kernel of a stream alone, 256 threads: the waves behind the first are its helpers from here on -- "one stream on four waves")
-  if constexpr (HW) { if (threadIdx.x >= 64u) { helper_loop((int)(threadIdx.x >> 6)); return; } }
+  if constexpr (HW) { if (threadIdx.x >= 64u) { helper_loop<LM>((int)(threadIdx.x >> 6)); return; } }
 #ifdef ZADA_LZ_PROF
   const unsigned long long prof_k0 = clock64();
   for (int i = 0; i < 8; i++) g_lzprof[i] = 0;
@@ -1255,7 +1289,7 @@ template <bool HW> __global__ void __launch_bounds__(HW ? 64 * HELP_WAVES : 64, 
     s_E.out = out_base + J.out_off; s_E.cap = J.cap; s_E.olen = 0;
     s_E.verify = J.level == 3 ? (uint32_t)J.verify : 0u; s_E.defect = 0;
     if (J.zip_prefix) { put_byte(16); put_byte(2); put_byte(5); put_byte(0); }   // zip-compress-lzma_e.adb:155-158
-    put_byte(3 + 9 * 0 + 45 * 2);                                                   // Write_LZMA_header :1513-1536
+    put_byte(props<LM>(J));                                                         // Write_LZMA_header :1513-1536
     for (int i = 0; i < 4; i++) put_byte((J.sbs >> (8 * i)) & 255);
     if (J.level == 3) running = lz_bt4_begin((int)J.sbs, J.in_off, sets);
   }
@@ -1285,16 +1319,17 @@ template <bool HW> __global__ void __launch_bounds__(HW ? 64 * HELP_WAVES : 64, 
       iter++;
     } else {
       if (!running) break;
-      sy = lz_next_symbol<HW>();
+      sy = lz_next_symbol<LM, HW>();
       if (bt_available() == 0 && bt_fill_window((int)J.sbs) == 0) running = false;    // (the window's bookkeeping: nothing the emission reads)
     }
-    if (sy.length) emit_dl<HW>(sy.distance, sy.length); else emit_literal(sy.literal);
+    if (sy.length) emit_dl<LM, HW>(sy.distance, sy.length); else emit_literal<LM>(sy.literal);
   }
   if (!done) {
     chain_sync<HW>();
     words_out(&S->P, s_P); words_out(&S->MM[0], s_MM[0]); words_out(&S->MM[1], s_MM[1]); words_out(&S->E, s_E); words_out(&S->B, s_B);
     if (threadIdx.x == 0) {
-      S->phase = 1; S->running = (running ? 1u : 0u) | ((uint32_t)J.level << 8); S->iter = iter;      // (the level: lzma_save_fits)
+      // (the level and, in bits 16 .. 23, the props byte XOR that of LZMA_0 .. LZMA_3: lzma_save_fits; a state of those methods reads as it always did)
+      S->phase = 1; S->running = (running ? 1u : 0u) | ((uint32_t)J.level << 8) | ((props<LM>(J) ^ 93u) << 16); S->iter = iter;
       result[2 * job] = s_E.olen;
       result[2 * job + 1] = s_E.ES.pos | (1ull << 63);                             // bit 63: more to come
     }
@@ -1363,19 +1398,26 @@ int lzma_save_info(const uint8_t *blob, uint64_t *pos, uint64_t *olen, uint64_t 
 int lzma_save_fits(const uint8_t *blob, const LzmaJob &J) {
   const LzSave *S = (const LzSave *)blob;
   if (S->phase != 1 || S->E.n != J.n || S->E.ES.pos > J.n) return 0;   // (olen beyond the caller's room is the coder's ordinary "counted, not written")
-  if ((int32_t)(S->running >> 8) != J.level || (S->running & 0xFEu)) return 0;
+  if ((int32_t)(S->running >> 8 & 0xFFu) != J.level || (S->running & 0xFF0000FEu)) return 0;
+  if ((S->running >> 16 & 0xFFu) != ((uint32_t)(J.lc + 9 * J.lp + 45 * J.pb) ^ 93u)) return 0;      // (lc, lp, pb: the method's, not only its level)
   if (J.level < 3) return S->iter <= (J.level == 0 ? J.n : J.ntok);   // (next byte / next token)
   if ((uint64_t)(uint32_t)S->B.sbs != J.sbs || S->B.base != J.in_off || S->B.in_pos > J.n) return 0;
   if (S->B.buf_len < 0 || S->B.readPos < -1 || S->B.readPos > S->B.buf_len || S->B.writePos < 0 || S->B.writePos > S->B.buf_len || S->B.readLimit > S->B.buf_len) return 0;
   return 1;
 }
 int lzma_launch(Ctx *c, const LzmaJob *d_jobs, const uint32_t *d_order, uint32_t count, const uint8_t *d_in, const uint32_t *d_tok, uint8_t *d_out, const Bt4Sets &sets, uint64_t *d_result,
-                uint8_t *d_save, uint64_t budget, uint64_t pos_cap, int waves) {
+                uint8_t *d_save, uint64_t budget, uint64_t pos_cap, int waves, int lit_home, uint16_t *d_lit) {
   if (count == 0) return 0;
-  if (waves > 1)                                                     // (the chain's wave and HELP_WAVES - 1 helpers)
-    hipLaunchKernelGGL(k_lzma_encode<true>, dim3(count), dim3(64 * HELP_WAVES), 0, c->stream, d_jobs, d_order, d_in, d_tok, d_out, sets, d_result, d_save, d_save ? budget : 0ull, pos_cap);
-  else
-  hipLaunchKernelGGL(k_lzma_encode<false>, dim3(count), dim3(64), 0, c->stream, d_jobs, d_order, d_in, d_tok, d_out, sets, d_result, d_save, d_save ? budget : 0ull, pos_cap);
+  if (lit_home < LM_DEF || lit_home > LM_HBM || (lit_home == LM_HBM && !d_lit)) { c->err = "k_lzma_encode: no literal table"; return ZADA_E_INVALID; }
+  const uint64_t bud = d_save ? budget : 0ull;
+  auto go = [&](auto hw, auto lm) {                                  // (hw: the chain's wave and HELP_WAVES - 1 helpers)
+    hipLaunchKernelGGL((k_lzma_encode<decltype(hw)::value, decltype(lm)::value>), dim3(count), dim3(decltype(hw)::value ? 64 * HELP_WAVES : 64), 0, c->stream,
+                       d_jobs, d_order, d_in, d_tok, d_out, sets, d_result, d_save, bud, pos_cap, d_lit);
+  };
+  using T = std::true_type; using F = std::false_type;
+  using L0 = std::integral_constant<int, LM_DEF>; using L1 = std::integral_constant<int, LM_LDS>; using L2 = std::integral_constant<int, LM_HBM>;
+  if (waves > 1) { if (lit_home == LM_DEF) go(T(), L0()); else if (lit_home == LM_LDS) go(T(), L1()); else go(T(), L2()); }
+  else { if (lit_home == LM_DEF) go(F(), L0()); else if (lit_home == LM_LDS) go(F(), L1()); else go(F(), L2()); }
   return hip_check(c, hipGetLastError(), "k_lzma_encode") ? ZADA_E_HIP : 0;
 }
 
