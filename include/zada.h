@@ -33,7 +33,12 @@ enum {
   ZADA_DEFLATE_1 = 8,       /* IZ_6  (8,16,128,128),   1 scan level     (:1576, lz77.adb:542) */
   ZADA_DEFLATE_2 = 9,       /* IZ_8  (32,128,258,1024), 2 scan levels   (:1577, lz77.adb:544) */
   ZADA_DEFLATE_3 = 10,      /* IZ_10 (34,258,258,4096), 3 scan levels   (:1578, lz77.adb:546) */
-  ZADA_DEFLATE_R = 11,      /* LZ77.Rich -- not implemented (out of scope) */
+  ZADA_DEFLATE_R = 11,      /* LZ77.Rich (lz77.adb:1829-2143) behind Deflate_3's entropy stage (:1310-1311, 1573-1579).  Rich parses
+                             * every 8 KiB sector of an entry afresh; its comparisons read up to 257 bytes past the bytes it has
+                             * loaded, where its ring still holds the bytes 32 KiB earlier -- or, in the ring's first lap, bytes it
+                             * never wrote (an uninitialised array in the reference).  Convention: UNWRITTEN BYTES READ AS 0.  This
+                             * can change a match choice near a sector's end in an entry's first 32 KiB and at its end; the stream
+                             * is always valid Deflate.   */
   ZADA_BZIP2_1 = 12,        /* BZip2, 100 000-byte blocks  (zip-compress-bzip2_e.adb:138-142, bzip2-encoding.adb:93-98) */
   ZADA_BZIP2_2 = 13,        /* BZip2, 400 000-byte blocks */
   ZADA_BZIP2_3 = 14,        /* BZip2, 900 000-byte blocks, four splitting tactics per block (bzip2-encoding.adb:1214-1345) */

@@ -21,7 +21,7 @@ LIB_PATH = os.environ.get("ZADA_LIB", os.path.join(_HERE, "libzada_hip.so"))   #
 
 
 class Method:
-    """Compression_Method'Pos, zip-compress.ads:59-122.  Shrink, Reduce and Deflate_R are not implemented; the Preselection methods pick
+    """Compression_Method'Pos, zip-compress.ads:59-122.  Shrink and Reduce are not implemented; the Preselection methods pick
     one of the others per entry (preselect)."""
     Store = 0
     Shrink_1 = 1

@@ -460,6 +460,7 @@ static int method_level(int method) {
     case ZADA_DEFLATE_1: return 6;
     case ZADA_DEFLATE_2: return 8;
     case ZADA_DEFLATE_3: return 10;
+    case ZADA_DEFLATE_R: return RICH_LEVEL;   // LZ77.Rich (zada_rich.hip)
     default: return -1;
   }
 }
@@ -598,6 +599,7 @@ int range_lz(Ctx *c, const GlobalState *entry, zada_feedback_fn fb, void *user) 
     job.dst_atoms = W.ea_atoms + LB_CAP + R.T; job.dst_apos = W.ea_apos + LB_CAP + R.T;
     job.apos_bias = (uint32_t)boff;
     job.cap_atoms = W.cap_atoms - R.T;
+    job.gpos = gbuf;
     if (arr) job.need = [&, boff, nbuf, pa](uint64_t upto) -> int {
       if (upto > nbuf) upto = nbuf;
       if (upto <= copied) return 0;
@@ -2059,7 +2061,7 @@ int zada_deflate_batch(zada_ctx *z, int method, int count, const uint8_t *const 
   int worst = 0;
   // Entries of up to 4 MiB go through ONE launch sequence, as many at a time as the workspace takes (batch_core); larger
   // ones fill the GPU by themselves and are compressed one after the other.
-  const bool batchable = method >= ZADA_DEFLATE_FIXED && method <= ZADA_DEFLATE_3;
+  const bool batchable = method >= ZADA_DEFLATE_FIXED && method <= ZADA_DEFLATE_R;     // (Deflate_R: the 32 KiB slots start on sectors)
   std::vector<int> group;
   uint64_t gbytes = 0;
   auto flush_group = [&]() {

@@ -383,9 +383,14 @@ struct ShardJob {
   // need (x): the first x bytes of W.in are to be valid before whatever is enqueued next on the context's stream runs (null: all of
   // them are).  The host-buffer entry point's input arrives piece by piece while the first kernel already works on what has come.
   std::function<int(uint64_t)> need;
+  uint64_t gpos = 0;                  // one stream: the stream offset of W.in [0] (Deflate_R: where the ring's first lap ends)
 };
 struct ShardResult { uint32_t ntok = 0; ExitState exit{0, SYNC_F}, warm{0, SYNC_F}; };
 int lz_shard(Ctx *c, int level, const ShardJob &job, ShardResult *res);
+// Deflate_R (zada_rich.hip): LZ77.Rich instead of the Info-Zip matcher.  Every 8 KiB sector is parsed afresh, so the state a
+// shard hands on is always "fresh at the boundary" (exit = end of the shard, SYNC_F).
+constexpr int RICH_LEVEL = 11;
+int rich_shard(Ctx *c, const ShardJob &job, ShardResult *res);
 
 int ensure_batch_workspace(Ctx *c, uint64_t entries, uint64_t fslots, uint64_t segs);
 int batch_geometry(Ctx *c, uint32_t E, const uint32_t *d_total_atoms);

@@ -2330,6 +2330,7 @@ int lz_shard(Ctx *c, int level, const ShardJob &job, ShardResult *res) {
   const uint64_t n = job.nbuf;
   res->ntok = 0; res->exit = ExitState{(uint32_t)n, SYNC_F}; res->warm = ExitState{job.tok_lo, SYNC_F};
   if (n == 0) return 0;
+  if (level == RICH_LEVEL) return rich_shard(c, job, res);
   if (job.need && (level == 0 || n < 32768 + 2)) { if (int rn = job.need(n)) return rn; }      // (no segments to go by: everything first)
   if (level == 0 && job.segend) {                  // a batch: the chunks' byte counts stand for their token counts (zada_api.hip, batch_core)
     const uint32_t nch = (uint32_t)((n + PCHUNK - 1) / PCHUNK);
