@@ -172,6 +172,36 @@ int zada_preselect(int method, int content_hint, int input_size_known, uint64_t 
 int zada_compress_data_hint(zada_ctx *ctx, int method, int content_hint, const uint8_t *in, uint64_t n, uint8_t *out,
                             uint64_t cap, uint64_t *out_len, uint32_t *crc_out, uint16_t *zip_type, int *method_used);
 
+/* ---- Password-protected entries: Zip.CRC_Crypto (zip-crc_crypto.adb:78-137) ---------------------------------------
+ * The traditional Zip cipher.  Update_keys (:90-99) per plaintext byte is three first-order recurrences -- a prefix CRC of the
+ * plaintext (key 0), x' = (x + lsb (key 0)) * 134775813 + 1 in Z / 2**32 (key 1), a prefix CRC of the bytes key 1 >> 24 (key 2) --
+ * so the keys at every 256-byte boundary come from three rounds of "summary per piece, scan over the pieces" on the device, and the
+ * pieces are then encoded independently (csrc/zada_crypt.hip).  keys[3] is Crypto_Pack.keys, in and out. */
+/* Init_Keys (:110-116): the keys of a password, one byte per Character'Pos.  Pure host code, no context. */
+void zada_crypt_init_keys(const uint8_t *password, uint64_t len, uint32_t keys[3]);
+/* The 12-byte encryption header of Compress_data_single_method (zip-compress.adb:153-161): random11, then crc_final >> 24, through Encode;
+ * out12 receives the encoded header and keys are advanced over it (they are mem_encrypt_pack, :166, afterwards).  The reference draws the
+ * eleven bytes from a generator it seeds from the clock (Reset (cg), :153); here they are the caller's.  Pure host code, no context. */
+void zada_crypt_header(uint32_t keys[3], const uint8_t random11[11], uint32_t crc_final, uint8_t out12[12]);
+/* Encode (:118-128) of n bytes in place, in host memory / at a device address (any alignment; 16-byte aligned is the fast path).  Calling
+ * them piece after piece gives the bytes and keys of one call over the whole buffer: what replaces the loop of Write_Block
+ * (zip-compress.adb:487) one buffer at a time.  n = 0 is a no-op. */
+int zada_crypt_encode(zada_ctx *ctx, uint32_t keys[3], uint8_t *buf, uint64_t n);
+int zada_crypt_encode_device(zada_ctx *ctx, uint32_t keys[3], void *d_buf, uint64_t n);
+/* `count` independent buffers (one per Zip entry), each with its own keys, in place: buffers of up to 256 KiB take one wave each in ONE
+ * launch (256 MiB of them at a time), longer ones go through zada_crypt_encode one after the other. */
+int zada_crypt_encode_batch(zada_ctx *ctx, int count, uint32_t (*keys)[3], uint8_t *const *buf, const uint64_t *n);
+/* Zip.Compress.Compress_Data with a password (Compress_data_single_method with is_encrypted, zip-compress.adb:142-241), in the
+ * reference's order: Init_Keys, the CRC-32 of the input in a scan of its own (:152), the header from random11 and that CRC, the keys kept
+ * as they stand behind it (:166), the encoder, Encode of its stream in device memory before it is copied back; where compression_ok =
+ * False (the unencrypted stream is not smaller than n, Write_Block :479-486) the input itself is encoded from the kept keys (:224-237).
+ * out receives the header and the payload, *out_len = payload + 12 (:238-240): cap >= n + 12 always suffices.  method may be Store or a
+ * Preselection method (content_hint as in zada_compress_data_hint; ZADA_HINT_NEUTRAL for a single method); *method_used may be NULL.
+ * pw_len = 0 is ZADA_E_INVALID: the unencrypted call is zada_compress_data. */
+int zada_compress_data_pw(zada_ctx *ctx, int method, int content_hint, const uint8_t *password, uint64_t pw_len, const uint8_t random11[11],
+                          const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len, uint32_t *crc_out,
+                          uint16_t *zip_type, int *method_used);
+
 /* ---- One stream over several contexts (GPUs) -------------------------------------------------------------------
  * The reference compresses an entry as ONE sequential stream (a 32 KiB window, a lazy-match state machine, a flush of the
  * LZ buffer every 65 536 atoms and the block chooser's state all run through it: lz77.adb:827-933,

@@ -8,6 +8,7 @@ toolchain exists in the build image, so the host side above the C ABI is written
     Zip.Compress.Deflate      zip_lib/zip-compress-deflate.ads:36-46 -> `Encoder.deflate`
     Zip.Compress.Compress_Data zip_lib/zip-compress.ads:169-180 -> `Encoder.compress_data`
     Zip.Create (Create_Archive / Add_Stream / Finish) zip_lib/zip-create.ads:75-211 -> `ZipCreate`
+    Zip.CRC_Crypto (Init_Keys / Encode) zip_lib/zip-crc_crypto.adb:90-128 -> `Encoder.crypt_*`, `password=` of `compress_data` / `ZipCreate`
 
 All compute runs in libzada_hip.so (hand-written HIP for gfx950).  There is no CPU fallback:
 loading fails loudly when the library or a GPU is missing.
@@ -164,6 +165,15 @@ def load_library():
         L.zada_guess_type_from_name.argtypes = [ctypes.c_char_p]
         L.zada_preselect.argtypes = [i32, i32, i32, u64]
         L.zada_compress_data_hint.argtypes = [vp, i32, i32, vp, u64, vp, u64, u64p, u32p, vp, vp]
+    if hasattr(L, "zada_crypt_encode"):              # (likewise: ZipCrypto)
+        L.zada_crypt_init_keys.restype = None
+        L.zada_crypt_init_keys.argtypes = [ctypes.c_char_p, u64, u32p]
+        L.zada_crypt_header.restype = None
+        L.zada_crypt_header.argtypes = [u32p, ctypes.c_char_p, ctypes.c_uint32, vp]
+        L.zada_crypt_encode.argtypes = [vp, u32p, vp, u64]
+        L.zada_crypt_encode_device.argtypes = [vp, u32p, vp, u64]
+        L.zada_crypt_encode_batch.argtypes = [vp, i32, vp, vp, vp]
+        L.zada_compress_data_pw.argtypes = [vp, i32, i32, ctypes.c_char_p, u64, ctypes.c_char_p, vp, u64, vp, u64, u64p, u32p, ctypes.POINTER(ctypes.c_uint16), vp]
     L.zada_bz2_last_blocks.restype = ctypes.c_uint64
     L.zada_bz2_last_blocks.argtypes = [vp, vp, u64]
     L.zada_crc32_combine.restype = ctypes.c_uint32
@@ -186,6 +196,14 @@ class _ParseState(ctypes.Structure):
 
 class _RangeInfo(ctypes.Structure):
     _fields_ = [("atoms", ctypes.c_uint64), ("exit", _ParseState), ("warm", _ParseState), ("crc_raw", ctypes.c_uint32), ("entry_known", ctypes.c_uint32)]
+
+
+def _password(password):
+    """A password as the bytes Init_Keys sees: Character'Pos of every character, i.e. Latin-1 (zip-crc_crypto.adb:110-116)."""
+    pw = password.encode("latin-1") if isinstance(password, str) else bytes(password)
+    if not pw:
+        raise ZadaError("empty password (Password = \"\" means no encryption, zip-create.adb:221)")
+    return pw
 
 
 def _addr(buf):
@@ -484,11 +502,25 @@ class Encoder:
             self._err(rc, "zada_deflate_device")
         return rc, ol.value, c.value
 
-    def compress_data(self, data, method=Method.Deflate_3, content_hint=None):
-        """Zip.Compress.Compress_Data (no password): returns (payload bytes, final CRC-32, zip_type) with the Store fallback applied.
+    def compress_data(self, data, method=Method.Deflate_3, content_hint=None, password=None, header=None):
+        """Zip.Compress.Compress_Data: returns (payload bytes, final CRC-32, zip_type) with the Store fallback applied.
         With a content_hint (ContentType) the method may be a Preselection method: the entry's method is then chosen by the content hint
-        and len(data) (zada_compress_data_hint, preselect).  Without one, a single method."""
+        and len(data) (zada_compress_data_hint, preselect).  Without one, a single method.
+        With a password (bytes, or str taken as Latin-1) the payload is the 12-byte encryption header followed by the encoded stream
+        (zada_compress_data_pw); `header` holds the header's eleven random bytes (default: os.urandom (11))."""
         n = len(data)
+        if password is not None:
+            pw = _password(password)
+            h11 = os.urandom(11) if header is None else bytes(header)
+            if len(h11) != 11:
+                raise ZadaError("header: eleven bytes")
+            out = ctypes.create_string_buffer(n + 64 + 12)
+            ol, c, zt = ctypes.c_uint64(0), ctypes.c_uint32(0), ctypes.c_uint16(0)
+            rc = self.lib.zada_compress_data_pw(self.ctx, method, ContentType.neutral if content_hint is None else int(content_hint), pw, len(pw), h11,
+                                                _addr(data) if n else None, n, ctypes.addressof(out), n + 64 + 12, ctypes.byref(ol), ctypes.byref(c), ctypes.byref(zt), None)
+            if rc != 0:
+                self._err(rc, "zada_compress_data_pw")
+            return out.raw[:ol.value], c.value, zt.value
         if method == Method.Store:
             import zlib  # CRC of stored data only; not on the Deflate path
             return bytes(data), zlib.crc32(data) & 0xFFFFFFFF, 0
@@ -505,6 +537,58 @@ class Encoder:
         if rc != 0:
             self._err(rc, "zada_compress_data")
         return out.raw[:ol.value], c.value, zt.value
+
+    # ---- ZipCrypto (Zip.CRC_Crypto, zip-crc_crypto.adb:78-137; include/zada.h "Password-protected entries") ----
+    def crypt_init_keys(self, password):
+        """Init_Keys: the three keys of a password (bytes, or str taken as Latin-1)."""
+        pw = password.encode("latin-1") if isinstance(password, str) else bytes(password)
+        k = (ctypes.c_uint32 * 3)()
+        self.lib.zada_crypt_init_keys(pw, len(pw), k)
+        return tuple(k)
+
+    def crypt_header(self, keys, random11, crc_final):
+        """The encryption header (zip-compress.adb:153-161) of eleven bytes and the entry's final CRC-32: (12 encoded bytes, keys behind them)."""
+        if len(random11) != 11:
+            raise ZadaError("header: eleven bytes")
+        k = (ctypes.c_uint32 * 3)(*keys)
+        out = ctypes.create_string_buffer(12)
+        self.lib.zada_crypt_header(k, bytes(random11), crc_final & 0xFFFFFFFF, ctypes.addressof(out))
+        return out.raw, tuple(k)
+
+    def crypt_encode(self, keys, data):
+        """Encode of `data` from `keys`: (cipher text, keys behind it).  Piece after piece gives the bytes of one call over the whole."""
+        import numpy as np
+        k = (ctypes.c_uint32 * 3)(*keys)
+        buf = np.frombuffer(data, dtype=np.uint8).copy() if len(data) else np.zeros(0, np.uint8)
+        rc = self.lib.zada_crypt_encode(self.ctx, k, buf.ctypes.data if len(buf) else None, len(buf))
+        if rc != 0:
+            self._err(rc, "zada_crypt_encode")
+        return buf.tobytes(), tuple(k)
+
+    def crypt_encode_device(self, keys, d_ptr, n):
+        """Encode of n bytes at a device address, in place.  Returns the keys behind them."""
+        k = (ctypes.c_uint32 * 3)(*keys)
+        rc = self.lib.zada_crypt_encode_device(self.ctx, k, d_ptr, n)
+        if rc != 0:
+            self._err(rc, "zada_crypt_encode_device")
+        return tuple(k)
+
+    def crypt_encode_batch(self, keys, datas):
+        """Independent buffers, each from its own keys, in one call (zada_crypt_encode_batch).  Returns a list of (cipher text, keys behind it)."""
+        import numpy as np
+        cnt = len(datas)
+        if cnt == 0:
+            return []
+        lens = np.fromiter((len(d) for d in datas), dtype=np.uint64, count=cnt)
+        offs = np.concatenate(([0], np.cumsum(lens)[:-1])).astype(np.uint64)
+        arena = np.frombuffer(b"".join(bytes(d) for d in datas) or b"\0", dtype=np.uint8).copy()
+        ptrs = (arena.ctypes.data + offs).astype(np.uint64)
+        ks = np.ascontiguousarray(np.array(keys, dtype=np.uint32).reshape(cnt, 3))
+        rc = self.lib.zada_crypt_encode_batch(self.ctx, cnt, ks.ctypes.data, ptrs.ctypes.data, lens.ctypes.data)
+        if rc != 0:
+            self._err(rc, "zada_crypt_encode_batch")
+        mv = memoryview(arena)
+        return [(bytes(mv[int(offs[i]):int(offs[i]) + int(lens[i])]), tuple(int(x) for x in ks[i])) for i in range(cnt)]
 
     def lz77_tokens(self, data, method=Method.Deflate_3):
         import numpy as np
@@ -635,11 +719,16 @@ class ZipCreate:
     def _presel(self):
         return self.method in (Method.Preselection_1, Method.Preselection_2)
 
-    def add_stream(self, name, data, file_time=None, unicode_name=True):
+    def add_stream(self, name, data, file_time=None, unicode_name=True, password=None, _header=None):
+        """Add_Stream (zip-create.adb:194-297).  password (bytes, or str taken as Latin-1): the entry is encrypted (Compress_Data's password,
+        :253-265); _header is a test hook: the eleven random bytes of the encryption header."""
         # (Preselection: the content hint is Guess_Type_from_Name of the entry's name, zip-create.adb:261)
         hint = guess_type_from_name(name) if self._presel() else None
-        payload, crc, zt = self.enc.compress_data(data, self.method, content_hint=hint)
-        return self.add_compressed(name, payload, crc, len(data), zt, file_time, unicode_name)
+        if password is None:
+            payload, crc, zt = self.enc.compress_data(data, self.method, content_hint=hint)
+            return self.add_compressed(name, payload, crc, len(data), zt, file_time, unicode_name)
+        payload, crc, zt = self.enc.compress_data(data, self.method, content_hint=hint, password=password, header=_header)
+        return self.add_compressed(name, payload, crc, len(data), zt, file_time, unicode_name, password=password)
 
     def _batch(self, datas, method):
         if method == Method.Store:
@@ -650,13 +739,17 @@ class ZipCreate:
             return self.enc.lzma_batch(datas, method)
         return self.enc.deflate_batch(datas, method)
 
-    def add_streams(self, names, datas, file_time=None, unicode_name=True):
+    def add_streams(self, names, datas, file_time=None, unicode_name=True, password=None, _headers=None):
         """Add_Stream for many entries at once: the entries are compressed as one batch (zada_deflate_batch: one launch
         sequence for all the small ones), with Compress_Data's Store fallback (zip-compress.adb:224-237) and CRC Init / Final
         (:144, 218) per entry.  The archive is the one Add_Stream after Add_Stream writes.  Preselection: every entry's method is
-        preselect (method, Guess_Type_from_Name (name), size); the entries of one method go through its batch entry point together."""
+        preselect (method, Guess_Type_from_Name (name), size); the entries of one method go through its batch entry point together.
+        With a password the entries are compressed the same way; their encryption headers are made on the host (twelve serial bytes each) and all
+        payloads -- those that fell back to Store too -- are encoded by one crypt_encode_batch.  _headers (test hook): eleven bytes per entry."""
         import zlib
         names, datas = list(names), list(datas)
+        if password is not None:
+            _password(password)
         if self._presel():
             methods = [preselect(self.method, guess_type_from_name(nm), len(d)) for nm, d in zip(names, datas)]
         else:
@@ -666,17 +759,31 @@ class ZipCreate:
             idx = [i for i, mi in enumerate(methods) if mi == m]
             for i, r in zip(idx, self._batch([datas[i] for i in idx], m)):
                 res[i] = r
+        plain = []                                   # (name, payload, final CRC-32, size, zip_type) as an unencrypted archive takes them
         for name, data, m, (rc, payload, crc) in zip(names, datas, methods, res):
             if rc == 0:
-                self.add_compressed(name, payload, crc ^ 0xFFFFFFFF, len(data), _zip_type(m), file_time, unicode_name)
+                plain.append((name, payload, crc ^ 0xFFFFFFFF, len(data), _zip_type(m)))
             else:
-                self.add_compressed(name, bytes(data), zlib.crc32(data) if m == Method.Store else crc ^ 0xFFFFFFFF, len(data), 0, file_time, unicode_name)
+                plain.append((name, bytes(data), (zlib.crc32(data) if m == Method.Store else crc ^ 0xFFFFFFFF) & 0xFFFFFFFF, len(data), 0))
+        if password is not None:
+            k0 = self.enc.crypt_init_keys(password)
+            hdrs, keys = [], []
+            for i, (_, _, crc, _, _) in enumerate(plain):
+                h, k = self.enc.crypt_header(k0, os.urandom(11) if _headers is None else _headers[i], crc)
+                hdrs.append(h); keys.append(k)
+            coded = self.enc.crypt_encode_batch(keys, [p[1] for p in plain])
+            for (name, _, crc, usize, zt), h, (ct, _) in zip(plain, hdrs, coded):
+                self.add_compressed(name, h + ct, crc, usize, zt, file_time, unicode_name, password=password)
+            return
+        for name, payload, crc, usize, zt in plain:
+            self.add_compressed(name, payload, crc, usize, zt, file_time, unicode_name)
 
-    def add_compressed(self, name, payload, crc, usize, zt, file_time=None, unicode_name=True):
+    def add_compressed(self, name, payload, crc, usize, zt, file_time=None, unicode_name=True, password=None):
         """Entry whose payload was compressed elsewhere (another rank / GPU): the bytes written
-        are those Add_Stream would have written for the same payload."""
+        are those Add_Stream would have written for the same payload.  With a password the payload is what Compress_Data left for it -- the
+        encryption header and the encoded stream -- and the entry carries Encryption_Flag_Bit (zip-create.adb:221-223)."""
         nm = name.replace("\\", "/").encode("utf-8")
-        e = dict(name=nm, flag=(0x0800 if unicode_name else 0) | (0x0002 if zt == 14 else 0),   # LZMA_EOS_Flag_Bit, zip-create.adb:266-278
+        e = dict(name=nm, flag=(0x0800 if unicode_name else 0) | (0x0002 if zt == 14 else 0) | (0x0001 if password else 0),   # LZMA_EOS_Flag_Bit, zip-create.adb:266-278
                  zip_type=zt, time=self.DEFAULT_TIME if file_time is None else file_time,
                  crc=crc, csize=len(payload), usize=usize, offset=len(self.buf) + self._bias)
         self._check_size(usize)

@@ -1028,6 +1028,7 @@ static void ctx_release(zada_ctx *z) {
   if (z->c.stream) hipStreamSynchronize(z->c.stream);
   if (z->c.stream2) hipStreamSynchronize(z->c.stream2);
   bz2_destroy(&z->c);
+  crypt_destroy(&z->c);
   lzma_free(&z->c);
   free_workspace(&z->c);
   for (hipEvent_t e : z->c.ev_pool) hipEventDestroy(e);
@@ -2181,6 +2182,121 @@ int zada_compress_data_hint(zada_ctx *z, int method, int content_hint, const uin
   if (m < 0) { z->c.err = "zada_compress_data_hint: method or content hint out of range"; return ZADA_E_INVALID; }
   if (method_used) *method_used = m;
   return zada_compress_data(z, m, in, n, out, cap, out_len, crc_out, zip_type);
+}
+
+// ---- ZipCrypto (zada_crypt.hip): CRC_Crypto on the device behind Compress_Data's password ----
+void zada_crypt_init_keys(const uint8_t *password, uint64_t len, uint32_t keys[3]) {      // Init_Keys, zip-crc_crypto.adb:110-116
+  keys[0] = 0x12345678u; keys[1] = 0x23456789u; keys[2] = 0x34567890u;
+  for (uint64_t i = 0; i < len; i++) crypt_update_keys(keys, password[i]);
+}
+
+void zada_crypt_header(uint32_t keys[3], const uint8_t random11[11], uint32_t crc_final, uint8_t out12[12]) {   // zip-compress.adb:153-161
+  uint8_t h[12];
+  memcpy(h, random11, 11);
+  h[11] = (uint8_t)(crc_final >> 24);
+  for (int i = 0; i < 12; i++) {                                  // Encode :118-128
+    out12[i] = h[i] ^ crypt_code(keys);
+    crypt_update_keys(keys, h[i]);
+  }
+}
+
+int zada_crypt_encode_device(zada_ctx *z, uint32_t keys[3], void *d_buf, uint64_t n) {
+  int rc = prepare(z);
+  if (rc) return rc;
+  Ctx *c = &z->c;
+  if (!keys || (n && !d_buf)) { c->err = "zada_crypt_encode_device: null argument"; return ZADA_E_INVALID; }
+  c->tbegin(); c->tmark("crypt:begin");
+  rc = finish_call(c, crypt_encode_device(c, keys, (uint8_t *)d_buf, n));
+  c->tmark("crypt:encode"); c->tend();
+  return rc;
+}
+
+int zada_crypt_encode(zada_ctx *z, uint32_t keys[3], uint8_t *buf, uint64_t n) {
+  int rc = prepare(z);
+  if (rc) return rc;
+  Ctx *c = &z->c;
+  if (!keys || (n && !buf)) { c->err = "zada_crypt_encode: null argument"; return ZADA_E_INVALID; }
+  if (n == 0) return ZADA_OK;
+  uint8_t *d = nullptr;
+  if ((rc = crypt_io(c, n, &d))) return rc;
+  copy_in(c, d, buf, n);
+  if ((rc = finish_call(c, crypt_encode_device(c, keys, d, n)))) return rc;
+  return copy_out(c, buf, d, n) ? ZADA_E_HIP : ZADA_OK;
+}
+
+int zada_crypt_encode_batch(zada_ctx *z, int count, uint32_t (*keys)[3], uint8_t *const *buf, const uint64_t *n) {
+  if (!z || count < 0) return ZADA_E_INVALID;
+  int rc = prepare(z);
+  if (rc) return rc;
+  Ctx *c = &z->c;
+  if (count && (!keys || !buf || !n)) { c->err = "zada_crypt_encode_batch: null argument"; return ZADA_E_INVALID; }
+  for (int i = 0; i < count; i++) if (n[i] && !buf[i]) { c->err = "zada_crypt_encode_batch: null buffer"; return ZADA_E_INVALID; }
+  // entries of up to CRYPT_WAVE_MAX bytes: one wave each, up to 256 MiB of them in one launch; longer ones through the tiled path, one after the other
+  std::vector<int> group;
+  uint64_t gbytes = 0;
+  auto flush_group = [&]() {
+    int r = group.empty() ? 0 : finish_call(c, crypt_encode_small(c, group.data(), (uint32_t)group.size(), keys, buf, n));
+    group.clear(); gbytes = 0;
+    return r;
+  };
+  for (int i = 0; i < count; i++) {
+    if (n[i] > CRYPT_WAVE_MAX) { if ((rc = zada_crypt_encode(z, keys[i], buf[i], n[i]))) return rc; continue; }
+    if (gbytes + n[i] + 16 > (256ull << 20) && (rc = flush_group())) return rc;
+    group.push_back(i); gbytes += n[i] + 16;
+  }
+  return flush_group();
+}
+
+// Compress_data_single_method with is_encrypted (zip-compress.adb:142-241), in the reference's order: the keys from the password (:146), the CRC-32 of the
+// input in a scan of its own (:152), the header (:153-161) and the keys as they stand behind it (:166), the encoder, Encode of its stream -- in device
+// memory, before it travels to the host --, or, where compression_ok = False, of the input itself from the kept keys (:224-237); 12 bytes more (:238-240).
+int zada_compress_data_pw(zada_ctx *z, int method, int content_hint, const uint8_t *password, uint64_t pw_len, const uint8_t random11[11],
+                          const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len, uint32_t *crc_out, uint16_t *zip_type, int *method_used) {
+  int rc = prepare(z);
+  if (rc) return rc;
+  Ctx *c = &z->c;
+  if (!out_len || !crc_out || !zip_type || !out || !random11 || (n && !in)) { c->err = "zada_compress_data_pw: null argument"; return ZADA_E_INVALID; }
+  if (!password || pw_len == 0) { c->err = "zada_compress_data_pw: empty password (the unencrypted call is zada_compress_data)"; return ZADA_E_INVALID; }
+  const int m = zada_preselect(method, content_hint, 1, n);
+  if (m < 0) { c->err = "zada_compress_data_pw: method or content hint out of range"; return ZADA_E_INVALID; }
+  const bool bz = m >= ZADA_BZIP2_1 && m <= ZADA_BZIP2_3, lz = is_lzma_method(m), df = method_level(m) >= 0;
+  if (m != 0 && !bz && !lz && !df) { c->err = "unsupported method"; return ZADA_E_INVALID; }
+  if (cap < 12) { c->err = "output buffer too small"; return ZADA_E_INVALID; }
+  if (method_used) *method_used = m;
+  uint32_t keys[3];
+  zada_crypt_init_keys(password, pw_len, keys);
+  // the input, then the stream, in one device buffer
+  const uint64_t in_room = (n + 255) & ~255ull, dcap = n + 64;
+  uint8_t *d_in = nullptr;
+  if ((rc = crypt_io(c, in_room + dcap + 256, &d_in))) return rc;
+  uint8_t *d_out = d_in + in_room;
+  copy_in(c, d_in, in, n);
+  uint32_t crc = 0xFFFFFFFFu;                                     // Init :144, Store_data (do_write => False) :152
+  const uint64_t piece = 2ull << 30;
+  if (n && (rc = ensure_crc_workspace(c, n < piece ? n : piece))) return rc;
+  for (uint64_t o = 0; o < n; o += piece) {
+    const uint64_t k = n - o < piece ? n - o : piece;
+    if ((rc = crc_launch(c, d_in + o, k)) || (rc = crc_finish(c, k, &crc))) return finish_call(c, rc);
+  }
+  crc = ~crc;                                                     // Final :157
+  zada_crypt_header(keys, random11, crc, out);                    // :153-161; `keys` is mem_encrypt_pack now (:166)
+  uint64_t ol = 0;
+  uint32_t crc2 = 0xFFFFFFFFu;
+  rc = m == 0 ? ZADA_INEFFICIENT                                  // Store: Store_data (do_write => True) :178-179, the bytes the fallback writes
+     : bz ? zada_bzip2_device(z, m, d_in, n, d_out, dcap, &ol, &crc2)
+     : lz ? zada_lzma_device(z, m, d_in, n, d_out, dcap, &ol, &crc2)
+          : zada_deflate_device(z, m, d_in, n, d_out, dcap, &ol, &crc2);
+  if (rc < 0 || rc == ZADA_ABORTED) return rc;
+  if (m != 0 && ~crc2 != crc) { c->err = "zada_compress_data_pw: the encoder's CRC-32 differs from the pre-scan's"; return ZADA_E_HIP; }
+  *zip_type = m == 0 ? 0 : bz ? 12 : lz ? 14 : 8;
+  uint8_t *d_payload = d_out;
+  if (rc == ZADA_INEFFICIENT) { d_payload = d_in; ol = n; *zip_type = 0; }     // :224-237
+  if (cap - 12 < ol) { c->err = "output buffer too small"; return ZADA_E_INVALID; }
+  if ((rc = finish_call(c, crypt_encode_device(c, keys, d_payload, ol)))) return rc;
+  if (copy_out(c, out + 12, d_payload, ol)) return ZADA_E_HIP;
+  *out_len = ol + 12;                                             // :238-240
+  *crc_out = crc;
+  return ZADA_OK;
 }
 
 int zada_lz77_tokens(zada_ctx *z, int method, const uint8_t *in, uint64_t n, uint32_t *tokens, uint64_t cap, uint64_t *ntok) {

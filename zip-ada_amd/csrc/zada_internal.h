@@ -259,6 +259,7 @@ struct Ctx {
   int atoms_grown = 0, fix_grown = 0;                // how often a call had to enlarge the atom arrays / the splice's token slots (last_timing: #atoms_grown, #fix_grown)
   bool lz_attrs_set = false;
   void *bz = nullptr;                                // BZip2 state (zada_bz2.hip), made on first use
+  void *zc = nullptr;                                // ZipCrypto state (zada_crypt.hip), made on first use
   void *lz_tab = nullptr; size_t cap_lz_tab = 0;     // LZMA (zada_lzma.hip): job table + results
   void *lz_save = nullptr; size_t cap_lz_save = 0;   // ... the coder's state between the launches of one stream
   void *lz_lit = nullptr; size_t cap_lz_lit = 0;     // ... the HBM literal tables of the methods with lc + lp >= 4, one per entry of a launch group
@@ -322,6 +323,14 @@ struct Ctx {
 extern thread_local std::string *tls_err;          // error text of a worker thread (see hip_check)
 int hip_check(Ctx *c, hipError_t e, const char *what);
 void bz2_destroy(Ctx *c);
+// ZipCrypto (zada_crypt.hip): CRC_Crypto.Encode over device memory, keys in and out
+void crypt_destroy(Ctx *c);
+void crypt_update_keys(uint32_t keys[3], uint8_t by);
+uint8_t crypt_code(const uint32_t keys[3]);
+constexpr uint64_t CRYPT_WAVE_MAX = 256u << 10;     // a batch's entries of up to this many bytes: one wave each, in one launch
+int crypt_io(Ctx *c, uint64_t bytes, uint8_t **p);
+int crypt_encode_device(Ctx *c, uint32_t keys[3], uint8_t *d_buf, uint64_t n);
+int crypt_encode_small(Ctx *c, const int *idx, uint32_t E, uint32_t (*keys)[3], uint8_t *const *buf, const uint64_t *n);
 int bz2_encode_device(Ctx *c, int option, const uint8_t *d_in, uint64_t n, int64_t size_hint, uint8_t *d_out, uint64_t cap, uint64_t *out_len,
                       int (*fb)(int, void *), void *user);
 uint64_t bz2_last_blocks(Ctx *c, uint64_t *dst, uint64_t cap_items);
