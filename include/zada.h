@@ -91,10 +91,11 @@ enum {
                              * length, span after span), zada_lzma* entries below 2 GiB - 64 KiB and batches below 4 GiB; LZMA_3 also what the match producer's 156 bytes of
                              * device memory per input byte allow */
   ZADA_E_NO_DEVICE = -5,    /* no gfx950 device / HIP extension unusable */
-  ZADA_E_REFERENCE = -6     /* LZMA_3 only: on this entry the reference's BT4 matcher reports a match that is none (lz77.adb:1262-1290 read behind pending
+  ZADA_E_REFERENCE = -6,    /* LZMA_3 only: on this entry the reference's BT4 matcher reports a match that is none (lz77.adb:1262-1290 read behind pending
                              * bytes that no window fill took up, :1000-1017, 1397-1406: lzPos lags behind readPos) and the reference's own stream does not
                              * decode to the input.  Cannot happen with the dictionary Zip.Compress.LZMA_E asks for unless the entry is beyond 256 MiB and its
                              * last window fill brings 163 .. 4 368 bytes; the shim Stores such an entry or takes another method.  Nothing was written. */
+  ZADA_E_DATA = -7          /* zada_inflate* only: the compressed data is not a valid stream (Zip.Archive_corrupted); zada_last_error names the rule and the bit */
 };
 
 typedef struct zada_ctx zada_ctx;
@@ -201,6 +202,43 @@ int zada_crypt_encode_batch(zada_ctx *ctx, int count, uint32_t (*keys)[3], uint8
 int zada_compress_data_pw(zada_ctx *ctx, int method, int content_hint, const uint8_t *password, uint64_t pw_len, const uint8_t random11[11],
                           const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len, uint32_t *crc_out,
                           uint16_t *zip_type, int *method_used);
+
+/* ---- The reader: UnZip.Decompress.Inflate (unzip-decompress.adb:1463-1889) -----------------------------------------
+ * Raw Deflate (Zip format 8) and Deflate64 (format 9: a 64 KiB window, length code 285 = 3 + 16 extra bits, distance codes 30 / 31 with 14
+ * extra bits, unzip-decompress.adb:61, 148, 1859, 2035) streams back into bytes; any other format is ZADA_E_INVALID.  One stream is a chain
+ * -- a Huffman code is found only by decoding the one before it, a match reads what earlier tokens wrote --, so ENTRIES are what runs in
+ * parallel: one wave per entry (csrc/zada_inflate.hip), use zada_inflate_batch for many of them.  ONE STREAM ALONE RUNS AT ONE
+ * WAVE'S PACE (as one LZMA stream does): 8.3 MB/s for one 64 MiB Deflate_3 stream of the benchmark corpus, where one zlib thread on the host
+ * does 434 MB/s, against 19.8 GB/s for 10 000 entries of 16 KiB in one launch (profiles/inflate/NOTES.md); cutting one stream over many waves is not done.
+ *   crc_inout : the running CRC-32 register (Init before, Final after: zip-crc_crypto.adb:49-76), updated over the bytes written, on the
+ *               device.  May be NULL.
+ *   cap       : the uncompressed size the directory promises; a stream that writes more is ZADA_E_DATA.  cap = 0 with the stream of an
+ *               empty entry is fine.
+ *   out_len   : bytes written.  in_used: bytes up to and including the one that holds the last bit of the final block; trailing bytes are
+ *               not an error.  Both may be NULL.
+ * A stream is valid when zlib's inflate accepts it (raw, no dictionary).  ZADA_E_DATA (Zip.Archive_corrupted) otherwise: block type 3; a stored
+ * block whose LEN is not the complement of NLEN; HLIT > 286 or HDIST > 30 (Deflate64: 32); an over-subscribed code; an incomplete code other
+ * than one code of length 1 (or no distance code at all); repeat code 16 with no previous length; a repeat past HLIT + HDIST; no code for
+ * end-of-block; literal/length symbol 286 / 287 or, in Deflate, distance symbol 30 / 31; an unassigned code; a distance beyond the bytes
+ * written so far; input exhausted before the final block's end-of-block (n_in = 0 included); output beyond cap.  zada_last_error names the rule
+ * and the bit position; nothing is delivered for such an entry (*out_len = *in_used = 0, the CRC register stays).  Nothing is read beyond n_in
+ * and nothing written beyond cap, whatever the stream holds.  Argument checks come before anything touches the device; a stream or a cap of
+ * 1 TiB or more is ZADA_E_TOO_LARGE. */
+int zada_inflate(zada_ctx *ctx, int format, const uint8_t *in, uint64_t n_in, uint8_t *out, uint64_t cap,
+                 uint64_t *out_len, uint64_t *in_used, uint32_t *crc_inout);
+/* the same with the stream and the output in device memory, at any alignment */
+int zada_inflate_device(zada_ctx *ctx, int format, const void *d_in, uint64_t n_in, void *d_out, uint64_t cap,
+                        uint64_t *out_len, uint64_t *in_used, uint32_t *crc_inout);
+/* `count` independent streams (one per Zip entry; what UnZip.Extract does entry after entry, unzip.adb), format [i] per entry.  The entries are
+ * staged in groups of up to "batch_mib" MiB of streams and outputs, every group one launch: the waves take the entries longest first.
+ * rc [i] is ZADA_OK or ZADA_E_DATA per entry, crc [i] in/out; the call returns the worst rc.  `out` may be NULL: the decoded bytes then
+ * stay on the device and only sizes, CRCs and verdicts come back (UnZip's test_only). */
+int zada_inflate_batch(zada_ctx *ctx, int count, const int *format, const uint8_t *const *in, const uint64_t *n_in,
+                       uint8_t *const *out, const uint64_t *cap, uint64_t *out_len, uint64_t *in_used, uint32_t *crc, int *rc);
+/* CRC_Crypto.Decode (zip-crc_crypto.adb:130-137) of `count` buffers in place, each from its own keys (in and out): what opens the entries
+ * zada_compress_data_pw writes (the first 12 bytes decode to the encryption header, whose last byte is the entry's check byte).  Unlike
+ * Encode it is serial -- key 0 is a CRC over the PLAIN text, known only byte by byte -- so there is no scan: one lane per buffer. */
+int zada_crypt_decode_batch(zada_ctx *ctx, int count, uint32_t (*keys)[3], uint8_t *const *buf, const uint64_t *n);
 
 /* ---- One stream over several contexts (GPUs) -------------------------------------------------------------------
  * The reference compresses an entry as ONE sequential stream (a 32 KiB window, a lazy-match state machine, a flush of the

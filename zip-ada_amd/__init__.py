@@ -78,6 +78,7 @@ def preselect(method, content_hint=ContentType.neutral, input_size=None):
 
 
 E_REFERENCE = -6     # zada.h ZADA_E_REFERENCE: LZMA_3, the reference's own matcher reports a match that is none on this entry
+E_DATA = -7          # zada.h ZADA_E_DATA: zada_inflate*, the compressed data is not a valid stream
 
 
 class ZadaError(RuntimeError):
@@ -87,6 +88,26 @@ class ZadaError(RuntimeError):
 class ReferenceDefect(ZadaError):
     """ZADA_E_REFERENCE: on this LZMA_3 entry the reference's BT4 matcher reports a match that is none (include/zada.h); the reference's own
     stream would not decode to the input, nothing was written."""
+
+
+class DataError(ZadaError):
+    """ZADA_E_DATA: the compressed data is not a valid Deflate / Deflate64 stream, or writes more than the size promised (Zip.Archive_corrupted)."""
+
+
+class WrongPassword(ZadaError):
+    """UnZip.Wrong_password (unzip.ads:276-283): the decoded encryption header does not end in the entry's check byte."""
+
+
+class SizeError(ZadaError):
+    """UnZip.Uncompressed_Size_Error: the entry decodes to another size than the directory says."""
+
+
+class CRCError(ZadaError):
+    """UnZip.CRC_Error: the CRC-32 of the decoded bytes is not the directory's."""
+
+
+class UnsupportedMethod(ZadaError):
+    """UnZip.Unsupported_method: the reader decodes Store (0), Deflate (8) and Deflate64 (9); BZip2, LZMA and the older formats are out of its scope."""
 
 
 class CompressionInefficient(Exception):
@@ -174,6 +195,11 @@ def load_library():
         L.zada_crypt_encode_device.argtypes = [vp, u32p, vp, u64]
         L.zada_crypt_encode_batch.argtypes = [vp, i32, vp, vp, vp]
         L.zada_compress_data_pw.argtypes = [vp, i32, i32, ctypes.c_char_p, u64, ctypes.c_char_p, vp, u64, vp, u64, u64p, u32p, ctypes.POINTER(ctypes.c_uint16), vp]
+    if hasattr(L, "zada_inflate"):                   # (likewise: the reader)
+        L.zada_inflate.argtypes = [vp, i32, vp, u64, vp, u64, u64p, u64p, u32p]
+        L.zada_inflate_device.argtypes = [vp, i32, vp, u64, vp, u64, u64p, u64p, u32p]
+        L.zada_inflate_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.zada_crypt_decode_batch.argtypes = [vp, i32, vp, vp, vp]
     L.zada_bz2_last_blocks.restype = ctypes.c_uint64
     L.zada_bz2_last_blocks.argtypes = [vp, vp, u64]
     L.zada_crc32_combine.restype = ctypes.c_uint32
@@ -242,6 +268,8 @@ class Encoder:
             raise ZadaError("unknown knob %r" % name)
 
     def _err(self, rc, what):
+        if rc == E_DATA:
+            raise DataError("%s: %s" % (what, self.lib.zada_last_error(self.ctx).decode()))
         if rc == E_REFERENCE:
             raise ReferenceDefect("%s: rc=%d (%s)" % (what, rc, self.lib.zada_last_error(self.ctx).decode()))
         raise ZadaError("%s failed: rc=%d (%s)" % (what, rc, self.lib.zada_last_error(self.ctx).decode()))
@@ -590,6 +618,85 @@ class Encoder:
         mv = memoryview(arena)
         return [(bytes(mv[int(offs[i]):int(offs[i]) + int(lens[i])]), tuple(int(x) for x in ks[i])) for i in range(cnt)]
 
+    def crypt_decode_batch(self, keys, datas):
+        """Decode (zip-crc_crypto.adb:130-137) of independent buffers, each from its own keys, in one launch (zada_crypt_decode_batch: one lane per
+        buffer -- Decode is serial).  Returns a list of (plain text, keys behind it)."""
+        import numpy as np
+        cnt = len(datas)
+        if cnt == 0:
+            return []
+        lens = np.fromiter((len(d) for d in datas), dtype=np.uint64, count=cnt)
+        offs = np.concatenate(([0], np.cumsum(lens)[:-1])).astype(np.uint64)
+        arena = np.frombuffer(b"".join(bytes(d) for d in datas) or b"\0", dtype=np.uint8).copy()
+        ptrs = (arena.ctypes.data + offs).astype(np.uint64)
+        ks = np.ascontiguousarray(np.array(keys, dtype=np.uint32).reshape(cnt, 3))
+        rc = self.lib.zada_crypt_decode_batch(self.ctx, cnt, ks.ctypes.data, ptrs.ctypes.data, lens.ctypes.data)
+        if rc != 0:
+            self._err(rc, "zada_crypt_decode_batch")
+        mv = memoryview(arena)
+        return [(bytes(mv[int(offs[i]):int(offs[i]) + int(lens[i])]), tuple(int(x) for x in ks[i])) for i in range(cnt)]
+
+    # ---- the reader: UnZip.Decompress.Inflate (unzip-decompress.adb:1463-1889; include/zada.h "Inflate") ----
+    def inflate(self, payload, size=None, format=8, crc=0xFFFFFFFF):
+        """One raw Deflate (format 8) or Deflate64 (9) stream.  size: the uncompressed size the directory promises (a stream that writes more is a
+        DataError); None = unknown: the output buffer starts at four times the payload and doubles while the only complaint is "output beyond cap".
+        Returns (bytes, input bytes used, running CRC register).  Raises DataError."""
+        n = len(payload)
+        cap = max(4 * n, 256) if size is None else int(size)
+        while True:
+            out = ctypes.create_string_buffer(max(cap, 1))
+            ol, iu, c = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(crc)
+            rc = self.lib.zada_inflate(self.ctx, format, _addr(payload) if n else None, n, ctypes.addressof(out), cap, ctypes.byref(ol), ctypes.byref(iu), ctypes.byref(c))
+            if rc == 0:
+                return out.raw[:ol.value], iu.value, c.value
+            if rc == E_DATA and size is None and b"output beyond cap" in self.lib.zada_last_error(self.ctx):
+                cap *= 2
+                continue
+            self._err(rc, "zada_inflate")
+
+    def inflate_batch(self, payloads, sizes, formats=8, crc=0xFFFFFFFF, deliver=True):
+        """Independent streams (one per Zip entry), one wave each, in one launch per group of "batch_mib".  sizes [i] = cap of entry i; formats: one
+        Zip code for all, or one per entry.  Returns a list of (rc, bytes or None, bytes written, input bytes used, running CRC register); rc is 0
+        or E_DATA.  deliver = False: the bytes stay on the device (sizes and CRCs only -- UnZip's test_only)."""
+        import numpy as np
+        cnt = len(payloads)
+        if cnt == 0:
+            return []
+        fm = np.full(cnt, formats, dtype=np.int32) if np.isscalar(formats) else np.ascontiguousarray(np.array(formats, dtype=np.int32))
+        lens = np.fromiter((len(d) for d in payloads), dtype=np.uint64, count=cnt)
+        caps = np.ascontiguousarray(np.array(sizes, dtype=np.uint64))
+        if len(caps) != cnt or len(fm) != cnt:
+            raise ZadaError("inflate_batch: one size and one format per payload")
+        keep = [d if len(d) else b"\0" for d in payloads]
+        ins = np.fromiter((_addr(d) for d in keep), dtype=np.uint64, count=cnt)
+        offs = np.concatenate(([0], np.cumsum(caps)[:-1])).astype(np.uint64)
+        total = sum(int(x) for x in caps)                  # (Python integers: the sizes may come from a directory that lies)
+        try:
+            if total >= 1 << 40:
+                raise MemoryError
+            arena = np.empty(total + 1 if deliver else 1, dtype=np.uint8)
+        except (MemoryError, ValueError):
+            raise ZadaError("inflate_batch: %d bytes of output are promised -- more than this machine holds" % total)
+        outp = (arena.ctypes.data + offs).astype(np.uint64)
+        ols, ius = np.zeros(cnt, dtype=np.uint64), np.zeros(cnt, dtype=np.uint64)
+        crcs = np.full(cnt, crc, dtype=np.uint32)
+        rcs = np.zeros(cnt, dtype=np.int32)
+        worst = self.lib.zada_inflate_batch(self.ctx, cnt, fm.ctypes.data, ins.ctypes.data, lens.ctypes.data, outp.ctypes.data if deliver else None, caps.ctypes.data,
+                                            ols.ctypes.data, ius.ctypes.data, crcs.ctypes.data, rcs.ctypes.data)
+        if worst < 0 and worst != E_DATA:
+            self._err(worst, "zada_inflate_batch")
+        mv = memoryview(arena)
+        return [(int(rcs[i]), bytes(mv[int(offs[i]):int(offs[i]) + int(ols[i])]) if deliver and rcs[i] == 0 else None, int(ols[i]), int(ius[i]), int(crcs[i]))
+                for i in range(cnt)]
+
+    def inflate_device(self, d_in_ptr, n_in, d_out_ptr, cap, format=8, crc=0xFFFFFFFF):
+        """Device-resident variant (HBM addresses of any alignment).  Returns (bytes written, input bytes used, running CRC register); raises DataError."""
+        ol, iu, c = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(crc)
+        rc = self.lib.zada_inflate_device(self.ctx, format, d_in_ptr, n_in, d_out_ptr, cap, ctypes.byref(ol), ctypes.byref(iu), ctypes.byref(c))
+        if rc != 0:
+            self._err(rc, "zada_inflate_device")
+        return ol.value, iu.value, c.value
+
     def lz77_tokens(self, data, method=Method.Deflate_3):
         import numpy as np
         n = len(data)
@@ -826,3 +933,172 @@ class ZipCreate:
         else:
             self.buf += struct.pack("<4sHHHHIIH", b"PK\x05\x06", 0, 0, n, n, cd_size, cd_off, 0)
         return bytes(self.buf)
+
+
+class ZipEntry:
+    """One entry of an archive's central directory (Zip.Zip_Info's Dir_node)."""
+    __slots__ = ("name", "raw_name", "method", "flags", "crc", "csize", "usize", "header_offset", "data_offset", "dos_time", "encrypted")
+
+    def __repr__(self):
+        return "ZipEntry(%r, method=%d, csize=%d, usize=%d)" % (self.name, self.method, self.csize, self.usize)
+
+
+class ZipInfo:
+    """Zip.Load (zip_lib/zip.adb, zip-headers.adb): the central directory of an archive held in memory.  Pure Python, needs no GPU.
+    .entries: ZipEntry (name, method code, flags, CRC, sizes, header and data offset), in directory order; .comment: the archive comment.
+    Sizes and CRC are the central directory's, so entries written with a data descriptor (flag bit 3) need no second look.  An archive
+    with bytes in front of it (offsets that do not start at the buffer) is read with the shift the end record implies."""
+
+    def __init__(self, data, entries, comment):
+        self.data, self.entries, self.comment = data, entries, comment
+
+    def __getitem__(self, name):
+        for e in self.entries:
+            if e.name == name:
+                return e
+        raise KeyError(name)
+
+    @classmethod
+    def load(cls, archive_bytes):
+        data = bytes(archive_bytes)
+        n = len(data)
+        try:
+            # end-of-central-directory record: the last one whose comment ends where the archive ends (zip-headers.adb:412-492)
+            pos = data.rfind(b"PK\x05\x06", max(0, n - 22 - 65535))
+            while pos >= 0:
+                if pos + 22 <= n and pos + 22 + struct.unpack_from("<H", data, pos + 20)[0] == n:
+                    break
+                pos = data.rfind(b"PK\x05\x06", max(0, n - 22 - 65535), pos)
+            if pos < 0:
+                raise ZadaError("ZipInfo.load: no end-of-central-directory record (not a Zip archive)")
+            _, disk, cd_disk, n_here, total, cd_size, cd_off, clen = struct.unpack_from("<4sHHHHIIH", data, pos)
+            comment = data[pos + 22:pos + 22 + clen]
+            tail = pos                                     # where the central directory's records end
+            if pos >= 20 and data[pos - 20:pos - 16] == b"PK\x06\x07":       # Zip64 locator, then the Zip64 end record (zip-headers.adb:534-579)
+                _, _, e64_off, _ = struct.unpack_from("<4sIQI", data, pos - 20)
+                p64 = pos - 20 - 56
+                if p64 < 0 or data[p64:p64 + 4] != b"PK\x06\x06":
+                    p64 = data.rfind(b"PK\x06\x06", 0, pos - 20)
+                if p64 < 0:
+                    raise ZadaError("ZipInfo.load: Zip64 locator without a Zip64 end record")
+                _, _, _, _, _, _, _, total, cd_size, cd_off = struct.unpack_from("<4sQHHIIQQQQ", data, p64)
+                tail = p64
+            cd_pos = tail - cd_size
+            if cd_pos < 0 or cd_size > n:
+                raise ZadaError("ZipInfo.load: the central directory lies beyond the file")
+            shift = cd_pos - cd_off                        # bytes in front of the archive (negative: the archive was cut out of a larger file)
+            entries, p = [], cd_pos
+            for _ in range(total):
+                if p + 46 > tail or data[p:p + 4] != b"PK\x01\x02":
+                    raise ZadaError("ZipInfo.load: truncated or damaged central header at %d" % p)
+                (_, _, _, flags, method, dos_time, crc, csize, usize, nlen, xlen, clen2, _, _, _, off) = struct.unpack_from("<4sHHHHIIIIHHHHHII", data, p)
+                if p + 46 + nlen + xlen + clen2 > tail:
+                    raise ZadaError("ZipInfo.load: truncated central header at %d" % p)
+                raw = data[p + 46:p + 46 + nlen]
+                extra = data[p + 46 + nlen:p + 46 + nlen + xlen]
+                q = 0
+                while q + 4 <= len(extra):                 # the Zip64 extended information: only the fields that are 0xFFFFFFFF above, in this order
+                    tag, sz = struct.unpack_from("<HH", extra, q)
+                    if tag == 1:
+                        f = q + 4
+                        vals = []
+                        while f + 8 <= q + 4 + sz and f + 8 <= len(extra):
+                            vals.append(struct.unpack_from("<Q", extra, f)[0]); f += 8
+                        if usize == 0xFFFFFFFF and vals:
+                            usize = vals.pop(0)
+                        if csize == 0xFFFFFFFF and vals:
+                            csize = vals.pop(0)
+                        if off == 0xFFFFFFFF and vals:
+                            off = vals.pop(0)
+                    q += 4 + sz
+                e = ZipEntry()
+                e.raw_name, e.name = raw, raw.decode("utf-8" if flags & 0x800 else "cp437", "replace")
+                e.method, e.flags, e.crc, e.csize, e.usize, e.dos_time = method, flags, crc, csize, usize, dos_time
+                e.encrypted = bool(flags & 1)
+                e.header_offset = off + shift
+                h = e.header_offset
+                if h < 0 or h + 30 > n or data[h:h + 4] != b"PK\x03\x04":
+                    raise ZadaError("ZipInfo.load: entry %r: no local header at %d" % (e.name, h))
+                lnl, lxl = struct.unpack_from("<HH", data, h + 26)
+                e.data_offset = h + 30 + lnl + lxl
+                if e.data_offset + csize > n:
+                    raise ZadaError("ZipInfo.load: entry %r: its data lie beyond the file" % e.name)
+                entries.append(e)
+                p += 46 + nlen + xlen + clen2
+            return cls(data, entries, comment)
+        except (struct.error, IndexError) as ex:
+            raise ZadaError("ZipInfo.load: damaged archive (%s)" % ex)
+
+
+class UnZip:
+    """UnZip.Extract (unzip.ads:55-290) on an archive in memory: Store (0), Deflate (8) and Deflate64 (9) entries; all Deflate entries of a call go
+    through ONE inflate_batch (one wave per entry), encrypted ones first through one crypt_decode_batch; size and CRC-32 -- computed on the device --
+    are compared with the directory.  BZip2, LZMA and the older formats are not decoded: UnsupportedMethod."""
+
+    _NAMES = {1: "Shrink", 2: "Reduce_1", 3: "Reduce_2", 4: "Reduce_3", 5: "Reduce_4", 6: "Implode", 12: "BZip2", 14: "LZMA", 98: "PPMd", 99: "AES"}
+
+    def __init__(self, encoder):
+        self.enc = encoder
+
+    def extract(self, info, what=None, password=None, test_only=False, errors="raise"):
+        """info: ZipInfo; what: None = every entry, or names.  Returns {name: bytes}.  An entry that fails is a WrongPassword, DataError, SizeError,
+        CRCError or UnsupportedMethod: with errors = "raise" (default) the first of them is raised once every other entry has been extracted, the
+        whole result in its .results; with errors = "collect" the exception stands in the result in place of the bytes.
+        test_only = True: {name: None or the exception} -- the per-entry verdicts, no bytes; the decoded bytes never leave the device."""
+        import zlib
+        ents = info.entries if what is None else [info[nm] for nm in ([what] if isinstance(what, str) else what)]
+        res, payload = {}, {}
+        enc_idx = []
+        for k, e in enumerate(ents):
+            if e.method not in (0, 8, 9):
+                res[k] = UnsupportedMethod("entry %r: method %d (%s) is not decoded by this reader: Store, Deflate and Deflate64 only -- BZip2 and LZMA decoding are out of scope"
+                                           % (e.name, e.method, self._NAMES.get(e.method, "unknown")))
+                continue
+            payload[k] = info.data[e.data_offset:e.data_offset + e.csize]
+            if e.encrypted:
+                if password is None:
+                    res[k] = WrongPassword("entry %r is encrypted and no password was given" % e.name)
+                elif e.csize < 12:
+                    res[k] = DataError("entry %r: shorter than its encryption header" % e.name)
+                else:
+                    enc_idx.append(k)
+        if enc_idx:
+            k0 = self.enc.crypt_init_keys(password)
+            for k, (plain, _) in zip(enc_idx, self.enc.crypt_decode_batch([k0] * len(enc_idx), [payload[k] for k in enc_idx])):
+                e = ents[k]
+                check = (e.dos_time >> 8) & 0xFF if e.flags & 8 else e.crc >> 24            # the header's last byte (zip-compress.adb:153-161; bit 3: the time stamp)
+                if plain[11] != check:
+                    res[k] = WrongPassword("entry %r: wrong password" % e.name)
+                else:
+                    payload[k] = plain[12:]
+        todo = [k for k in range(len(ents)) if k not in res and ents[k].method in (8, 9)]
+        if todo:
+            got = self.enc.inflate_batch([payload[k] for k in todo], [ents[k].usize for k in todo], [ents[k].method for k in todo], deliver=not test_only)
+            for k, (rc, out, ol, _, reg) in zip(todo, got):
+                e = ents[k]
+                if rc != 0:
+                    res[k] = DataError("entry %r: not a valid %s stream, or longer than the %d bytes promised" % (e.name, "Deflate64" if e.method == 9 else "Deflate", e.usize))
+                elif ol != e.usize:
+                    res[k] = SizeError("entry %r: %d bytes decoded, %d promised" % (e.name, ol, e.usize))
+                elif reg ^ 0xFFFFFFFF != e.crc:
+                    res[k] = CRCError("entry %r: CRC-32 %08x, the directory says %08x" % (e.name, reg ^ 0xFFFFFFFF, e.crc))
+                else:
+                    res[k] = None if test_only else out
+        for k, e in enumerate(ents):
+            if k in res:
+                continue
+            d = payload[k]                                 # Store: the slice itself
+            if len(d) != e.usize:
+                res[k] = SizeError("entry %r: %d bytes stored, %d promised" % (e.name, len(d), e.usize))
+            elif zlib.crc32(d) & 0xFFFFFFFF != e.crc:
+                res[k] = CRCError("entry %r: CRC-32 %08x, the directory says %08x" % (e.name, zlib.crc32(d) & 0xFFFFFFFF, e.crc))
+            else:
+                res[k] = None if test_only else d
+        out = {e.name: res[k] for k, e in enumerate(ents)}
+        if test_only or errors == "collect":
+            return out
+        for v in out.values():
+            if isinstance(v, Exception):
+                v.results = out
+                raise v
+        return out

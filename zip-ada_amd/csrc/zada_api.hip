@@ -1029,6 +1029,7 @@ static void ctx_release(zada_ctx *z) {
   if (z->c.stream2) hipStreamSynchronize(z->c.stream2);
   bz2_destroy(&z->c);
   crypt_destroy(&z->c);
+  inflate_destroy(&z->c);
   lzma_free(&z->c);
   free_workspace(&z->c);
   for (hipEvent_t e : z->c.ev_pool) hipEventDestroy(e);

@@ -260,6 +260,7 @@ struct Ctx {
   bool lz_attrs_set = false;
   void *bz = nullptr;                                // BZip2 state (zada_bz2.hip), made on first use
   void *zc = nullptr;                                // ZipCrypto state (zada_crypt.hip), made on first use
+  void *inf = nullptr;                               // Inflate state (zada_inflate.hip), made on first use
   void *lz_tab = nullptr; size_t cap_lz_tab = 0;     // LZMA (zada_lzma.hip): job table + results
   void *lz_save = nullptr; size_t cap_lz_save = 0;   // ... the coder's state between the launches of one stream
   void *lz_lit = nullptr; size_t cap_lz_lit = 0;     // ... the HBM literal tables of the methods with lc + lp >= 4, one per entry of a launch group
@@ -325,6 +326,7 @@ int hip_check(Ctx *c, hipError_t e, const char *what);
 void bz2_destroy(Ctx *c);
 // ZipCrypto (zada_crypt.hip): CRC_Crypto.Encode over device memory, keys in and out
 void crypt_destroy(Ctx *c);
+void inflate_destroy(Ctx *c);                       // Inflate (zada_inflate.hip)
 void crypt_update_keys(uint32_t keys[3], uint8_t by);
 uint8_t crypt_code(const uint32_t keys[3]);
 constexpr uint64_t CRYPT_WAVE_MAX = 256u << 10;     // a batch's entries of up to this many bytes: one wave each, in one launch
