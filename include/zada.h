@@ -361,7 +361,11 @@ int zada_lzma_device(zada_ctx *ctx, int method, const void *d_in, uint64_t n, vo
  * Feedback / User_abort (zip-compress-lzma_e.adb:78-92) turned into a checkpoint: a stream that takes longer than one call may run is coded in two.
  * A state is spent by the next zada_lzma / zada_lzma_device call whatever comes of it, and it is checked before the coder takes it: a blob that is not
  * a stopped stream's (length, phase) is refused by zada_lzma_import_state, one whose stream length, method level, (lc, lp, pb), dictionary or counters do not fit the
- * call it meets by that call (ZADA_E_INVALID both times).  What cannot be checked is the input's CONTENT: the same bytes are the caller's to hand over. */
+ * call it meets by that call (ZADA_E_INVALID both times).  What cannot be checked is the input's CONTENT: the same bytes are the caller's to hand over.
+ * The export must FOLLOW the stop: the context remembers that its last call was a zada_lzma that returned ZADA_ABORTED between two launches, and every
+ * other entry point that works on the context (any compress, inflate, crypt, range, batch or token call, zada_lzma_device and zada_lzma included)
+ * forgets it at its start -- such a call may reuse or re-allocate the buffer the stream so far lies in.  zada_lzma_export_state without that
+ * memory returns ZADA_E_INVALID (the length query with state = NULL is answered always); knobs, zada_last_* and zada_lzma_import_state leave it alone. */
 int zada_lzma_export_state(zada_ctx *ctx, uint8_t *state, uint64_t state_cap, uint64_t *state_len, uint8_t *out, uint64_t out_cap, uint64_t *out_bytes,
                            uint64_t *positions);
 int zada_lzma_import_state(zada_ctx *ctx, const uint8_t *state, uint64_t state_len);

@@ -76,7 +76,8 @@ def hostcheck():
         hdr = os.path.join(ROOT, "zip-ada_amd", "csrc", "zada_logic.h")
         hdr2 = os.path.join(d, "hostcheck_logic.h")
         hdr3 = os.path.join(ROOT, "zip-ada_amd", "csrc", "zada_bt4.h")
-        if not os.path.exists(p) or os.path.getmtime(p) < max(os.path.getmtime(f) for f in (src, hdr, hdr2, hdr3)):
+        hdr4 = os.path.join(ROOT, "zip-ada_amd", "csrc", "zada_sizing.h")
+        if not os.path.exists(p) or os.path.getmtime(p) < max(os.path.getmtime(f) for f in (src, hdr, hdr2, hdr3, hdr4)):
             subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", p, src], check=True)
         H = ctypes.CDLL(p)
         H.hc_chunked_tokens.restype = ctypes.c_uint64
@@ -88,8 +89,35 @@ def hostcheck():
         H.hc_bt4_sets.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32]
         H.hc_bt4_sets_segments.argtypes = H.hc_bt4_sets.argtypes + [ctypes.c_uint32]
         H.hc_bt4_reads_behind_a_gap.argtypes = [ctypes.c_uint64, ctypes.c_int64]
+        H.hc_sizing_range_request.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p]
+        H.hc_sizing_range_rooms.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
+        H.hc_sizing_span_booking.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p]
+        H.hc_sizing_entropy_room.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]
         _cache["h"] = H
     return _cache["h"]
+
+
+def booked_atoms(span, atoms_pct=50):
+    """Atoms the entropy workspace of a context with no history holds once deflate_spans has booked it for spans of `span` bytes
+    (zada_sizing.h through hostcheck: the product's own arithmetic)."""
+    q = (ctypes.c_uint64 * 2)(); r = (ctypes.c_uint64 * 3)()
+    H = hostcheck()
+    H.hc_sizing_span_booking(span, atoms_pct, q)
+    H.hc_sizing_entropy_room(q[0], q[1], r)
+    return int(r[0])
+
+
+def atsize_digest(name, data):
+    """The entry `name` of tests/golden/atsize_digests.json (the oracle's stream for an input of the at-size tests: size, SHA-256, CRC-32),
+    after checking that `data` (numpy uint8 or bytes) IS that input -- a corpus generator that has changed is a fixture to make again
+    (tests/golden/make_golden.py atsize), not a parity failure."""
+    import hashlib
+    import json
+    with open(os.path.join(GOLDEN, "atsize_digests.json")) as f:
+        e = json.load(f)[name]
+    assert len(data) == e["n"] and hashlib.sha256(memoryview(data)).hexdigest() == e["in_sha256"], \
+        "atsize_digests.json[%r] was taken on another input: the fixture is stale (make_golden.py atsize)" % name
+    return e
 
 
 def mixlib():

@@ -13,6 +13,9 @@
   lzma_digests.json   the same for the LZMA half (methods 15 .. 18), with the counters of the DL-code variants taken
   bzip2_digests.json  the same for the BZip2 half (methods 12 .. 14), with the block / tactic trace; every stream was
                       decompressed with libbz2 when the file was made
+  atsize_digests.json  SHA-256 + size + CRC of the oracle's stream for the streams the at-size GPU tests make (1 GiB to 4.2 GiB;
+                      `make_golden.py atsize`, needs neither the reference nor a GPU: the corpus generator and the oracle alone).
+                      BZip2_3 at size is left out (the oracle would take 80 minutes per stream): see ATSIZE below
   zlib_tokens_*.npz   position-indexed LZ77 tokens made by libz 1.2.11 deflateTune for the
                       fixture files (the independent pin of the LZ77 stage)
 """
@@ -122,7 +125,65 @@ def lzma_digests():
     json.dump(out, open(os.path.join(HERE, "lzma_digests.json"), "w"), indent=0, sort_keys=True)
 
 
+# The streams the at-size GPU tests make (tests/test_gpu_parity.py::test_full_size_properties, tests/test_gpu_atsize.py).  name ->
+# (corpus version, seed, n, method, through zo_compress_data).  The oracle runs one core at about 3 MB/s (Deflate_3) and 9 MB/s
+# (Deflate_1): the longest of the four takes about a quarter of an hour, `atsize` runs them as four processes side by side (each
+# needs about twice its input in RAM).  BZip2_3 at size (the 1.2 GiB and 1.125 GiB streams of test_gpu_atsize.py) is not here:
+# zo_bzip2 takes 64.5 s for 16 MiB of the corpus on one core, which projects to 82 and 77 minutes for the two streams -- beyond the
+# 45 minutes of one core set as the limit for a fixture that has to be made again whenever the corpus generator changes.
+ATSIZE = {
+    "c2_1gib_v2": (2, 0x5A1E51A, 1 << 30, 10, False),
+    "two_and_a_half_gib": (1, 0x5A1E51A, (5 << 29) + 12345, 10, False),
+    "c3_rank_shape": (1, 0x5A1E51A, (64 << 20) + (2 << 30) + (64 << 20), 10, False),
+    "zip64_big_bin": (1, 0x5A1E51A, (4 << 30) + (200 << 20) + 77, 8, True),
+}
+
+
+def atsize_one(name):
+    """One entry of atsize_digests.json, printed as a JSON line (no copy of the input or the stream is made on the way)."""
+    import time
+    from _common import mixlib
+    version, seed, n, method, through_compress_data = ATSIZE[name]
+    O = ctypes.CDLL(oracle()._name)                 # (a handle of its own: the input goes in as a pointer, not as bytes)
+    M = mixlib()
+    d = np.zeros(n, dtype=np.uint8)
+    (M.zada_silesia_mix_v2 if version >= 2 else M.zada_silesia_mix)(seed, 0x1F, 0, n, d.ctypes.data)
+    out = np.zeros(n + 64, dtype=np.uint8)
+    ol = ctypes.c_uint64(0)
+    crc = ctypes.c_uint32(0xFFFFFFFF)
+    pin, pout = ctypes.c_void_p(d.ctypes.data), ctypes.c_void_p(out.ctypes.data)
+    t0 = time.time()
+    if through_compress_data:
+        zt = ctypes.c_uint16(0)
+        rc = O.zo_compress_data(pin, ctypes.c_uint64(n), method, pout, ctypes.c_uint64(n + 64), ctypes.byref(ol), ctypes.byref(crc), ctypes.byref(zt))
+        assert zt.value == 8, zt.value
+        crc_final = crc.value
+    else:
+        rc = O.zo_deflate(pin, ctypes.c_uint64(n), method, pout, ctypes.c_uint64(n + 64), ctypes.byref(ol), ctypes.byref(crc), None, None, None, None)
+        crc_final = crc.value ^ 0xFFFFFFFF
+    assert rc == 0, rc
+    z = memoryview(out)[:ol.value]
+    e = dict(version=version, seed=seed, n=n, in_sha256=hashlib.sha256(memoryview(d)).hexdigest(), method=method,
+             through="zo_compress_data" if through_compress_data else "zo_deflate", rc=rc, size=ol.value,
+             sha256=hashlib.sha256(z).hexdigest(), crc=crc_final, oracle_seconds=round(time.time() - t0))
+    print(json.dumps({name: e}), flush=True)
+
+
+def atsize_digests():
+    import subprocess
+    procs = [(k, subprocess.Popen([sys.executable, os.path.abspath(__file__), "atsize", k], stdout=subprocess.PIPE)) for k in ATSIZE]
+    out = {}
+    for k, p in procs:
+        text = p.communicate()[0]
+        assert p.returncode == 0, k
+        out.update(json.loads(text.decode().strip().splitlines()[-1]))
+    json.dump(out, open(os.path.join(HERE, "atsize_digests.json"), "w"), indent=0, sort_keys=True)
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "atsize":
+        atsize_one(sys.argv[2]) if len(sys.argv) > 2 else atsize_digests()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "bzip2":
         bzip2_digests()
         sys.exit(0)

@@ -6,11 +6,30 @@
 #include <vector>
 #include "hostcheck_logic.h"
 #include "../../zip-ada_amd/csrc/zada_bt4.h"
+#include "../../zip-ada_amd/csrc/zada_sizing.h"
 #include <algorithm>
 #include <numeric>
 using namespace zada;
 
 extern "C" {
+
+// zada_sizing.h as the product calls it: q = {atoms, out_bytes} asked for, r = {cap_atoms, out_need, cap_out}.
+void hc_sizing_range_request(uint64_t n, int atoms_pct, uint64_t carry_atoms, uint64_t *q) {
+  const EntropyRequest e = sizing_range_request(n, sizing_pct(atoms_pct), carry_atoms); q[0] = e.atoms; q[1] = e.out_bytes;
+}
+void hc_sizing_span_booking(uint64_t span, int atoms_pct, uint64_t *q) {
+  const EntropyRequest e = sizing_span_booking(span, sizing_pct(atoms_pct)); q[0] = e.atoms; q[1] = e.out_bytes;
+}
+// ... for many range lengths at once: what each range_open asks for (atoms) and the output room it needs (out_need)
+void hc_sizing_range_rooms(const uint64_t *n, uint64_t count, int atoms_pct, uint64_t carry_atoms, uint64_t *atoms, uint64_t *out_need) {
+  for (uint64_t i = 0; i < count; i++) {
+    const EntropyRequest e = sizing_range_request(n[i], sizing_pct(atoms_pct), carry_atoms);
+    atoms[i] = e.atoms; out_need[i] = sizing_entropy_room(e).out_need;
+  }
+}
+void hc_sizing_entropy_room(uint64_t atoms, uint64_t out_bytes, uint64_t *r) {
+  const EntropyRoom e = sizing_entropy_room(EntropyRequest{atoms, out_bytes}); r[0] = e.cap_atoms; r[1] = e.out_need; r[2] = e.cap_out;
+}
 
 void hc_llhc(const uint32_t *freq, int n, int max_bits, uint8_t *bl) {
   static LlhcScratch S;

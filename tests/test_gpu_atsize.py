@@ -1,9 +1,14 @@
 """At-size checks and soak seeds, under pytest so that the driver's `-m gpu` run sees them (round 2 kept them as one-off scripts).
 
-At BASELINE's sizes the oracle is out of reach (11 MB/s), so the checks are the size-independent ones: the stream of ONE call equals
-the stream of the same input cut over several contexts (two different cuts of the sequential encoder's state), and an independent
-decoder (zlib / libbz2 / zipfile) gives the input back.  The soak seeds compare random cases with the oracle byte for byte."""
+At BASELINE's sizes the oracle takes minutes per stream (3 to 10 MB/s on one core), too long for a GPU run but not for a fixture: the Deflate
+streams here are compared with the size, SHA-256 and CRC-32 of the ORACLE's stream for the same input, taken once on a CPU and kept in
+tests/golden/atsize_digests.json (`tests/golden/make_golden.py atsize`; _common.atsize_digest checks first that the input is the one the
+digest was taken on).  The BZip2_3 streams have no such digest -- the oracle would need 80 minutes for each -- and keep the size-independent
+checks, which the Deflate streams have as well: the stream of ONE call equals the stream of the same input cut over several contexts (two
+different cuts of the sequential encoder's state), and an independent decoder (zlib / libbz2 / zipfile) gives the input back.  The soak seeds
+compare random cases with the oracle byte for byte."""
 import bz2
+import hashlib
 import io
 import os
 import zipfile
@@ -12,7 +17,7 @@ import zlib
 import numpy as np
 import pytest
 
-from _common import oracle_deflate, product
+from _common import atsize_digest, oracle_deflate, product
 from test_ranges import deflate_over_contexts
 
 pytestmark = pytest.mark.gpu
@@ -38,12 +43,13 @@ def _inflate_crc(stream):
 
 def test_deflate_stream_of_two_and_a_half_gib(encoder):
     """A 2.5 GiB Deflate_3 stream in ONE call on one context (device buffers: two spans of the default 2 GiB, the first in two 1 GiB
-    shards) == the same stream as two ranges on two contexts (512 MiB shards, boundary state exchanged) == the input after zlib's
-    inflate, with the CRC-32 the calls deliver."""
+    shards) == the oracle's stream (size, SHA-256 and CRC-32 of atsize_digests.json) == the same stream as two ranges on two contexts
+    (512 MiB shards, boundary state exchanged) == the input after zlib's inflate, with the CRC-32 the calls deliver."""
     import torch
     za = product()
     n = (5 << 29) + 12345
     host = za.silesia_mix(n)
+    digest = atsize_digest("two_and_a_half_gib", host)
     want_crc = zlib.crc32(host)
     t_in = torch.from_numpy(host).cuda()
     t_out = torch.empty(n + 4096, dtype=torch.uint8, device="cuda")
@@ -52,6 +58,7 @@ def test_deflate_stream_of_two_and_a_half_gib(encoder):
     one = bytes(t_out[:ol].cpu().numpy())
     del t_in, t_out
     torch.cuda.empty_cache()
+    assert (len(one), hashlib.sha256(one).hexdigest(), want_crc) == (digest["size"], digest["sha256"], digest["crc"])
     c, tot, eof = _inflate_crc(one)
     assert tot == n and c == want_crc and eof
     encoder.close()                                  # (its workspace: about 100 GiB of HBM)
@@ -63,10 +70,12 @@ def test_deflate_stream_of_two_and_a_half_gib(encoder):
 def test_zip64_entry_beyond_four_gib(encoder):
     """Zip.Create promotes an archive to Zip_64 when an entry does not fit 32 bits (zip-create.adb:161-179, local header extension
     :237-251, central extension and end records :682-752).  A 4.2 GiB entry through zada_compress_data (host buffers, span after
-    span) and ZipCreate, read back by Python's zipfile, entries before and behind it included."""
+    span) and ZipCreate, read back by Python's zipfile, entries before and behind it included; the entry's compressed bytes in the archive are
+    those the oracle's Compress_Data writes for it (size, SHA-256 and CRC-32 of atsize_digests.json)."""
     za = product()
     n = (4 << 30) + (200 << 20) + 77
     big = za.silesia_mix(n)
+    digest = atsize_digest("zip64_big_bin", big)
     zc = za.ZipCreate(encoder, za.Method.Deflate_1)
     first = za.silesia_mix(100000, class_mask=1).tobytes()
     zc.add_stream("small/first.txt", first)
@@ -78,6 +87,12 @@ def test_zip64_entry_beyond_four_gib(encoder):
     infos = zf.infolist()
     assert [i.filename for i in infos] == ["small/first.txt", "big.bin", "small/last.txt"]
     assert infos[1].file_size == n and infos[1].compress_type == 8 and infos[1].compress_size < n // 2
+    # big.bin's payload: behind its local header (30 bytes, the name, the extra field with the Zip_64 extension)
+    lo = infos[1].header_offset
+    name_len, extra_len = int.from_bytes(arc[lo + 26:lo + 28], "little"), int.from_bytes(arc[lo + 28:lo + 30], "little")
+    payload = memoryview(arc)[lo + 30 + name_len + extra_len:][:infos[1].compress_size]
+    assert arc[lo:lo + 4] == b"PK\x03\x04" and (infos[1].compress_size, hashlib.sha256(payload).hexdigest(), infos[1].CRC) == (digest["size"], digest["sha256"], digest["crc"])
+    del payload
     crc = 0
     with zf.open("big.bin") as f:
         while True:
@@ -118,12 +133,14 @@ def test_c3_rank_shape_two_gib_range_between_its_neighbours(encoder):
     its size, on the one GPU there is: a 2 GiB range cut from the middle of a longer stream, the boundary state it needs (parser
     states, edge atoms, the 352-byte chooser state) produced by contexts on the 64 MiB ranges on either side of it, all through
     sharding.deflate_stream_rank -- the code a rank of bench.py runs.  The stitched stream == the stream of ONE call on the whole input
-    (another cut of the sequential encoder's state) == the input after zlib's inflate, with the combined CRC-32."""
+    (another cut of the sequential encoder's state) == the oracle's stream (size, SHA-256 and CRC-32 of atsize_digests.json) == the input
+    after zlib's inflate, with the combined CRC-32."""
     import torch
     za = product()
     side, mid = 64 << 20, 2 << 30
     n = side + mid + side
     host = za.silesia_mix(n)
+    digest = atsize_digest("c3_rank_shape", host)
     want_crc = zlib.crc32(host)
     t_in = torch.from_numpy(host).cuda()
     t_out = torch.empty(n // 2 + (64 << 20), dtype=torch.uint8, device="cuda")
@@ -136,6 +153,7 @@ def test_c3_rank_shape_two_gib_range_between_its_neighbours(encoder):
     ranges = [(0, side), (side, mid), (side + mid, side)]
     rc2, three, crc2, res = deflate_over_contexts(host, 3, 10, ranges=ranges)
     assert rc2 == 0 and crc2 == crc and three == one, (len(three), len(one))
+    assert (len(three), hashlib.sha256(three).hexdigest(), want_crc) == (digest["size"], digest["sha256"], digest["crc"])
     assert res[1]["infos"][1]["n"] == mid and res[1]["bit_begin"] == res[0]["bit_end"] and res[2]["bit_begin"] == res[1]["bit_end"]
     c, tot, eof = _inflate_crc(three)
     assert tot == n and c == want_crc and eof

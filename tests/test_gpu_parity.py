@@ -11,7 +11,7 @@ import zlib
 import numpy as np
 import pytest
 
-from _common import GOLDEN, METHODS, edge_inputs, few_symbol_inputs, oracle_deflate, oracle_tokens, oracle_zip, product, silesia_mix
+from _common import GOLDEN, METHODS, atsize_digest, booked_atoms, edge_inputs, few_symbol_inputs, oracle_deflate, oracle_tokens, oracle_zip, product, silesia_mix
 
 pytestmark = pytest.mark.gpu
 FIXTURE_FILES = ("sample.xls", "sample.jpg", "sample_pgm_100k.bin")
@@ -319,13 +319,16 @@ def test_archive_of_many_small_files_equals_the_oracles(encoder):
 
 
 def test_full_size_properties(encoder):
-    """BASELINE config C2 size (1 GiB, Deflate_3): properties that do not need the oracle at full size --
-    the stream inflates back to the input (independent inflater), CRC equals zlib's, and the first
-    16 MiB compressed alone equal the oracle's stream (the encoder is a pure function).  The benchmark stream (silesia_mix_v2)."""
+    """BASELINE config C2 size (1 GiB, Deflate_3), the benchmark stream (silesia_mix_v2): the stream IS the oracle's -- its size and SHA-256
+    are those of tests/golden/atsize_digests.json, which `make_golden.py atsize` took from the oracle's stream for this input --, it inflates
+    back to the input (independent inflater), the CRC equals zlib's, and the first 16 MiB compressed alone equal the oracle's stream (the
+    encoder is a pure function)."""
     za = product()
     n = 1 << 30
     d = za.silesia_mix(n, version=2)
+    digest = atsize_digest("c2_1gib_v2", d)
     out, crc = encoder.deflate(d, 10)
+    assert (len(out), hashlib.sha256(out).hexdigest(), crc ^ 0xFFFFFFFF) == (digest["size"], digest["sha256"], digest["crc"])
     dec = zlib.decompressobj(-15)
     h = hashlib.sha256()
     total = 0
@@ -441,15 +444,25 @@ def test_workspace_guesses_that_turn_out_too_small(encoder):
                 assert grown[0] >= 1 and grown[1] >= 1, grown            # both fall-backs really ran
             else:
                 assert grown[1] == 0 or stride, grown
-        # ... and in a stream that goes through one context span after span (the atoms carried from span to span live in the arrays that grow)
-        d = inputs[2] + inputs[0]
-        encoder.set_knob("span_mib", 4); encoder.set_knob("shard_kib", 1 << 20)
+        # ... and in a stream that goes through one context span after span (the atoms carried from span to span live in the arrays that grow):
+        # spans of 8 MiB -- a stream in spans of 4 MiB cannot outgrow its booking, which is for one atom per byte of a range below 4 MiB
+        # (zada_sizing.h) --, the second one 6 MiB of random bytes, one atom each: more than the 1 % guess books, so the arrays grow while they
+        # hold the first span's carried atoms
+        d = inputs[0] + inputs[2] + inputs[1]
+        span = 8 << 20
+        encoder.set_knob("span_mib", 8); encoder.set_knob("shard_kib", 1 << 20)
         for method in (10, 7):
             rc, ref, crc = oracle_deflate(d, method)
+            t = oracle_tokens(d, method)
+            starts = np.concatenate(([0], np.cumsum(np.where(t & 0x80000000, (t >> 16) & 0x1FF, 1).astype(np.int64))[:-1]))
+            per_span = np.bincount(starts // span)
+            # precondition: growth is certain -- with Deflate_3 in the second span, behind carried atoms (Deflate_0 has an atom per byte everywhere)
+            assert per_span.max() > booked_atoms(span, 1), (method, per_span)
+            assert method != 10 or (per_span[1] > booked_atoms(span, 1) > per_span[0] and per_span[0] % 65536 != 0), per_span
             encoder.set_knob("atoms_pct", 1)
             rc2, out, crc2 = gpu_deflate(encoder, d, method)
             assert rc == rc2 and (rc != 0 or (out == ref and crc == crc2)), ("spans", method)
-            assert dict(encoder.last_timing()).get("#atoms_grown", 0) >= 0
+            assert dict(encoder.last_timing()).get("#atoms_grown", 0) >= 1
     finally:
         encoder.set_knob("atoms_pct", 50); encoder.set_knob("fix_stride", 0); encoder.set_knob("shard_kib", 1 << 20); encoder.set_knob("span_mib", 2048)
 

@@ -292,3 +292,79 @@ def test_fused_cross_links_model():
             w = want[s * SEG:(s + 1) * SEG]
             assert np.array_equal(got, w), (trial, s, int(np.argmax(got != w)))
             prev_tails = tails
+
+
+# ---- the entropy workspace of a spanned stream is booked once (zada_sizing.h) ----
+
+SIZING_SPANS_MIB = list(range(1, 65)) + [128, 512, 1024, 2048, 3968]
+
+
+def _sizing_lengths(span):
+    """The span itself and every k * 65536 + {0, 1, 65535} up to min(span, 8 MiB): the lengths a span of the stream can have (the last
+    one any length; 65 536-byte steps cover both sides of every step of the guess)."""
+    top = min(span, 8 << 20)
+    k = np.arange(0, top // 65536 + 1, dtype=np.uint64) * np.uint64(65536)
+    n = np.concatenate([k, k + np.uint64(1), k + np.uint64(65535), np.array([span], dtype=np.uint64)])
+    return np.unique(n[(n > 0) & (n <= span)])
+
+
+def _sizing_violations(H, booking):
+    """(span_mib, pct, n, carry, atoms asked, atoms booked, out_need, cap_out) of the first length per (span, pct) whose range_open would
+    make ensure_entropy_workspace book anew -- `booking(span, pct)` -> the (atoms, out_bytes) deflate_spans asks for."""
+    bad = []
+    r = (ctypes.c_uint64 * 3)()
+    for span_mib in SIZING_SPANS_MIB:
+        span = span_mib << 20
+        n = _sizing_lengths(span)
+        atoms = np.zeros(len(n), dtype=np.uint64); need = np.zeros(len(n), dtype=np.uint64)
+        for pct in range(1, 101):
+            ba, bo = booking(span, pct)
+            H.hc_sizing_entropy_room(ba, bo, r)
+            cap_atoms, cap_out = int(r[0]), int(r[2])
+            assert cap_atoms >= ba and cap_out >= int(r[1])             # a booking satisfies its own request
+            for carry in (1, 65536):                                    # range_open gets Tc + 1, Tc < 65 536
+                H.hc_sizing_range_rooms(n.ctypes.data, len(n), pct, carry, atoms.ctypes.data, need.ctypes.data)
+                short = (atoms > cap_atoms) | (need > cap_out)
+                if short.any():
+                    i = int(np.argmax(short))
+                    bad.append((span_mib, pct, int(n[i]), carry, int(atoms[i]), cap_atoms, int(need[i]), cap_out))
+                    break
+    return bad
+
+
+def test_a_span_never_asks_for_more_than_the_stream_booked():
+    """deflate_spans books the entropy workspace once; between two spans the carried atoms and their look-behind live in it, and
+    ensure_entropy_workspace frees the arrays when a request exceeds what is there.  So for every "span_mib" (1 .. 64 and 128, 512, 1024, 2048,
+    3968), every "atoms_pct" (1 .. 100), every span length n (the span itself and every k * 65536 + {0, 1, 65535} up to min(span, 8 MiB)) and 1 or
+    65 536 carried atoms, what range_open asks for -- atoms and output room -- is within what deflate_spans booked on a context that had
+    nothing: the three functions the product itself calls (zada_sizing.h), compared with ensure_entropy_workspace's own condition."""
+    H = hostcheck()
+
+    def booking(span, pct):
+        q = (ctypes.c_uint64 * 2)()
+        H.hc_sizing_span_booking(span, pct, q)
+        return int(q[0]), int(q[1])
+    bad = _sizing_violations(H, booking)
+    assert not bad, (len(bad), bad[:5])
+
+
+def test_the_sizing_check_catches_a_booking_by_the_span_s_own_guess():
+    """The check above is not vacuous: a booking by the guess of a FULL span alone (span / 100 * pct + 1 MiB, at most the span, + a flush +
+    4096: what deflate_spans asked for before zada_sizing.h) fails it -- a span below 4 MiB is guessed at one atom per byte, a longer one by
+    the percentage, so a shorter last span can ask for more than a full one.  With the default "atoms_pct" 50: "span_mib" 3 (every span
+    behind the first) and 4 and 5 (a last span a little shorter than the span); with 1: every "span_mib" from 2 to 128; 932 of the 6 900
+    (span, pct) pairs in all."""
+    H = hostcheck()
+
+    def by_full_span_guess(span, pct):
+        g = span // 100 * pct + (1 << 20)
+        return min(g, span) + 65536 + 4096, span + 65536 + 4096
+    bad = {(b[0], b[1]): b for b in _sizing_violations(H, by_full_span_guess)}
+    assert [m for m in SIZING_SPANS_MIB if (m, 50) in bad] == [3, 4, 5]
+    q = (ctypes.c_uint64 * 2)()
+    H.hc_sizing_range_request(3 << 20, 50, 1, q)
+    assert bad[(3, 50)][5] == 2752512 and int(q[0]) == (3 << 20) + 1      # booked / what every full span behind the first asks for
+    assert (3 << 20) < bad[(4, 50)][2] < (4 << 20)
+    assert all((m, 1) in bad for m in range(2, 65)) and (1, 1) not in bad
+    assert sum(1 for k in bad if k[1] in (1, 2, 3, 5, 10, 25, 50, 75, 100)) == 289 and len(bad) == 932        # of 630 / of 6 900 pairs
+    assert all(b[4] > b[5] for b in bad.values())                    # (the atoms, never the output room, which both book by the span)

@@ -205,14 +205,13 @@ int ensure_lz_workspace(Ctx *c, uint64_t nbuf) {
 // Entropy stage: sized for the atoms of one range (worst case one atom per byte) and its output.
 int ensure_entropy_workspace(Ctx *c, uint64_t atoms, uint64_t flushes, uint64_t out_bytes) {
   Workspace &W = c->ws;
+  const EntropyRoom room = sizing_entropy_room(EntropyRequest{atoms, out_bytes});      // (zada_sizing.h)
   if (out_bytes < atoms) out_bytes = atoms;
-  const uint64_t out_need = out_bytes + out_bytes / 8 + (1u << 20);
-  if (W.cap_atoms >= atoms && W.cap_flush >= flushes && W.cap_atoms > 0 && W.cap_out >= out_need) return 0;
+  if (W.cap_atoms >= atoms && W.cap_flush >= flushes && W.cap_atoms > 0 && W.cap_out >= room.out_need) return 0;
   hipStreamSynchronize(c->stream); hipStreamSynchronize(c->stream2);
   free_group(W.en_allocs);
   W.cap_atoms = 0; W.cap_flush = 0;
-  uint64_t cap = atoms < (1u << 20) ? (1u << 20) : atoms;
-  cap = (cap + 65535) & ~65535ull;
+  const uint64_t cap = room.cap_atoms;
   // flushes: one per 65 536 atoms of a stream; a batch of small entries has (at least) one per entry
   const uint64_t nflush = (cap / FLUSH > flushes ? cap / FLUSH : flushes + flushes / 4) + 3;
   int rc = 0;
@@ -235,11 +234,7 @@ int ensure_entropy_workspace(Ctx *c, uint64_t atoms, uint64_t flushes, uint64_t 
   A(blk_entry, W.cap_blocks + 16);
   A(chooser, 1); A(carry, 2);
   A(scan2, nflush / 1024 + 1024); A(total2, 16);
-  // the largest stream the encoder can produce for `cap` bytes: every literal in nine bits (fixed code) + block overheads
-  {
-    const uint64_t ob = ((out_bytes < (1u << 20) ? (1u << 20) : out_bytes) + 65535) & ~65535ull;
-    W.cap_out = ob + ob / 8 + (1u << 20);
-  }
+  W.cap_out = room.cap_out;
   A(out, W.cap_out);
 #undef A
   if (!rc) rc = ensure_crc_workspace(c, out_bytes > cap ? out_bytes : cap);
@@ -529,9 +524,8 @@ int range_open(Ctx *c, int method, const uint8_t *rin, uint64_t stream_size, uin
   // The atom arrays start with room for "atoms_pct" atoms per 100 bytes (one atom per byte is the worst case, the benchmark stream has 0.3) and grow
   // when a shard has more (range_lz: grow_atoms); everything the entropy stage sizes by atoms is the smaller for it.  A workspace that is large enough
   // already (an earlier, larger call) stays as it is.
-  const uint64_t pct = c->knob_atoms_pct < 1 ? 1 : c->knob_atoms_pct > 100 ? 100 : (uint64_t)c->knob_atoms_pct;
-  const uint64_t guess = n < (4u << 20) ? n : n / 100 * pct + (1u << 20);
-  int rc = ensure_entropy_workspace(c, (guess < n ? guess : n) + carry_atoms, 0, n);
+  const EntropyRequest want = sizing_range_request(n, sizing_pct(c->knob_atoms_pct), carry_atoms);
+  int rc = ensure_entropy_workspace(c, want.atoms, 0, want.out_bytes);
   if (!rc) rc = ensure_lz_workspace(c, (n < shard ? n : shard) + SHARD_HALO + SHARD_TAIL);
   if (rc) return rc;
   Range &R = c->rg;
@@ -743,11 +737,10 @@ static int deflate_spans(Ctx *c, int method, const uint8_t *d_src, const uint8_t
   if (fb && fb(0, user)) return ZADA_ABORTED;
   c->tbegin(); c->tmark("begin");
   // (The entropy workspace is booked once, for the largest request a span can make -- range_open asks for its guess plus the carried atoms, fewer than a
-  // flush --, so that it is never booked anew between spans: the carried atoms live in it.  A span with more atoms than the guess enlarges it through
-  // range_lz's grow_atoms, which keeps them.)
-  const uint64_t pct = c->knob_atoms_pct < 1 ? 1 : c->knob_atoms_pct > 100 ? 100 : (uint64_t)c->knob_atoms_pct;
-  const uint64_t sguess = span / 100 * pct + (1u << 20);
-  int rc = ensure_entropy_workspace(c, (sguess < span ? sguess : span) + FLUSH + 4096, 0, span + FLUSH + 4096);
+  // flush; the guess of a last span SHORTER than the span can be the larger one, zada_sizing.h --, so that it is never booked anew between spans: the
+  // carried atoms live in it.  A span with more atoms than the guess enlarges it through range_lz's grow_atoms, which keeps them.)
+  const EntropyRequest booking = sizing_span_booking(span, sizing_pct(c->knob_atoms_pct));
+  int rc = ensure_entropy_workspace(c, booking.atoms, 0, booking.out_bytes);
   if (rc) return rc;
   GlobalState entry{0, SYNC_F, 0};
   uint64_t G = 0, ws_prev = 0, carry_first_byte = 0, base_bytes = 0;
@@ -756,7 +749,7 @@ static int deflate_spans(Ctx *c, int method, const uint8_t *d_src, const uint8_t
   ChooserCarry cc = ChooserCarry();
   cc.last_type = BT_RESERVED; cc.cur_eob = 7u << 16;
   bool inefficient = false;
-  int total_demand = 0, total_splice = 0;
+  int total_demand = 0, total_splice = 0, total_atoms_grown = 0, total_fix_grown = 0;
   for (uint64_t lo = 0; lo < n; lo += span) {
     const uint64_t hi = lo + span < n ? lo + span : n;
     const bool last = hi == n;
@@ -780,7 +773,7 @@ static int deflate_spans(Ctx *c, int method, const uint8_t *d_src, const uint8_t
       hipLaunchKernelGGL(k_add_u32, dim3((nlb + Tc + 255) / 256), dim3(256), 0, st, W.ea_apos + LB_CAP - nlb, nlb + Tc, (uint32_t)(ws_prev - ws));
     rc = range_lz(c, lo > 0 ? &entry : nullptr, nullptr, nullptr);
     if (rc) return rc;
-    total_demand += c->demand_rounds; total_splice += c->parse_rounds;
+    total_demand += c->demand_rounds; total_splice += c->parse_rounds; total_atoms_grown += c->atoms_grown; total_fix_grown += c->fix_grown;
     // what the entropy stage takes now: whole flushes (the stream's position on the flush grid is G, a multiple of 65 536)
     const uint64_t tview = last ? R.T : R.T / FLUSH * FLUSH;
     R.G = G; R.n_la = 0; R.T_view = tview; R.T_total = last ? G + R.T : ~0ull >> 2;
@@ -838,7 +831,7 @@ static int deflate_spans(Ctx *c, int method, const uint8_t *d_src, const uint8_t
     crc = crc32_advance(crc, hi - lo) ^ R.crc_raw;
     if (fb && fb((int)(100 * hi / n), user)) return ZADA_ABORTED;
   }
-  c->demand_rounds = total_demand; c->parse_rounds = total_splice;
+  c->demand_rounds = total_demand; c->parse_rounds = total_splice; c->atoms_grown = total_atoms_grown; c->fix_grown = total_fix_grown;      // (of all spans: range_open starts them at 0)
   c->tmark("end"); c->tend();
   *out_len = inefficient ? base_bytes : (cc.pos + 7) / 8;
   if (crc_inout) *crc_inout = crc;
@@ -1198,6 +1191,7 @@ static int copy_out(Ctx *c, uint8_t *dst, const void *d_src, uint64_t n) {
 static int prepare(zada_ctx *z) {
   if (!z) return ZADA_E_INVALID;
   if (hipSetDevice(z->c.device) != hipSuccess) return ZADA_E_HIP;
+  z->c.lz_stopped = z->c.lz_run_stopped = false;                  // (whatever this call does to the context's buffers, a stopped LZMA stream is no longer there to export)
   return 0;
 }
 
@@ -1547,6 +1541,7 @@ static int lzma_run(Ctx *c, std::vector<LzmaJob> &jobs, const uint8_t *d_in, uin
         if (!more) break;
         if (fb && fb(pct_lo + (int)((uint64_t)(pct_hi - pct_lo) * coded / (total ? total : 1)), user)) {
           if (seg_shift < 32) hipStreamSynchronize(c->stream2);      // (walks under way write into the context's buffers)
+          c->lz_run_stopped = E == 1;                                // (between two launches: lz_save holds the coder's state)
           return ZADA_ABORTED;
         }
         if (coded >= cap) break;
@@ -1646,6 +1641,7 @@ int zada_lzma(zada_ctx *z, int method, const uint8_t *in, uint64_t n, uint8_t *o
   c->lz_last_n = n; c->lz_last_out_off = (n + 63) & ~63ull;
   rc = finish_call(c, lzma_core(c, method, c->ws.rin_own, n, d_out, cap, &ol, crc_inout, fb, user));
   c->lz_resume.clear();                                           // (an imported state is for one call)
+  c->lz_stopped = rc == ZADA_ABORTED && c->lz_run_stopped;        // (until the next entry point: zada_lzma_export_state)
   if (rc < 0 || rc == ZADA_ABORTED) return rc;
   if (out_len) *out_len = ol;
   if (ol <= cap && copy_out(c, out, d_out, ol)) return ZADA_E_HIP;
@@ -1662,6 +1658,7 @@ int zada_lzma_export_state(zada_ctx *z, uint8_t *state, uint64_t state_cap, uint
   const uint64_t sb = lzma_save_stride();
   if (state_len) *state_len = sb;
   if (!state) return ZADA_OK;                                      // (the length only)
+  if (!c->lz_stopped) { c->err = "zada_lzma_export_state: the last call on this context was not a zada_lzma that stopped between two launches of ONE stream"; return ZADA_E_INVALID; }
   if (!c->lz_save || c->cap_lz_save < sb || state_cap < sb) { c->err = "zada_lzma_export_state: no stopped stream, or the state buffer is too small"; return ZADA_E_INVALID; }
   if (c->lz_last_lit_hbm) { c->err = "zada_lzma_export_state: the stream's method keeps its literal table in HBM (lc + lp >= 4); its state is not exported"; return ZADA_E_INVALID; }
   if (hipSetDevice(c->device) != hipSuccess) return ZADA_E_HIP;

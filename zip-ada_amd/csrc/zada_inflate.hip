@@ -413,6 +413,7 @@ static constexpr uint64_t INF_MAX_BYTES = 1ull << 40;
 
 static int inf_prepare(zada_ctx *z, int format, const char *who) {
   if (!z) return ZADA_E_INVALID;
+  z->c.lz_stopped = false;                                          // (as every entry point: zada_lzma_export_state)
   if (format != 8 && format != 9) { z->c.err = std::string(who) + ": format must be 8 (Deflate) or 9 (Deflate64)"; return ZADA_E_INVALID; }
   return 0;
 }
@@ -448,6 +449,7 @@ int zada_inflate_batch(zada_ctx *z, int count, const int *format, const uint8_t 
                        uint64_t *out_len, uint64_t *in_used, uint32_t *crc, int *rc_out) {
   if (!z || count < 0) return ZADA_E_INVALID;
   Ctx *c = &z->c;
+  c->lz_stopped = false;
   if (count && (!format || !in || !n_in || !cap || !rc_out)) { c->err = "zada_inflate_batch: null argument"; return ZADA_E_INVALID; }
   for (int i = 0; i < count; i++) {
     if (format[i] != 8 && format[i] != 9) { c->err = "zada_inflate_batch: format must be 8 (Deflate) or 9 (Deflate64)"; return ZADA_E_INVALID; }
@@ -535,6 +537,7 @@ int zada_inflate(zada_ctx *z, int format, const uint8_t *in, uint64_t n_in, uint
 int zada_crypt_decode_batch(zada_ctx *z, int count, uint32_t (*keys)[3], uint8_t *const *buf, const uint64_t *n) {
   if (!z || count < 0) return ZADA_E_INVALID;
   Ctx *c = &z->c;
+  c->lz_stopped = false;
   if (count && (!keys || !buf || !n)) { c->err = "zada_crypt_decode_batch: null argument"; return ZADA_E_INVALID; }
   for (int i = 0; i < count; i++) if (n[i] && !buf[i]) { c->err = "zada_crypt_decode_batch: null buffer"; return ZADA_E_INVALID; }
   if (count == 0) return ZADA_OK;

@@ -9,6 +9,7 @@
 #include <functional>
 #include <vector>
 #include "zada_logic.h"
+#include "zada_sizing.h"
 
 namespace zada {
 
@@ -40,6 +41,7 @@ struct DistPlanes {
 
 // ---- entropy stage geometry (zip-compress-deflate.adb:942, 1294, 1313) ----
 constexpr uint32_t FLUSH = 65536;                 // atoms per Flush_half_buffer
+static_assert(FLUSH == SIZING_FLUSH, "zada_sizing.h books the carried atoms by the flush");
 constexpr uint32_t MIN_STEP = 750, HALF_SLIDER = 2048, SLIDER = 4096;
 constexpr uint32_t SLOTS = 88;                    // descriptor slots per flush segment (1 initial + <= 84 sliding)
 constexpr uint32_t MAXBLK_PER_SEG = 86;
@@ -269,6 +271,9 @@ struct Ctx {
                                                      // groups; 12 GiB: 2 048 tables of 6 MiB, as many entries as the coder has workgroups in flight)
   int lzma_launches = 0;                             // launches the last chunked LZMA call took
   std::vector<uint8_t> lz_resume;                    // zada_lzma_import_state: the coder's state the next zada_lzma call goes on from (one stream)
+  bool lz_stopped = false;                           // the last call on the context was a zada_lzma that returned ZADA_ABORTED between two launches: every entry point
+                                                     // clears it at its start (prepare), zada_lzma_export_state refuses without it
+  bool lz_run_stopped = false;                       // ... lzma_run's part of it: it returned between two launches of one stream
   uint64_t lz_last_n = 0, lz_last_out_off = 0;       // the last zada_lzma call: its input length and where its stream lies in the context's buffer (zada_lzma_export_state)
   void *bt4 = nullptr;                               // ... the BT4 match producer's buffers (zada_bt4.hip), made on first use
   uint32_t bt4_buckets = 0, bt4_long = 0, bt4_overflow = 0;   // last producer run: hash-4 buckets, long ones among them, overflow blocks booked
