@@ -95,7 +95,7 @@ enum {
                              * bytes that no window fill took up, :1000-1017, 1397-1406: lzPos lags behind readPos) and the reference's own stream does not
                              * decode to the input.  Cannot happen with the dictionary Zip.Compress.LZMA_E asks for unless the entry is beyond 256 MiB and its
                              * last window fill brings 163 .. 4 368 bytes; the shim Stores such an entry or takes another method.  Nothing was written. */
-  ZADA_E_DATA = -7          /* zada_inflate* only: the compressed data is not a valid stream (Zip.Archive_corrupted); zada_last_error names the rule and the bit */
+  ZADA_E_DATA = -7          /* zada_inflate* and zada_bunzip2* only: the compressed data is not a valid stream (Zip.Archive_corrupted); zada_last_error names the rule and the bit */
 };
 
 typedef struct zada_ctx zada_ctx;
@@ -120,7 +120,7 @@ const char *zada_version(void);
  * needs more gets the full 1152 and the parse starts again), "inner_budget" (ZADA_INNER_BUDGET), "shard_kib" (ZADA_SHARD_KIB: KiB of
  * a stream the match finder takes at a time, multiple of 64), "span_mib" (MiB of a stream one pass takes; longer streams go span after
  * span, default 2048), "link_run" (segments of 32 KiB one workgroup of the link stage takes one after the other, making their cross links itself:
- * a power of two from 1 to 64, 0 = by size; anything else is ZADA_E_INVALID), "batch_mib" (MiB one batch of small entries may take), "bz_batch_mib" / "bz_span_mib" / "bz_batch_melems" (BZip2
+ * a power of two from 1 to 64, 0 = by size; anything else is ZADA_E_INVALID), "batch_mib" (MiB one batch of small entries may take), "bunzip_batch_mib" (MiB of HBM one group of zada_bunzip2_batch may take: streams, outputs, slots, tt arrays; 16 .. 262144, default 8192), "bz_batch_mib" / "bz_span_mib" / "bz_batch_melems" (BZip2
  * batching; "bz_lists", "bz_list_rows", "bz_text_order", "bz_pipeline", "bz_pipe_prio", "bz_small_wg", "bz_split", "bz_tail_pct": scheduling of the BZip2 stages), "lzma_chunk" (positions of an LZMA stream one launch codes between two feedback calls; 0 = by level, -1 = one launch
  * per stream), "lzma_pool" (test knob: blocks of the LZMA_3 match sets' overflow pool to start with, 0 = by size; a pool that is too small is
  * counted and the match producer's walk runs again; for a stream whose producer works in segments the pool grows between the segments), "lzma_pool_fixed" (test knob: 1 = it
@@ -239,6 +239,42 @@ int zada_inflate_batch(zada_ctx *ctx, int count, const int *format, const uint8_
  * zada_compress_data_pw writes (the first 12 bytes decode to the encryption header, whose last byte is the entry's check byte).  Unlike
  * Encode it is serial -- key 0 is a CRC over the PLAIN text, known only byte by byte -- so there is no scan: one lane per buffer. */
 int zada_crypt_decode_batch(zada_ctx *ctx, int count, uint32_t (*keys)[3], uint8_t *const *buf, const uint64_t *n);
+
+/* ---- The reader: BZip2.Decoding.Decompress (bzip2-decoding.adb; Zip format 12) ---------------------------------------
+ * One BZip2 stream back into bytes.  Unlike Deflate, a BZip2 stream is parallel INSIDE: a block starts with a 48-bit magic and is
+ * independent of the others, so the unit of work is the block -- ten thousand entries of one block each and one stream of three hundred
+ * blocks run through the same launches (csrc/zada_bunzip2.hip): a scan of every bit position for the magics, one wave per
+ * candidate block for the Huffman / MTF chain (the only serial part, csrc/zada_bunzip2_logic.h), then the inverse BWT as a counting sort and a
+ * walk between splitters, RLE_1 as a prefix sum and a fill, and bzip2's CRC -- all parallel inside a block.  The result is exactly the
+ * serial reading: candidates the chain of end bits never reaches are dropped.  crc_inout, cap, out_len, in_used as for zada_inflate: the CRC
+ * is the Zip CRC-32 register over the bytes written; in_used counts up to the byte with the last bit of the footer's CRC.  Only the first
+ * stream of a concatenation is decoded; trailing bytes are not an error.
+ * A stream is valid when libbz2's BZ2_bzDecompress accepts it.  ZADA_E_DATA otherwise, by the rules of enum BzdRule (csrc/zada_bunzip2_logic.h):
+ * BZD_R_STREAM_MAGIC (no BZh1 .. BZh9), BZD_R_BLOCK_MAGIC (neither block nor footer magic where a block has to begin), BZD_R_RANDOMISED (the
+ * randomised flag is set: de-randomising is not built), BZD_R_ORIGIN (origin not below the block's symbol count; a block with no symbols is
+ * invalid), BZD_R_NO_BYTE_IN_USE, BZD_R_CODER_COUNT (not 2 .. 6), BZD_R_SELECTOR_COUNT (0), BZD_R_SELECTOR_INDEX, BZD_R_CODE_LENGTH (not 1 .. 20),
+ * BZD_R_SELECTORS_EXHAUSTED, BZD_R_CODE_TOO_LONG, BZD_R_CODE_VECTOR, BZD_R_PERM_INDEX (the three range checks of Get_MTF_Value),
+ * BZD_R_RUN_TOO_LONG, BZD_R_BLOCK_OVERFLOW (more symbols than 100 000 x level), BZD_R_BLOCK_CRC, BZD_R_STREAM_CRC, BZD_R_TRUNCATED (input
+ * exhausted anywhere before the last bit of the footer's CRC, n_in = 0 included), BZD_R_OUTPUT_FULL (output beyond cap).  zada_last_error names
+ * the rule, the block number and the bit; nothing is delivered for such an entry (*out_len = *in_used = 0, the CRC register stays).  Nothing is
+ * read beyond n_in, nothing written beyond cap or beyond a block's slot.  Argument checks come before anything touches the device; a stream or
+ * a cap of 1 TiB or more is ZADA_E_TOO_LARGE. */
+int zada_bunzip2(zada_ctx *ctx, const uint8_t *in, uint64_t n_in, uint8_t *out, uint64_t cap,
+                 uint64_t *out_len, uint64_t *in_used, uint32_t *crc_inout);
+/* the same with the stream and the output in device memory, at any alignment */
+int zada_bunzip2_device(zada_ctx *ctx, const void *d_in, uint64_t n_in, void *d_out, uint64_t cap,
+                        uint64_t *out_len, uint64_t *in_used, uint32_t *crc_inout);
+/* `count` independent streams (one per Zip entry).  The entries are staged in groups bounded by the knob "bunzip_batch_mib" (default 8192):
+ * half of it for a group's streams and outputs, the rest for the work arrays of a round of blocks -- the slots of the last columns (a slot holds
+ * min (100 000 x level, cap + cap / 4) symbols), the tt arrays and the bytes behind the inverse BWT, 6.8 bytes of HBM per symbol; a group
+ * with more candidate blocks than that takes several rounds.  rc [i] is ZADA_OK or ZADA_E_DATA per entry, crc [i] in/out; the call returns the
+ * worst rc.  `out` may be NULL: the decoded bytes then stay on the device (UnZip's test_only). */
+int zada_bunzip2_batch(zada_ctx *ctx, int count, const uint8_t *const *in, const uint64_t *n_in,
+                       uint8_t *const *out, const uint64_t *cap, uint64_t *out_len, uint64_t *in_used, uint32_t *crc, int *rc);
+/* What the last zada_bunzip2* call on the context found, as 64-bit values.  what = 0: four per entry -- the BzdRule broken (0: none), the block
+ * it was broken in (from 1; 0: before the first), the bit, 0.  what = 1: five per block of the entries' chains, in order -- entry, symbols,
+ * origin, stored CRC, end bit.  Up to cap_items values are copied; returns how many there are. */
+uint64_t zada_bunzip2_last_records(zada_ctx *ctx, int what, uint64_t *dst, uint64_t cap_items);
 
 /* ---- One stream over several contexts (GPUs) -------------------------------------------------------------------
  * The reference compresses an entry as ONE sequential stream (a 32 KiB window, a lazy-match state machine, a flush of the

@@ -78,7 +78,7 @@ def preselect(method, content_hint=ContentType.neutral, input_size=None):
 
 
 E_REFERENCE = -6     # zada.h ZADA_E_REFERENCE: LZMA_3, the reference's own matcher reports a match that is none on this entry
-E_DATA = -7          # zada.h ZADA_E_DATA: zada_inflate*, the compressed data is not a valid stream
+E_DATA = -7          # zada.h ZADA_E_DATA: zada_inflate* / zada_bunzip2*, the compressed data is not a valid stream
 
 
 class ZadaError(RuntimeError):
@@ -200,6 +200,12 @@ def load_library():
         L.zada_inflate_device.argtypes = [vp, i32, vp, u64, vp, u64, u64p, u64p, u32p]
         L.zada_inflate_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.zada_crypt_decode_batch.argtypes = [vp, i32, vp, vp, vp]
+    if hasattr(L, "zada_bunzip2"):                   # (likewise: the BZip2 reader)
+        L.zada_bunzip2.argtypes = [vp, vp, u64, vp, u64, u64p, u64p, u32p]
+        L.zada_bunzip2_device.argtypes = [vp, vp, u64, vp, u64, u64p, u64p, u32p]
+        L.zada_bunzip2_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.zada_bunzip2_last_records.restype = u64
+        L.zada_bunzip2_last_records.argtypes = [vp, i32, vp, u64]
     L.zada_bz2_last_blocks.restype = ctypes.c_uint64
     L.zada_bz2_last_blocks.argtypes = [vp, vp, u64]
     L.zada_crc32_combine.restype = ctypes.c_uint32
@@ -262,7 +268,7 @@ class Encoder:
             pass
 
     def set_knob(self, name, value):
-        """Tuning / test knobs ("budget", "max_demand_rounds", "inner_budget", "shard_kib", "span_mib", "batch_mib"); none changes a byte of output.
+        """Tuning / test knobs ("budget", "max_demand_rounds", "inner_budget", "shard_kib", "span_mib", "batch_mib", "bunzip_batch_mib"); none changes a byte of output.
         "lzma_dict" is the reference's dictionary_size parameter for LZMA_3 (0 = the entry's size, what Zip.Compress.LZMA_E passes)."""
         if self.lib.zada_set_knob(self.ctx, name.encode(), int(value)) != 0:
             raise ZadaError("unknown knob %r" % name)
@@ -697,6 +703,75 @@ class Encoder:
             self._err(rc, "zada_inflate_device")
         return ol.value, iu.value, c.value
 
+    # ---- the reader: BZip2.Decoding.Decompress (bzip2-decoding.adb; include/zada.h "BZip2.Decoding") ----
+    def bunzip2(self, payload, size=None, crc=0xFFFFFFFF):
+        """One BZip2 stream (Zip format 12), its blocks in parallel.  size: the uncompressed size the directory promises (a stream that writes more
+        is a DataError); None = unknown: the output buffer starts at eight times the payload and doubles while the only complaint is "output beyond
+        cap".  Returns (bytes, input bytes used, running CRC register).  Raises DataError."""
+        n = len(payload)
+        cap = max(8 * n, 4096) if size is None else int(size)
+        while True:
+            out = ctypes.create_string_buffer(max(cap, 1))
+            ol, iu, c = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(crc)
+            rc = self.lib.zada_bunzip2(self.ctx, _addr(payload) if n else None, n, ctypes.addressof(out), cap, ctypes.byref(ol), ctypes.byref(iu), ctypes.byref(c))
+            if rc == 0:
+                return out.raw[:ol.value], iu.value, c.value
+            if rc == E_DATA and size is None and b"output beyond cap" in self.lib.zada_last_error(self.ctx):
+                cap *= 2
+                continue
+            self._err(rc, "zada_bunzip2")
+
+    def bunzip2_batch(self, payloads, sizes, crc=0xFFFFFFFF, deliver=True):
+        """Independent BZip2 streams (one per Zip entry): the blocks of all of them through the same launches, in groups bounded by
+        "bunzip_batch_mib".  sizes [i] = cap of entry i.  Returns a list of (rc, bytes or None, bytes written, input bytes used, running CRC
+        register); rc is 0 or E_DATA.  deliver = False: the bytes stay on the device (sizes and CRCs only -- UnZip's test_only)."""
+        import numpy as np
+        cnt = len(payloads)
+        if cnt == 0:
+            return []
+        lens = np.fromiter((len(d) for d in payloads), dtype=np.uint64, count=cnt)
+        caps = np.ascontiguousarray(np.array(sizes, dtype=np.uint64))
+        if len(caps) != cnt:
+            raise ZadaError("bunzip2_batch: one size per payload")
+        keep = [d if len(d) else b"\0" for d in payloads]
+        ins = np.fromiter((_addr(d) for d in keep), dtype=np.uint64, count=cnt)
+        offs = np.concatenate(([0], np.cumsum(caps)[:-1])).astype(np.uint64)
+        total = sum(int(x) for x in caps)                  # (Python integers: the sizes may come from a directory that lies)
+        try:
+            if total >= 1 << 40:
+                raise MemoryError
+            arena = np.empty(total + 1 if deliver else 1, dtype=np.uint8)
+        except (MemoryError, ValueError):
+            raise ZadaError("bunzip2_batch: %d bytes of output are promised -- more than this machine holds" % total)
+        outp = (arena.ctypes.data + offs).astype(np.uint64)
+        ols, ius = np.zeros(cnt, dtype=np.uint64), np.zeros(cnt, dtype=np.uint64)
+        crcs = np.full(cnt, crc, dtype=np.uint32)
+        rcs = np.zeros(cnt, dtype=np.int32)
+        worst = self.lib.zada_bunzip2_batch(self.ctx, cnt, ins.ctypes.data, lens.ctypes.data, outp.ctypes.data if deliver else None, caps.ctypes.data,
+                                            ols.ctypes.data, ius.ctypes.data, crcs.ctypes.data, rcs.ctypes.data)
+        if worst < 0 and worst != E_DATA:
+            self._err(worst, "zada_bunzip2_batch")
+        mv = memoryview(arena)
+        return [(int(rcs[i]), bytes(mv[int(offs[i]):int(offs[i]) + int(ols[i])]) if deliver and rcs[i] == 0 else None, int(ols[i]), int(ius[i]), int(crcs[i]))
+                for i in range(cnt)]
+
+    def bunzip2_last_records(self, blocks=False):
+        """The last bunzip2* call: per entry (rule, block, bit, 0) -- or, blocks = True, per block of the chains (entry, symbols, origin, stored CRC,
+        end bit) -- as a numpy array of 64-bit values."""
+        import numpy as np
+        n = self.lib.zada_bunzip2_last_records(self.ctx, int(blocks), None, 0)
+        a = np.zeros(max(int(n), 1), dtype=np.uint64)
+        self.lib.zada_bunzip2_last_records(self.ctx, int(blocks), a.ctypes.data, int(n))
+        return a[:int(n)].reshape(-1, 5 if blocks else 4)
+
+    def bunzip2_device(self, d_in_ptr, n_in, d_out_ptr, cap, crc=0xFFFFFFFF):
+        """Device-resident variant (HBM addresses of any alignment).  Returns (bytes written, input bytes used, running CRC register); raises DataError."""
+        ol, iu, c = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(crc)
+        rc = self.lib.zada_bunzip2_device(self.ctx, d_in_ptr, n_in, d_out_ptr, cap, ctypes.byref(ol), ctypes.byref(iu), ctypes.byref(c))
+        if rc != 0:
+            self._err(rc, "zada_bunzip2_device")
+        return ol.value, iu.value, c.value
+
     def lz77_tokens(self, data, method=Method.Deflate_3):
         import numpy as np
         n = len(data)
@@ -1033,12 +1108,15 @@ class ZipInfo:
 class UnZip:
     """UnZip.Extract (unzip.ads:55-290) on an archive in memory: Store (0), Deflate (8) and Deflate64 (9) entries; all Deflate entries of a call go
     through ONE inflate_batch (one wave per entry), encrypted ones first through one crypt_decode_batch; size and CRC-32 -- computed on the device --
-    are compared with the directory.  BZip2, LZMA and the older formats are not decoded: UnsupportedMethod."""
+    are compared with the directory.  BZip2, LZMA and the older formats are not decoded: UnsupportedMethod.
+    UnZip (encoder, bzip2=True) also decodes BZip2 (12) entries: all of a call through ONE bunzip2_batch (their blocks in parallel), with the same
+    checks and errors; the default leaves them UnsupportedMethod.  LZMA entries are UnsupportedMethod either way."""
 
     _NAMES = {1: "Shrink", 2: "Reduce_1", 3: "Reduce_2", 4: "Reduce_3", 5: "Reduce_4", 6: "Implode", 12: "BZip2", 14: "LZMA", 98: "PPMd", 99: "AES"}
 
-    def __init__(self, encoder):
+    def __init__(self, encoder, bzip2=False):
         self.enc = encoder
+        self.bzip2 = bool(bzip2)
 
     def extract(self, info, what=None, password=None, test_only=False, errors="raise"):
         """info: ZipInfo; what: None = every entry, or names.  Returns {name: bytes}.  An entry that fails is a WrongPassword, DataError, SizeError,
@@ -1050,7 +1128,11 @@ class UnZip:
         res, payload = {}, {}
         enc_idx = []
         for k, e in enumerate(ents):
-            if e.method not in (0, 8, 9):
+            if e.method not in (0, 8, 9) and not (self.bzip2 and e.method == 12):
+                if self.bzip2:
+                    res[k] = UnsupportedMethod("entry %r: method %d (%s) is not decoded by this reader: Store, Deflate, Deflate64 and BZip2 only -- LZMA decoding is out of scope"
+                                               % (e.name, e.method, self._NAMES.get(e.method, "unknown")))
+                    continue
                 res[k] = UnsupportedMethod("entry %r: method %d (%s) is not decoded by this reader: Store, Deflate and Deflate64 only -- BZip2 and LZMA decoding are out of scope"
                                            % (e.name, e.method, self._NAMES.get(e.method, "unknown")))
                 continue
@@ -1078,6 +1160,19 @@ class UnZip:
                 e = ents[k]
                 if rc != 0:
                     res[k] = DataError("entry %r: not a valid %s stream, or longer than the %d bytes promised" % (e.name, "Deflate64" if e.method == 9 else "Deflate", e.usize))
+                elif ol != e.usize:
+                    res[k] = SizeError("entry %r: %d bytes decoded, %d promised" % (e.name, ol, e.usize))
+                elif reg ^ 0xFFFFFFFF != e.crc:
+                    res[k] = CRCError("entry %r: CRC-32 %08x, the directory says %08x" % (e.name, reg ^ 0xFFFFFFFF, e.crc))
+                else:
+                    res[k] = None if test_only else out
+        todo = [k for k in range(len(ents)) if k not in res and ents[k].method == 12]
+        if todo:
+            got = self.enc.bunzip2_batch([payload[k] for k in todo], [ents[k].usize for k in todo], deliver=not test_only)
+            for k, (rc, out, ol, _, reg) in zip(todo, got):
+                e = ents[k]
+                if rc != 0:
+                    res[k] = DataError("entry %r: not a valid BZip2 stream, or longer than the %d bytes promised" % (e.name, e.usize))
                 elif ol != e.usize:
                     res[k] = SizeError("entry %r: %d bytes decoded, %d promised" % (e.name, ol, e.usize))
                 elif reg ^ 0xFFFFFFFF != e.crc:

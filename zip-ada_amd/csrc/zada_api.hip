@@ -1023,6 +1023,7 @@ static void ctx_release(zada_ctx *z) {
   bz2_destroy(&z->c);
   crypt_destroy(&z->c);
   inflate_destroy(&z->c);
+  bunzip2_destroy(&z->c);
   lzma_free(&z->c);
   free_workspace(&z->c);
   for (hipEvent_t e : z->c.ev_pool) hipEventDestroy(e);
@@ -1076,6 +1077,7 @@ int zada_set_knob(zada_ctx *z, const char *name, int value) {
   else if (!strcmp(name, "inner_budget")) z->c.knob_inner_budget = value;
   else if (!strcmp(name, "link_run")) { if (value < 0 || value > 64 || (value & (value - 1))) return ZADA_E_INVALID; z->c.knob_link_run = value; }
   else if (!strcmp(name, "span_mib")) { if (value < 1 || value > 3968) return ZADA_E_INVALID; z->c.knob_span_mib = value; }
+  else if (!strcmp(name, "bunzip_batch_mib")) { if (value < 16 || value > 262144) return ZADA_E_INVALID; z->c.knob_bunzip_batch_mib = value; }
   else if (!strcmp(name, "bz_batch_mib")) { if (value < 1 || value > 2048) return ZADA_E_INVALID; z->c.knob_bz_batch_mib = value; }
   else if (!strcmp(name, "bz_span_mib")) { if (value < 24 || value > 3072) return ZADA_E_INVALID; z->c.knob_bz_span_mib = value; }
   else if (!strcmp(name, "bz_batch_melems")) { if (value < 1 || value > 1536) return ZADA_E_INVALID; z->c.knob_bz_batch_melems = value; }

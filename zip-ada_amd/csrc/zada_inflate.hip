@@ -398,6 +398,33 @@ static int inf_run(Ctx *c, InfState *S, const std::vector<InfJob> &jobs, const u
   return 0;
 }
 
+// The Zip CRC-32 of E outputs in device memory through k_inf_crc, for the BZip2 reader (zada_bunzip2.hip): regs [i] is the register before
+// entry i's out_len [i] bytes at out [i] on entry, the one behind them on return.
+int inflate_crc_entries(Ctx *c, uint32_t E, const uint64_t *out, const uint64_t *out_len, uint32_t *regs) {
+  if (E == 0) return 0;
+  InfState *S = inf_state(c);
+  if (!S) { c->err = "inflate: no memory for the tables"; return ZADA_E_NOMEM; }
+  std::vector<InfJob> jobs(E);
+  std::vector<InfResult> res(E);
+  for (uint32_t i = 0; i < E; i++) {
+    jobs[i] = InfJob{0, out[i], 0, out_len[i], 8, 0};
+    res[i] = InfResult{0, 0, out_len[i], 0, 0, 0, 0};
+  }
+  const uint64_t o_jobs = 0, o_crc = o_jobs + (uint64_t)E * sizeof(InfJob), o_res = (o_crc + (uint64_t)E * 4 + 15) & ~15ull, total = o_res + (uint64_t)E * sizeof(InfResult);
+  int rc = inf_grow(c, &S->tabs, &S->cap_tabs, total, "hipMalloc (inflate tables)");
+  if (rc) return rc;
+  hipStream_t st = c->stream;
+  hipMemcpyAsync(S->tabs + o_jobs, jobs.data(), (size_t)E * sizeof(InfJob), hipMemcpyHostToDevice, st);
+  hipMemcpyAsync(S->tabs + o_crc, regs, (size_t)E * 4, hipMemcpyHostToDevice, st);
+  hipMemcpyAsync(S->tabs + o_res, res.data(), (size_t)E * sizeof(InfResult), hipMemcpyHostToDevice, st);
+  hipLaunchKernelGGL(k_inf_crc, dim3(E), dim3(INF_WAVE), 0, st, (const InfJob *)(S->tabs + o_jobs), (InfResult *)(S->tabs + o_res), (const uint32_t *)(S->tabs + o_crc),
+                     (const InfCrcOps *)S->d_ops, E);
+  hipMemcpyAsync(res.data(), S->tabs + o_res, (size_t)E * sizeof(InfResult), hipMemcpyDeviceToHost, st);
+  if (hip_check(c, hipGetLastError(), "crc launch") || hip_check(c, hipStreamSynchronize(st), "crc")) return ZADA_E_HIP_;
+  for (uint32_t i = 0; i < E; i++) regs[i] = res[i].crc;
+  return 0;
+}
+
 static void inf_describe(Ctx *c, const InfResult &R, int entry) {
   char buf[200];
   snprintf(buf, sizeof buf, "inflate: entry %d: %s at bit %llu", entry, inf_rule_name(R.rule), (unsigned long long)R.bitpos);

@@ -263,6 +263,7 @@ struct Ctx {
   void *bz = nullptr;                                // BZip2 state (zada_bz2.hip), made on first use
   void *zc = nullptr;                                // ZipCrypto state (zada_crypt.hip), made on first use
   void *inf = nullptr;                               // Inflate state (zada_inflate.hip), made on first use
+  void *bzd = nullptr;                               // BZip2 reader state (zada_bunzip2.hip), made on first use
   void *lz_tab = nullptr; size_t cap_lz_tab = 0;     // LZMA (zada_lzma.hip): job table + results
   void *lz_save = nullptr; size_t cap_lz_save = 0;   // ... the coder's state between the launches of one stream
   void *lz_lit = nullptr; size_t cap_lz_lit = 0;     // ... the HBM literal tables of the methods with lc + lp >= 4, one per entry of a launch group
@@ -304,6 +305,7 @@ struct Ctx {
   int knob_inner_budget = 0;        // ZADA_INNER_BUDGET: rounds for positions deep inside a match (0 = as every other position; A/B: 1 round saves 4.7 ms in k_match and costs 8.9 ms of demand searches, 2 rounds: -3.2 / +3.7)
   int knob_span_mib = 2048;         // MiB of a stream one pass takes (longer streams: spans one after the other, deflate_spans)
   int knob_batch_mib = 512;         // MiB of LZ buffer one batch of small entries may take (zada_deflate_batch)
+  int knob_bunzip_batch_mib = 8192; // BZip2 reader: MiB of HBM one group of entries may take -- streams and outputs (half of it), slots, tt arrays, bytes behind the inverse BWT
   int knob_bz_batch_mib = 256;      // BZip2: MiB of small entries zada_bzip2_batch takes through one launch sequence
   int knob_bz_span_mib = 1024;      // BZip2: MiB of the stream whose block limits are found at a time
   int knob_bz_text_order = 1;       // BZip2: the group lists of the late sort rounds in text order (one library radix sort per build)
@@ -332,6 +334,8 @@ void bz2_destroy(Ctx *c);
 // ZipCrypto (zada_crypt.hip): CRC_Crypto.Encode over device memory, keys in and out
 void crypt_destroy(Ctx *c);
 void inflate_destroy(Ctx *c);                       // Inflate (zada_inflate.hip)
+int inflate_crc_entries(Ctx *c, uint32_t E, const uint64_t *out, const uint64_t *out_len, uint32_t *regs);   // ... its k_inf_crc over outputs in device memory
+void bunzip2_destroy(Ctx *c);                       // the BZip2 reader (zada_bunzip2.hip)
 void crypt_update_keys(uint32_t keys[3], uint8_t by);
 uint8_t crypt_code(const uint32_t keys[3]);
 constexpr uint64_t CRYPT_WAVE_MAX = 256u << 10;     // a batch's entries of up to this many bytes: one wave each, in one launch
