@@ -95,7 +95,7 @@ enum {
                              * bytes that no window fill took up, :1000-1017, 1397-1406: lzPos lags behind readPos) and the reference's own stream does not
                              * decode to the input.  Cannot happen with the dictionary Zip.Compress.LZMA_E asks for unless the entry is beyond 256 MiB and its
                              * last window fill brings 163 .. 4 368 bytes; the shim Stores such an entry or takes another method.  Nothing was written. */
-  ZADA_E_DATA = -7          /* zada_inflate* and zada_bunzip2* only: the compressed data is not a valid stream (Zip.Archive_corrupted); zada_last_error names the rule and the bit */
+  ZADA_E_DATA = -7          /* zada_inflate*, zada_bunzip2* and zada_unlzma* only: the compressed data is not a valid stream (Zip.Archive_corrupted); zada_last_error names the rule and the bit (zada_unlzma*: the input byte) */
 };
 
 typedef struct zada_ctx zada_ctx;
@@ -275,6 +275,44 @@ int zada_bunzip2_batch(zada_ctx *ctx, int count, const uint8_t *const *in, const
  * it was broken in (from 1; 0: before the first), the bit, 0.  what = 1: five per block of the entries' chains, in order -- entry, symbols,
  * origin, stored CRC, end bit.  Up to cap_items values are copied; returns how many there are. */
 uint64_t zada_bunzip2_last_records(zada_ctx *ctx, int what, uint64_t *dst, uint64_t cap_items);
+
+/* ---- The reader: LZMA.Decoding.Decode (lzma-decoding.adb, as UnZip.Decompress.LZMA_Decode calls it; Zip format 14) ------
+ * One LZMA payload back into bytes: 2 bytes of SDK version (ignored), 2 bytes of properties size (5), the properties (lc / lp / pb in one byte
+ * below 225, the dictionary size as a little-endian u32), the range-coded stream.  Like a Deflate stream, an LZMA stream is a chain -- every bit
+ * is decoded from the probability the bits before it left --, so ENTRIES are what runs in parallel: one wave per entry (csrc/zada_unlzma.hip,
+ * DESIGN.md 15), use zada_unlzma_batch for many of them: 10 000 entries of 16 KiB take 60 ms on the device (2.7 GB/s; 16 liblzma threads: 0.9), where ONE
+ * STREAM ALONE RUNS AT ONE WAVE'S PACE, 2.5 MB/s against 116 MB/s of one liblzma thread (profiles/unlzma/NOTES.md).  The probability model is in LDS; a literal
+ * table of lc + lp >= 4 (24 KiB .. 6 MiB) is in HBM, one per entry, in launch groups bounded by the knob "lzma_lit_mib".
+ *   eos       : bit 1 of the entry's general-purpose flags: the stream ends on the marker (the reference's marker_expected).
+ *   cap       : the uncompressed size the directory promises (the reference's given_size).
+ *   crc_inout, out_len as for zada_inflate; in_used counts the bytes through the last one the range decoder's normalisation consumed;
+ *   trailing bytes are not an error.
+ * A stream is valid when LZMA.Decoding.Decode accepts it with (has_size => False, given_size => cap, marker_expected => eos,
+ * fail_on_bad_range_code => True).  ZADA_E_DATA otherwise, by the rules of enum UlzRule (csrc/zada_unlzma_logic.h): ULZ_R_PROPERTIES (properties
+ * size not 5, properties byte >= 225), ULZ_R_OUTPUT_FULL (a literal, a match or a rep match with cap bytes written, or a match that runs past
+ * cap), ULZ_R_DISTANCE (not distance - 1 < min (dictionary size, bytes written); a dictionary size below 4096 counts as 4096),
+ * ULZ_R_EMPTY_WINDOW (a rep match with no byte written), ULZ_R_MARKER (the marker -- distance 0xFFFFFFFF of a simple match -- with a range
+ * decoder that is not finished), ULZ_R_RANGE_CORRUPTED (first range-coder byte not 0, code = range after the initial load or inside the direct
+ * bits: refused at the end), ULZ_R_INPUT_END (the stream needs a byte beyond n_in, n_in = 0 included).  The ends: the marker, with eos = 0 as well
+ * (the caller's size check then judges the length: out_len may be below cap); or, with eos = 0 only, cap bytes written and code = 0.  With
+ * eos = 1 only the marker ends a stream.  zada_last_error names the rule and the input byte; nothing is delivered for such an entry (*out_len =
+ * *in_used = 0, the CRC register stays).  Nothing is read beyond n_in, nothing written beyond cap.  Argument checks come before anything touches
+ * the device; a stream or a cap of 1 TiB or more is ZADA_E_TOO_LARGE. */
+int zada_unlzma(zada_ctx *ctx, const uint8_t *in, uint64_t n_in, uint8_t *out, uint64_t cap, int eos,
+                uint64_t *out_len, uint64_t *in_used, uint32_t *crc_inout);
+/* the same with the payload and the output in device memory, at any alignment */
+int zada_unlzma_device(zada_ctx *ctx, const void *d_in, uint64_t n_in, void *d_out, uint64_t cap, int eos,
+                       uint64_t *out_len, uint64_t *in_used, uint32_t *crc_inout);
+/* `count` independent payloads (one per Zip entry), eos [i] per entry.  The entries are staged in groups of up to "batch_mib" MiB of streams and
+ * outputs; the waves take a group's entries longest first, those with a literal table in HBM in launches of their own, bounded by
+ * "lzma_lit_mib".  rc [i] is ZADA_OK or ZADA_E_DATA per entry, crc [i] in/out; the call returns the worst rc.  `out` may be NULL: the decoded
+ * bytes then stay on the device (UnZip's test_only). */
+int zada_unlzma_batch(zada_ctx *ctx, int count, const uint8_t *const *in, const uint64_t *n_in,
+                      uint8_t *const *out, const uint64_t *cap, const int *eos, uint64_t *out_len, uint64_t *in_used, uint32_t *crc, int *rc);
+/* What the last zada_unlzma* call on the context found, as 64-bit values, four per entry: the UlzRule broken (0: none), the input byte and the
+ * output position where the decoder stood, how the stream ended (1: on a marker, 2: without, 0: it did not).  Up to cap_items values are
+ * copied; returns how many there are. */
+uint64_t zada_unlzma_last_records(zada_ctx *ctx, uint64_t *dst, uint64_t cap_items);
 
 /* ---- One stream over several contexts (GPUs) -------------------------------------------------------------------
  * The reference compresses an entry as ONE sequential stream (a 32 KiB window, a lazy-match state machine, a flush of the

@@ -78,7 +78,7 @@ def preselect(method, content_hint=ContentType.neutral, input_size=None):
 
 
 E_REFERENCE = -6     # zada.h ZADA_E_REFERENCE: LZMA_3, the reference's own matcher reports a match that is none on this entry
-E_DATA = -7          # zada.h ZADA_E_DATA: zada_inflate* / zada_bunzip2*, the compressed data is not a valid stream
+E_DATA = -7          # zada.h ZADA_E_DATA: zada_inflate* / zada_bunzip2* / zada_unlzma*, the compressed data is not a valid stream
 
 
 class ZadaError(RuntimeError):
@@ -206,6 +206,12 @@ def load_library():
         L.zada_bunzip2_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
         L.zada_bunzip2_last_records.restype = u64
         L.zada_bunzip2_last_records.argtypes = [vp, i32, vp, u64]
+    if hasattr(L, "zada_unlzma"):                    # (likewise: the LZMA reader)
+        L.zada_unlzma.argtypes = [vp, vp, u64, vp, u64, i32, u64p, u64p, u32p]
+        L.zada_unlzma_device.argtypes = [vp, vp, u64, vp, u64, i32, u64p, u64p, u32p]
+        L.zada_unlzma_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.zada_unlzma_last_records.restype = u64
+        L.zada_unlzma_last_records.argtypes = [vp, vp, u64]
     L.zada_bz2_last_blocks.restype = ctypes.c_uint64
     L.zada_bz2_last_blocks.argtypes = [vp, vp, u64]
     L.zada_crc32_combine.restype = ctypes.c_uint32
@@ -772,6 +778,82 @@ class Encoder:
             self._err(rc, "zada_bunzip2_device")
         return ol.value, iu.value, c.value
 
+    # ---- the reader: LZMA.Decoding.Decode (lzma-decoding.adb; include/zada.h "LZMA.Decoding") ----
+    def unlzma(self, payload, cap=None, eos=True, crc=0xFFFFFFFF):
+        """One LZMA payload (Zip format 14: version, properties size, properties, range-coded stream).  cap: the uncompressed size the directory
+        promises (a stream that writes more is a DataError; one without marker, eos = False, ends there); None = unknown (eos = True only): the
+        output buffer starts at eight times the payload and doubles while the only complaint is "output beyond cap".  eos: bit 1 of the entry's
+        general-purpose flags -- the stream ends on a marker.  Returns (bytes, input bytes used, running CRC register).  Raises DataError."""
+        n = len(payload)
+        if cap is None and not eos:
+            raise ZadaError("unlzma: a stream without marker needs its size")
+        size, cap = cap, (max(8 * n, 4096) if cap is None else int(cap))
+        while True:
+            out = ctypes.create_string_buffer(max(cap, 1))
+            ol, iu, c = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(crc)
+            rc = self.lib.zada_unlzma(self.ctx, _addr(payload) if n else None, n, ctypes.addressof(out), cap, int(bool(eos)), ctypes.byref(ol), ctypes.byref(iu),
+                                      ctypes.byref(c))
+            if rc == 0:
+                return out.raw[:ol.value], iu.value, c.value
+            if rc == E_DATA and size is None and b"output beyond cap" in self.lib.zada_last_error(self.ctx):
+                cap *= 2
+                continue
+            self._err(rc, "zada_unlzma")
+
+    def unlzma_batch(self, payloads, caps, eos=True, crc=0xFFFFFFFF, deliver=True):
+        """Independent LZMA payloads (one per Zip entry), one wave per entry, in groups bounded by "batch_mib" (and, for literal tables in HBM,
+        "lzma_lit_mib").  caps [i] = cap of entry i; eos: one flag for all, or one per entry.  Returns a list of (rc, bytes or None, bytes written,
+        input bytes used, running CRC register); rc is 0 or E_DATA.  deliver = False: the bytes stay on the device (UnZip's test_only)."""
+        import numpy as np
+        cnt = len(payloads)
+        if cnt == 0:
+            return []
+        lens = np.fromiter((len(d) for d in payloads), dtype=np.uint64, count=cnt)
+        caps = np.ascontiguousarray(np.array(caps, dtype=np.uint64))
+        if len(caps) != cnt:
+            raise ZadaError("unlzma_batch: one cap per payload")
+        flags = np.full(cnt, int(bool(eos)), dtype=np.int32) if isinstance(eos, (bool, int)) else np.ascontiguousarray(np.array([int(bool(x)) for x in eos], dtype=np.int32))
+        if len(flags) != cnt:
+            raise ZadaError("unlzma_batch: one eos flag per payload")
+        keep = [d if len(d) else b"\0" for d in payloads]
+        ins = np.fromiter((_addr(d) for d in keep), dtype=np.uint64, count=cnt)
+        offs = np.concatenate(([0], np.cumsum(caps)[:-1])).astype(np.uint64)
+        total = sum(int(x) for x in caps)                  # (Python integers: the sizes may come from a directory that lies)
+        try:
+            if total >= 1 << 40:
+                raise MemoryError
+            arena = np.empty(total + 1 if deliver else 1, dtype=np.uint8)
+        except (MemoryError, ValueError):
+            raise ZadaError("unlzma_batch: %d bytes of output are promised -- more than this machine holds" % total)
+        outp = (arena.ctypes.data + offs).astype(np.uint64)
+        ols, ius = np.zeros(cnt, dtype=np.uint64), np.zeros(cnt, dtype=np.uint64)
+        crcs = np.full(cnt, crc, dtype=np.uint32)
+        rcs = np.zeros(cnt, dtype=np.int32)
+        worst = self.lib.zada_unlzma_batch(self.ctx, cnt, ins.ctypes.data, lens.ctypes.data, outp.ctypes.data if deliver else None, caps.ctypes.data,
+                                           flags.ctypes.data, ols.ctypes.data, ius.ctypes.data, crcs.ctypes.data, rcs.ctypes.data)
+        if worst < 0 and worst != E_DATA:
+            self._err(worst, "zada_unlzma_batch")
+        mv = memoryview(arena)
+        return [(int(rcs[i]), bytes(mv[int(offs[i]):int(offs[i]) + int(ols[i])]) if deliver and rcs[i] == 0 else None, int(ols[i]), int(ius[i]), int(crcs[i]))
+                for i in range(cnt)]
+
+    def unlzma_last_records(self):
+        """The last unlzma* call: per entry (rule broken or 0, input byte, output position, how the stream ended -- 1: on a marker, 2: without, 0: it did
+        not) as a numpy array of 64-bit values."""
+        import numpy as np
+        n = self.lib.zada_unlzma_last_records(self.ctx, None, 0)
+        a = np.zeros(max(int(n), 1), dtype=np.uint64)
+        self.lib.zada_unlzma_last_records(self.ctx, a.ctypes.data, int(n))
+        return a[:int(n)].reshape(-1, 4)
+
+    def unlzma_device(self, d_in_ptr, n_in, d_out_ptr, cap, eos=True, crc=0xFFFFFFFF):
+        """Device-resident variant (HBM addresses of any alignment).  Returns (bytes written, input bytes used, running CRC register); raises DataError."""
+        ol, iu, c = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(crc)
+        rc = self.lib.zada_unlzma_device(self.ctx, d_in_ptr, n_in, d_out_ptr, cap, int(bool(eos)), ctypes.byref(ol), ctypes.byref(iu), ctypes.byref(c))
+        if rc != 0:
+            self._err(rc, "zada_unlzma_device")
+        return ol.value, iu.value, c.value
+
     def lz77_tokens(self, data, method=Method.Deflate_3):
         import numpy as np
         n = len(data)
@@ -1110,13 +1192,16 @@ class UnZip:
     through ONE inflate_batch (one wave per entry), encrypted ones first through one crypt_decode_batch; size and CRC-32 -- computed on the device --
     are compared with the directory.  BZip2, LZMA and the older formats are not decoded: UnsupportedMethod.
     UnZip (encoder, bzip2=True) also decodes BZip2 (12) entries: all of a call through ONE bunzip2_batch (their blocks in parallel), with the same
-    checks and errors; the default leaves them UnsupportedMethod.  LZMA entries are UnsupportedMethod either way."""
+    checks and errors; the default leaves them UnsupportedMethod.  UnZip (encoder, lzma=True) likewise decodes LZMA (14) entries: all of a call
+    through ONE unlzma_batch (one wave per entry), eos = bit 1 of the entry's flags, cap = its uncompressed size; an entry whose stream ended on a
+    marker with fewer bytes than promised is a SizeError.  Without lzma=True, LZMA entries are UnsupportedMethod."""
 
     _NAMES = {1: "Shrink", 2: "Reduce_1", 3: "Reduce_2", 4: "Reduce_3", 5: "Reduce_4", 6: "Implode", 12: "BZip2", 14: "LZMA", 98: "PPMd", 99: "AES"}
 
-    def __init__(self, encoder, bzip2=False):
+    def __init__(self, encoder, bzip2=False, lzma=False):
         self.enc = encoder
         self.bzip2 = bool(bzip2)
+        self.lzma = bool(lzma)
 
     def extract(self, info, what=None, password=None, test_only=False, errors="raise"):
         """info: ZipInfo; what: None = every entry, or names.  Returns {name: bytes}.  An entry that fails is a WrongPassword, DataError, SizeError,
@@ -1128,7 +1213,12 @@ class UnZip:
         res, payload = {}, {}
         enc_idx = []
         for k, e in enumerate(ents):
-            if e.method not in (0, 8, 9) and not (self.bzip2 and e.method == 12):
+            if e.method not in (0, 8, 9) and not (self.bzip2 and e.method == 12) and not (self.lzma and e.method == 14):
+                if self.lzma:
+                    res[k] = UnsupportedMethod("entry %r: method %d (%s) is not decoded by this reader: Store, Deflate, Deflate64%s and LZMA only%s"
+                                               % (e.name, e.method, self._NAMES.get(e.method, "unknown"), ", BZip2" if self.bzip2 else "",
+                                                  "" if self.bzip2 else " -- BZip2 decoding is out of scope"))
+                    continue
                 if self.bzip2:
                     res[k] = UnsupportedMethod("entry %r: method %d (%s) is not decoded by this reader: Store, Deflate, Deflate64 and BZip2 only -- LZMA decoding is out of scope"
                                                % (e.name, e.method, self._NAMES.get(e.method, "unknown")))
@@ -1173,6 +1263,19 @@ class UnZip:
                 e = ents[k]
                 if rc != 0:
                     res[k] = DataError("entry %r: not a valid BZip2 stream, or longer than the %d bytes promised" % (e.name, e.usize))
+                elif ol != e.usize:
+                    res[k] = SizeError("entry %r: %d bytes decoded, %d promised" % (e.name, ol, e.usize))
+                elif reg ^ 0xFFFFFFFF != e.crc:
+                    res[k] = CRCError("entry %r: CRC-32 %08x, the directory says %08x" % (e.name, reg ^ 0xFFFFFFFF, e.crc))
+                else:
+                    res[k] = None if test_only else out
+        todo = [k for k in range(len(ents)) if k not in res and ents[k].method == 14]
+        if todo:
+            got = self.enc.unlzma_batch([payload[k] for k in todo], [ents[k].usize for k in todo], [bool(ents[k].flags & 2) for k in todo], deliver=not test_only)
+            for k, (rc, out, ol, _, reg) in zip(todo, got):
+                e = ents[k]
+                if rc != 0:
+                    res[k] = DataError("entry %r: not a valid LZMA stream, or longer than the %d bytes promised" % (e.name, e.usize))
                 elif ol != e.usize:
                     res[k] = SizeError("entry %r: %d bytes decoded, %d promised" % (e.name, ol, e.usize))
                 elif reg ^ 0xFFFFFFFF != e.crc:

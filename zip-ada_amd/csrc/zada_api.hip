@@ -1024,6 +1024,7 @@ static void ctx_release(zada_ctx *z) {
   crypt_destroy(&z->c);
   inflate_destroy(&z->c);
   bunzip2_destroy(&z->c);
+  unlzma_destroy(&z->c);
   lzma_free(&z->c);
   free_workspace(&z->c);
   for (hipEvent_t e : z->c.ev_pool) hipEventDestroy(e);

@@ -264,6 +264,7 @@ struct Ctx {
   void *zc = nullptr;                                // ZipCrypto state (zada_crypt.hip), made on first use
   void *inf = nullptr;                               // Inflate state (zada_inflate.hip), made on first use
   void *bzd = nullptr;                               // BZip2 reader state (zada_bunzip2.hip), made on first use
+  void *ulz = nullptr;                               // LZMA reader state (zada_unlzma.hip), made on first use
   void *lz_tab = nullptr; size_t cap_lz_tab = 0;     // LZMA (zada_lzma.hip): job table + results
   void *lz_save = nullptr; size_t cap_lz_save = 0;   // ... the coder's state between the launches of one stream
   void *lz_lit = nullptr; size_t cap_lz_lit = 0;     // ... the HBM literal tables of the methods with lc + lp >= 4, one per entry of a launch group
@@ -336,6 +337,7 @@ void crypt_destroy(Ctx *c);
 void inflate_destroy(Ctx *c);                       // Inflate (zada_inflate.hip)
 int inflate_crc_entries(Ctx *c, uint32_t E, const uint64_t *out, const uint64_t *out_len, uint32_t *regs);   // ... its k_inf_crc over outputs in device memory
 void bunzip2_destroy(Ctx *c);                       // the BZip2 reader (zada_bunzip2.hip)
+void unlzma_destroy(Ctx *c);                        // the LZMA reader (zada_unlzma.hip)
 void crypt_update_keys(uint32_t keys[3], uint8_t by);
 uint8_t crypt_code(const uint32_t keys[3]);
 constexpr uint64_t CRYPT_WAVE_MAX = 256u << 10;     // a batch's entries of up to this many bytes: one wave each, in one launch
