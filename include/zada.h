@@ -485,6 +485,22 @@ int zada_lzma_match_sets(zada_ctx *ctx, const uint8_t *in, uint64_t n, uint8_t *
 /* Test hooks: sub-blocks (Encode_Block jobs) of a host buffer through the stages, and the tables they leave. */
 int zada_bz2_run(zada_ctx *ctx, const uint8_t *in, uint64_t n, uint32_t nsb, const uint64_t *starts, const uint32_t *lens, int option, int stages);
 int zada_bz2_fetch(zada_ctx *ctx, const char *name, void *dst, uint64_t cap, uint64_t *nbytes);
+/* Test hooks: the three device-only building blocks on inputs of the caller's choice (zip-ada_amd/csrc/zada_testhooks.hip).  Host pointers;
+ * 0, ZADA_E_INVALID or ZADA_E_HIP (device memory that cannot be had included).
+ *   zada_test_llhc        count vectors of n <= 288 counts each through llhc_wave <max_bits> (Length_Limited_Coding on one wave), max_bits 7, 15, 16
+ *                         or 17, one wave per vector, waves_per_group (1 or 4) vectors per workgroup; bl receives count x n code lengths.  The
+ *                         counts are read from LDS for half of the vectors and from global memory for the other half, and the halves swap
+ *                         between waves_per_group 1 and 4.  ZADA_E_INVALID for a vector the reference refuses (more used symbols than
+ *                         2 ** max_bits) or the product never makes (counts adding up to 2 ** 27 or more).
+ *   zada_test_radix_sort  radix_sort_pairs: n pairs of a 32-bit key and a value of value_bytes (4 or 16), stable by the key bits [begin_bit,
+ *                         end_bit), with a temporary buffer of exactly the size the library asks for; in_place: outputs over the inputs on the
+ *                         device.  Out of place, ZADA_E_INVALID if the inputs were changed.
+ *   zada_test_scan        exclusive_scan_u32: out [i] = in [0] + ... + in [i - 1], *total = the sum of all n (1 .. 2 ** 30); in_place as above.
+ * Every device buffer has a guard behind it: ZADA_E_HIP if one was written. */
+int zada_test_llhc(zada_ctx *ctx, int max_bits, int n, uint32_t count, int waves_per_group, const uint32_t *freq, uint8_t *bl);
+int zada_test_radix_sort(zada_ctx *ctx, uint64_t n, int value_bytes, unsigned begin_bit, unsigned end_bit, int in_place, const uint32_t *keys, const void *vals,
+                         uint32_t *keys_out, void *vals_out);
+int zada_test_scan(zada_ctx *ctx, uint64_t n, int in_place, const uint32_t *in, uint32_t *out, uint32_t *total);
 
 #ifdef __cplusplus
 }

@@ -277,6 +277,80 @@ def _fixed_like(natoms, seed, pm=0.22):
     return bytes(out[start:]), bytes(out[:start])
 
 
+def _steep(k, slack=8):
+    """1, 1, 4, 5, 9, 13, 23, ...: every count is the sum of ALL the counts two and more places before it, plus three, plus an eighth of
+    that sum.  A Huffman code over k such counts is a single chain, k - 1 deep, and stays one while fewer than that margin is miscounted
+    below.  (The Fibonacci numbers are the same thing without a margin -- the sum of all before F [j - 1] is F [j] - 1 -- and so stand on
+    the edge: one stray count at the bottom, the end-of-block code for one, makes two chains of one and halves the depth; measured.)"""
+    f = [1, 1]
+    while len(f) < k:
+        below = sum(f[:-1])
+        f.append(below + 3 + below // slack)
+    return f[:k]
+
+
+def _skewed_like(seed, nlit, ncopy, nbg, slack=8):
+    """LZ atoms with EXACT counts under which Length_Limited_Coding's 15-bit limit binds, shuffled, realised as bytes the reference's
+    parser reads back as nearly those atoms:
+      * the counts of _steep (Fibonacci-like, with a margin) over nlit literal values, among nbg literals drawn from all the other values;
+      * the same over ncopy length codes (2 .. ncopy + 1, lengths from 5: none is found by chance), the shortest the most frequent;
+      * the same over ncopy distance codes (8 .. ncopy + 7, distances from 17), the widest codes the most frequent: a copy's source is
+        a stretch no earlier copy has read, so that the parser finds no second, nearer place for it, and a wide code has room for that;
+      * in symbol order a rare symbol stands between frequent ones (the odd literal values 1, 3, ...; every other code gets the counts from
+        the small end), so that Tweak_for_better_RLE (zip-compress-deflate.adb:340-365), which levels stretches of similar counts, finds none.
+    The copies read what lies before them, from 64 random bytes on; one that reaches farther back than there are bytes yet waits its turn.
+    Returns (bytes, history).  tests/test_primitives_model.py holds that the limit binds in the oracle's stream."""
+    r = np.random.RandomState(seed)
+
+    def dist_range(dc):
+        e = (dc >> 1) - 1
+        lo = ((2 + (dc & 1)) << e) + 1
+        return lo, lo + (1 << e)
+    out = bytearray(r.randint(0, 256, 64).astype(np.uint8).tobytes())
+    start = len(out)
+    chain = 2 * np.arange(nlit) + 1
+    others = np.setdiff1d(np.arange(256), chain)
+    lits = np.concatenate([np.repeat(chain, _steep(nlit, slack)), others[r.randint(0, len(others), nbg)]])
+    f = _steep(ncopy, slack)
+    half = ncopy // 2
+    len_code = {(ncopy - 1 - i // 2 if i % 2 == 0 else i // 2): 2 + i for i in range(ncopy)}       # rank of the count -> code: large, small, large, ...
+    dist_code = {(half + i // 2 if i % 2 == 0 else i // 2): 8 + i for i in range(ncopy)}           # the large ones growing with the distance
+    assert sorted(len_code) == sorted(dist_code) == list(range(ncopy))
+    # which length goes with which distance is free: the longest with the farthest, so that no copy is longer than its distance
+    lcs = np.sort(np.repeat([len_code[t] for t in range(ncopy)], f))[::-1]
+    dcs = np.sort(np.repeat([dist_code[t] for t in range(ncopy)], f))[::-1]
+    atoms = r.permutation(np.concatenate([lits, -1 - np.arange(len(lcs))]))
+    used = bytearray(len(out) + len(atoms) * 64)
+    todo, late = list(atoms), []                              # late: copies that find no unread stretch at their distance yet, in their order
+
+    def copy(t):
+        c, (lo, hi) = int(lcs[t]), dist_range(int(dcs[t]))
+        n = len(out)
+        if n < hi:
+            return False
+        L = _LEN_BASE[c] + (r.randint(0, 1 << _LEN_EXTRA[c]) if _LEN_EXTRA[c] else 0)
+        assert L <= lo
+        s = n - r.randint(lo, hi)
+        free = used.find(bytes(L), s, n - lo + L)
+        if free < 0:
+            free = used.find(bytes(L), n - hi + 1, s + L)
+        if free < 0:
+            return False
+        used[free:free + L] = b"\x01" * L
+        out.extend(out[free:free + L])
+        return True
+    while todo or late:
+        a = int(todo.pop()) if todo else int(others[r.randint(0, len(others))])       # (at the end: more of the other literals until the last has its room)
+        if a >= 0:
+            out.append(a)
+        elif not copy(-1 - a):
+            late.append(-1 - a)
+            continue
+        if late and copy(late[0]):
+            late.pop(0)
+    return bytes(out[start:]), bytes(out[:start])
+
+
 def _copies(n, seed):
     """Random bytes with a 4..12-byte copy every ~20 bytes at a log-uniform distance 4..32000: ~230 distinct
     literals per window, so that the empty-statistics descriptor of the null-slice quirk
@@ -328,6 +402,13 @@ def format_inputs():
     for per in (32505, 32506, 32507):
         blk = bytes(rs.randint(0, 256, per - 2000).astype(np.uint8)) + text[500000:502000]
         cases["period_%d" % per] = blk * 3 + blk[:1234]
+    # Length_Limited_Coding's 15-bit limit binds: on the literal / length code (17 rare literal values among 30 000 others, no copies:
+    # 40 732 bytes), on the distance code (17 distance codes, 111 597 bytes).  Sized by the census of tests/test_primitives_model.py:
+    # with 16 values / 16 codes the code without a limit is 15 deep and the limit no longer binds in the oracle's stream; with fewer other
+    # literals the copies of skew_dist find no unread sources and wait, which makes the input longer, not shorter.
+    if "skew" not in _cache:
+        _cache["skew"] = [h + a for a, h in (_skewed_like(11, nlit=17, ncopy=0, nbg=30000), _skewed_like(11, nlit=4, ncopy=17, nbg=10000))]
+    cases["skew_litlen"], cases["skew_dist"] = _cache["skew"]
     return cases
 
 

@@ -427,6 +427,15 @@ def test_one_bzip2_stream_over_two_and_three_ranks_protocol():
 # ----------------------------------------------------------------------------------------------------------------------
 # gather_stream_begin: every range received at its byte offset, shared edge bytes OR-ed
 # ----------------------------------------------------------------------------------------------------------------------
+def _free_port():
+    """A port nobody holds at this moment, from the kernel.  (A port worked out from the pid lies among the ephemeral ports, 32768 and up:
+    whichever connection another process has open from it keeps rank 0 from listening there, and the test fails for no fault of the code.)"""
+    import socket
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        return s.getsockname()[1]
+
+
 def _gather_worker(rank, world, port, q, spans, seed):
     sys.path.insert(0, ROOT)
     import importlib
@@ -465,7 +474,7 @@ def test_stream_gather_puts_every_range_at_its_offset(spans):
     world = len(spans)
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = 35500 + (os.getpid() + world * 13 + spans[0][1]) % 2000
+    port = _free_port()
     procs = [ctx.Process(target=_gather_worker, args=(r, world, port, q, spans, 5)) for r in range(world)]
     for p in procs:
         p.start()

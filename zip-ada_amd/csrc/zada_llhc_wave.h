@@ -1,8 +1,11 @@
 // zada_llhc_wave.h -- Huffman.Encoding.Length_Limited_Coding on ONE WAVE (64 lanes), device only.
 //
 // Same result, bit for bit, as the reference's sequential procedure
-// (zip_lib/huffman-encoding-length_limited_coding.adb:46-280), obtained from two observations that
-// tests/hostcheck (hc_llhc_pm) checks against the oracle on tens of thousands of inputs:
+// (zip_lib/huffman-encoding-length_limited_coding.adb:46-280), obtained from the two observations
+// below.  Their math is restated on the CPU (tests/hostcheck, hc_llhc_pm) and this code runs on its own,
+// one wave per vector, behind the hook zada_test_llhc (zada_testhooks.hip); both are held to the
+// oracle's lengths on the same 20 000 vectors (tests/_primitives.py, tests/test_primitives_model.py,
+// tests/test_gpu_primitives.py):
 //
 //  * Quick_sort (:196-223) is a Hoare partition around a(n/2) comparing weights only.  Its result
 //    on a sub-array has a closed form: with I = positions holding weight >= pivot (ascending) and
