@@ -135,16 +135,21 @@ int zada_set_knob(zada_ctx *ctx, const char *name, int value);
  * `in`, and passes `out` through CRC_Crypto.Encode + Zip.Block_Write afterwards).
  *   crc_inout : the RUNNING CRC register ("only updated here": caller does Init before and
  *               Final after, zip-compress.adb:144, 218).  May be NULL.
- *   cap       : capacity of out; cap >= n + 64 always suffices.
- *   out_len   : output_size.
+ *   cap       : capacity of out.  The stream is delivered when it fits -- a cap of exactly its length is enough, and cap >= n always
+ *               suffices: a stream of n bytes or more is ZADA_INEFFICIENT whatever cap is, and is not delivered.  A stream smaller than
+ *               the input that does not fit is ZADA_E_INVALID ("output buffer too small").  Nothing is written at or beyond out + cap.
+ *   out_len   : output_size; with ZADA_INEFFICIENT a length that is not below n.
  * Output bytes are bit-exact with the CPU restatement of the reference encoder (oracle/) for the same method; parity with an
  * Ada build of the reference is unpinned (no GNAT in this image: DESIGN.md 2). */
 int zada_deflate(zada_ctx *ctx, int method, const uint8_t *in, uint64_t n,
                  uint8_t *out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout,
                  zada_feedback_fn fb, void *user);
 
-/* Same, with `d_in` / `d_out` already resident in device memory (HBM) of ctx's device.
- * d_in must be readable for n bytes; d_out must hold cap >= n + 64 bytes. */
+/* Same, with `d_in` / `d_out` already resident in device memory (HBM) of ctx's device, both at any byte alignment (an input that is not
+ * 16-byte aligned is copied into the context's workspace first).  d_in must be readable for n bytes and is never written; d_out holds cap
+ * bytes, cap as above: the stream's exact length is enough.  Nothing is written at or beyond d_out + cap; with ZADA_E_INVALID or
+ * ZADA_INEFFICIENT the bytes below may hold the spans written before the verdict (a stream longer than "span_mib" goes out span after span).  crc_inout is the
+ * running register -- started anywhere, unchanged for n = 0 -- and may be NULL (tests/test_gpu_device_contract.py). */
 int zada_deflate_device(zada_ctx *ctx, int method, const void *d_in, uint64_t n,
                         void *d_out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout);
 
@@ -385,19 +390,23 @@ void zada_silesia_mix(uint64_t seed, unsigned class_mask, uint64_t offset, uint6
  * The stream is the complete BZip2 stream ("BZh9" ... footer).  Unlike zada_deflate it is also delivered with
  * ZADA_INEFFICIENT when it fits `cap` (*out_len <= cap), so the entry points serve a stand-alone .bz2 writer (bzip2_enc.adb) too.
  * A stream that is SMALLER than the input but does not fit `cap` is an error (ZADA_E_INVALID, "output buffer too small"), not
- * ZADA_INEFFICIENT: cap >= n is always enough for the Zip use (a stream of n bytes or more is inefficient whatever cap is).
+ * ZADA_INEFFICIENT: cap >= n is always enough for the Zip use (a stream of n bytes or more is inefficient whatever cap is).  There is no
+ * least cap: the 34 or 36 bytes of an empty entry's stream are delivered into a buffer of exactly that length, and *out_len of a stream
+ * that was not delivered is a lower bound of its length (not below n with ZADA_INEFFICIENT).
  * Streams of any length: the block limits are found a span of the stream at a time (knob "bz_span_mib", default 1024).
  * --------------------------------------------------------------------------------------------------------------- */
 int zada_bzip2(zada_ctx *ctx, int method, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len,
                uint32_t *crc_inout, zada_feedback_fn fb, void *user);
-/* the same with input and output in device memory (d_out: cap bytes) */
+/* the same with input and output in device memory, both at any byte alignment (an input that is not 16-byte aligned is copied into the
+ * context's workspace first).  d_in is never written; d_out: cap bytes, the stream's exact length is enough, nothing is written at or
+ * beyond d_out + cap, and nothing at all for a stream that does not fit.  crc_inout: the running register, may be NULL. */
 int zada_bzip2_device(zada_ctx *ctx, int method, const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len,
                       uint32_t *crc_inout);
 /* Many entries in one call (zipada's usual workload: many small files): the entries that are one block each -- up to 0.8 block
  * capacities, 720 000 bytes for BZip2_3 -- go through ONE launch sequence (every entry is a block of the call with its own stream
  * header, tactic choice and footer); longer ones are taken one after the other.  Arrays as for zada_deflate_batch; rc[i] is
  * zada_bzip2's return code for entry i, the stream is delivered whenever it fits cap[i].  Knob "bz_batch_mib" (default 256):
- * MiB of entries per launch sequence.  Returns the worst rc. */
+ * MiB of entries per launch sequence.  Returns the last negative rc[i], or 0 (an entry's ZADA_INEFFICIENT is in rc[i] only). */
 int zada_bzip2_batch(zada_ctx *ctx, int method, int count, const uint8_t *const *in, const uint64_t *n, uint8_t *const *out,
                      const uint64_t *cap, uint64_t *out_len, uint32_t *crc, int *rc);
 /* ---------------------------------------------------------------------------------------------------------------
@@ -424,7 +433,12 @@ int zada_bzip2_batch(zada_ctx *ctx, int method, int count, const uint8_t *const 
  * --------------------------------------------------------------------------------------------------------------- */
 int zada_lzma(zada_ctx *ctx, int method, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout,
               zada_feedback_fn fb, void *user);
-/* the same with input and output in device memory (d_out: cap bytes) */
+/* the same with input and output in device memory, both at any byte alignment (an input that is not 16-byte aligned is copied into the
+ * context's workspace first).  d_in is never written.  d_out: cap bytes; the coder writes the payload there as it goes and counts the bytes
+ * beyond cap without writing them, so nothing is written at or beyond d_out + cap, and of a payload that does not fit the first cap bytes
+ * are there.  As with zada_bzip2, a payload that fits is delivered with ZADA_INEFFICIENT too (its exact length is enough), one smaller than
+ * the input that does not fit is ZADA_E_INVALID ("output buffer too small"), and *out_len is the payload's full length either way.
+ * crc_inout: the running register, may be NULL. */
 int zada_lzma_device(zada_ctx *ctx, int method, const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout);
 /* A stream that stopped between two launches (its feedback returned non-zero: ZADA_ABORTED) can be taken up again -- by this context, another one or
  * another process: zada_lzma_export_state copies out the coder's state (*state_len bytes: the probability model, the range coder, the window
@@ -446,7 +460,7 @@ int zada_lzma_import_state(zada_ctx *ctx, const uint8_t *state, uint64_t state_l
 /* bytes of device memory the literal table of one entry of `method` takes (0: it is in the coder's LDS, or not an LZMA method).  Pure host code. */
 uint64_t zada_lzma_lit_table_bytes(int method);
 /* Many entries, one launch of the coder for all of them.  Arrays as for zada_deflate_batch; rc[i] is zada_lzma's return code
- * for entry i.  Returns the worst rc. */
+ * for entry i, the payload is delivered whenever it fits cap[i].  Returns the last negative rc[i], or 0 (an entry's ZADA_INEFFICIENT is in rc[i] only). */
 int zada_lzma_batch(zada_ctx *ctx, int method, int count, const uint8_t *const *in, const uint64_t *n, uint8_t *const *out,
                     const uint64_t *cap, uint64_t *out_len, uint32_t *crc, int *rc);
 /* Trace of the last zada_bzip2* call: per block of Read_and_Split_Block (bzip2-encoding.adb:1144) four values -- raw start,

@@ -1926,10 +1926,10 @@ int zada_deflate_device(zada_ctx *z, int method, const void *d_in, uint64_t n, v
     return rc;
   }
   const uint8_t *src = (const uint8_t *)d_in;
-  if (((uintptr_t)d_in & 15) != 0 && n) {              // the kernels read 16 bytes at a time
+  if (((uintptr_t)d_in & 15) != 0) {                   // the kernels read 16 bytes at a time (an empty input too: range_open looks at the address)
     rc = ensure_rin(c, n);
     if (rc) return rc;
-    hipMemcpyAsync(c->ws.rin_own, d_in, n, hipMemcpyDeviceToDevice, c->stream);
+    if (n) hipMemcpyAsync(c->ws.rin_own, d_in, n, hipMemcpyDeviceToDevice, c->stream);
     src = c->ws.rin_own;
   }
   uint64_t ol = 0;

@@ -2946,7 +2946,7 @@ int bz2_encode_device(Ctx *c, int option, const uint8_t *d_in, uint64_t n, int64
                       zada_feedback_fn fb, void *user) {
   Bz2State *B = bz_state(c);
   int rc;
-  if (cap < 64) { c->err = "output buffer too small"; return ZADA_E_INVALID; }
+  // (any cap: what does not fit is refused below, before a byte is written -- a stream of n bytes or more as ZADA_INEFFICIENT, whatever cap is)
   bz_reset_call(c);
   B->trace.clear();
   if (fb && fb(0, user)) return ZADA_ABORTED;
