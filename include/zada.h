@@ -120,7 +120,7 @@ const char *zada_version(void);
  * needs more gets the full 1152 and the parse starts again), "inner_budget" (ZADA_INNER_BUDGET), "shard_kib" (ZADA_SHARD_KIB: KiB of
  * a stream the match finder takes at a time, multiple of 64), "span_mib" (MiB of a stream one pass takes; longer streams go span after
  * span, default 2048), "link_run" (segments of 32 KiB one workgroup of the link stage takes one after the other, making their cross links itself:
- * a power of two from 1 to 64, 0 = by size; anything else is ZADA_E_INVALID), "batch_mib" (MiB one batch of small entries may take), "bunzip_batch_mib" (MiB of HBM one group of zada_bunzip2_batch may take: streams, outputs, slots, tt arrays; 16 .. 262144, default 8192), "bz_batch_mib" / "bz_span_mib" / "bz_batch_melems" (BZip2
+ * a power of two from 1 to 64, 0 = by size; anything else is ZADA_E_INVALID), "batch_mib" (MiB one batch of small entries may take), "unzip_piece" (test knob: log2 of the bytes of one piece of a stored entry in zada_unzip_device, 8 .. 14, default 14),"bunzip_batch_mib" (MiB of HBM one group of zada_bunzip2_batch may take: streams, outputs, slots, tt arrays; 16 .. 262144, default 8192), "bz_batch_mib" / "bz_span_mib" / "bz_batch_melems" (BZip2
  * batching; "bz_lists", "bz_list_rows", "bz_text_order", "bz_pipeline", "bz_pipe_prio", "bz_small_wg", "bz_split", "bz_tail_pct": scheduling of the BZip2 stages), "lzma_chunk" (positions of an LZMA stream one launch codes between two feedback calls; 0 = by level, -1 = one launch
  * per stream), "lzma_pool" (test knob: blocks of the LZMA_3 match sets' overflow pool to start with, 0 = by size; a pool that is too small is
  * counted and the match producer's walk runs again; for a stream whose producer works in segments the pool grows between the segments), "lzma_pool_fixed" (test knob: 1 = it
@@ -318,6 +318,45 @@ int zada_unlzma_batch(zada_ctx *ctx, int count, const uint8_t *const *in, const 
  * output position where the decoder stood, how the stream ended (1: on a marker, 2: without, 0: it did not).  Up to cap_items values are
  * copied; returns how many there are. */
 uint64_t zada_unlzma_last_records(zada_ctx *ctx, uint64_t *dst, uint64_t cap_items);
+
+/* ---- The reader: an archive that lies in device memory, extracted into device memory -----------------------------------
+ * `count` entries of one archive in ONE call, every method the reader decodes: what UnZip.Extract does entry after entry (unzip.adb), with no entry
+ * byte crossing the host.  ent [i] is the entry's row of the directory:
+ *   in_off, n_in  : its data, archive bytes [in_off, in_off + n_in), the 12-byte encryption header included
+ *   out_off, cap  : its output, bytes [out_off, out_off + cap) of d_out; cap = the uncompressed size the directory promises
+ *   method        : 0 Store, 8 Deflate, 9 Deflate64, 12 BZip2, 14 LZMA
+ *   flags         : bit 0: encrypted (CRC_Crypto), bit 1: the LZMA stream ends on the marker (eos)
+ *   check         : encrypted: the byte the decoded encryption header must end in (crc >> 24, or the time stamp's high byte with flag bit 3)
+ * d_archive (archive_len bytes) and d_out (out_bytes bytes) are device addresses at any byte alignment, in_off and out_off any values.  The archive is
+ * never written: encrypted data are decoded out of place, from keys0 -- the keys of the password (zada_crypt_init_keys), the same for every entry --
+ * into workspace of the context (a stored entry: straight into its output range) by one lane per entry, sixteen bytes a step, which also checks the
+ * header's last byte: a mismatch is ZADA_E_PASSWORD for that entry, whose decoding stops behind the header and whose output range stays untouched.
+ * In d_out nothing is written outside the entries' ranges.
+ * res [i]: rc is ZADA_OK, ZADA_E_DATA or ZADA_E_PASSWORD; crc is in/out, the running register as everywhere else; out_len the bytes written; in_used
+ * counts archive bytes (with the 12 header bytes of an encrypted entry; Store: n_in).  ZADA_OK and ZADA_E_DATA are what the method's decoder above gives
+ * for the same bytes, by the same rules: Deflate, Deflate64, BZip2 and LZMA entries run through the same launches as zada_inflate_batch,
+ * zada_bunzip2_batch and zada_unlzma_batch (whose bounds on work arrays hold: the work-array half of "bunzip_batch_mib", "lzma_lit_mib"), their jobs
+ * pointing into the archive -- or the decoded copy -- and into d_out.  An encrypted entry shorter than 12 bytes is ZADA_E_DATA; so is a stored entry
+ * with more bytes (less the header) than cap, otherwise its out_len is that length.  A failed entry delivers nothing (out_len = in_used = 0, the
+ * register unchanged).  Stored entries are copied and summed in one pass, parallel INSIDE an entry: pieces of 16 KiB (test knob "unzip_piece": log2 of
+ * the piece, 8 .. 14; it changes no byte), one wave per piece, then one wave per entry folds the pieces' registers.
+ * Argument checks come before anything touches the device, each ZADA_E_INVALID with the entry's index in zada_last_error: a range beyond archive_len or
+ * out_bytes, an unknown method, an encrypted entry with keys0 = NULL, two entries with cap > 0 whose output ranges overlap; a stream or a cap of 1 TiB
+ * or more is ZADA_E_TOO_LARGE.  d_out = NULL is the test-only form: out_off and out_bytes are ignored, the decoded bytes go to workspace of the context
+ * in groups of at most "batch_mib" MiB, and only res comes back.  The call returns the worst res [i].rc, or what stopped it; it synchronises the
+ * context's stream before it returns, and forgets a stopped LZMA stream as every entry point does. */
+enum { ZADA_E_PASSWORD = -8 };  /* zada_unzip_device only: the decoded encryption header does not end in the entry's check byte */
+typedef struct {
+  uint64_t in_off, n_in;
+  uint64_t out_off, cap;
+  uint16_t method;
+  uint8_t flags;
+  uint8_t check;
+  uint32_t pad;
+} zada_unzip_entry;
+typedef struct { int32_t rc; uint32_t crc; uint64_t out_len, in_used; } zada_unzip_result;
+int zada_unzip_device(zada_ctx *ctx, const void *d_archive, uint64_t archive_len, void *d_out, uint64_t out_bytes,
+                      int count, const zada_unzip_entry *ent, const uint32_t keys0[3], zada_unzip_result *res);
 
 /* ---- One stream over several contexts (GPUs) -------------------------------------------------------------------
  * The reference compresses an entry as ONE sequential stream (a 32 KiB window, a lazy-match state machine, a flush of the

@@ -710,6 +710,25 @@ static void bzd_describe(Ctx *c, const BzdResult &R, int entry) {
   c->err = buf;
 }
 
+// bzd_run for zada_unzip_device (zada_internal.h)
+int bunzip2_run_jobs(Ctx *c, uint32_t E, const ReaderJob *rj, ReaderRes *rr, bool *described) {
+  if (E == 0) return 0;
+  BzdState *S = bzd_state(c);
+  if (!S) { c->err = "bunzip2: no memory for the tables"; return ZADA_E_NOMEM; }
+  std::vector<BzdJob> jobs(E);
+  std::vector<uint32_t> regs(E);
+  std::vector<BzdResult> res;
+  for (uint32_t k = 0; k < E; k++) { jobs[k] = BzdJob{rj[k].in, rj[k].out, rj[k].n_in, rj[k].cap}; regs[k] = rr[k].crc; }
+  S->last_entries.clear(); S->last_blocks.clear();
+  const int rc = bzd_run(c, S, jobs, regs.data(), res);
+  if (rc) return rc;
+  for (uint32_t k = 0; k < E; k++) {
+    if (res[k].rc) { rr[k] = ReaderRes{ZADA_E_DATA, regs[k], 0, 0}; if (!*described) { bzd_describe(c, res[k], rj[k].index); *described = true; } }
+    else rr[k] = ReaderRes{ZADA_OK, res[k].crc, res[k].out_len, res[k].in_used};
+  }
+  return 0;
+}
+
 }  // namespace zada
 
 using namespace zada;

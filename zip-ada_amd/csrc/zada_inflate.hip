@@ -431,6 +431,24 @@ static void inf_describe(Ctx *c, const InfResult &R, int entry) {
   c->err = buf;
 }
 
+// inf_run for zada_unzip_device (zada_internal.h)
+int inflate_run_jobs(Ctx *c, uint32_t E, const ReaderJob *rj, ReaderRes *rr, bool *described) {
+  if (E == 0) return 0;
+  InfState *S = inf_state(c);
+  if (!S) { c->err = "inflate: no memory for the tables"; return ZADA_E_NOMEM; }
+  std::vector<InfJob> jobs(E);
+  std::vector<uint32_t> regs(E);
+  std::vector<InfResult> res;
+  for (uint32_t k = 0; k < E; k++) { jobs[k] = InfJob{rj[k].in, rj[k].out, rj[k].n_in, rj[k].cap, rj[k].format, 0}; regs[k] = rr[k].crc; }
+  const int rc = inf_run(c, S, jobs, regs.data(), res);
+  if (rc) return rc;
+  for (uint32_t k = 0; k < E; k++) {
+    if (res[k].rc) { rr[k] = ReaderRes{ZADA_E_DATA, regs[k], 0, 0}; if (!*described) { inf_describe(c, res[k], rj[k].index); *described = true; } }
+    else rr[k] = ReaderRes{ZADA_OK, res[k].crc, res[k].out_len, res[k].in_used};
+  }
+  return 0;
+}
+
 }  // namespace zada
 
 using namespace zada;

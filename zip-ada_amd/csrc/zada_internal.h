@@ -265,6 +265,8 @@ struct Ctx {
   void *inf = nullptr;                               // Inflate state (zada_inflate.hip), made on first use
   void *bzd = nullptr;                               // BZip2 reader state (zada_bunzip2.hip), made on first use
   void *ulz = nullptr;                               // LZMA reader state (zada_unlzma.hip), made on first use
+  void *uz = nullptr;                                // archive reader state (zada_unzip.hip), made on first use
+  int knob_unzip_piece = 14;                         // "unzip_piece" (test knob): log2 of the bytes of one piece of a stored entry (8 .. 14)
   void *lz_tab = nullptr; size_t cap_lz_tab = 0;     // LZMA (zada_lzma.hip): job table + results
   void *lz_save = nullptr; size_t cap_lz_save = 0;   // ... the coder's state between the launches of one stream
   void *lz_lit = nullptr; size_t cap_lz_lit = 0;     // ... the HBM literal tables of the methods with lc + lp >= 4, one per entry of a launch group
@@ -338,6 +340,16 @@ void inflate_destroy(Ctx *c);                       // Inflate (zada_inflate.hip
 int inflate_crc_entries(Ctx *c, uint32_t E, const uint64_t *out, const uint64_t *out_len, uint32_t *regs);   // ... its k_inf_crc over outputs in device memory
 void bunzip2_destroy(Ctx *c);                       // the BZip2 reader (zada_bunzip2.hip)
 void unlzma_destroy(Ctx *c);                        // the LZMA reader (zada_unlzma.hip)
+void unzip_destroy(Ctx *c);                         // the archive reader (zada_unzip.hip)
+// The readers' runners (inf_run, bzd_run, ulz_run) on jobs whose streams and outputs are device addresses, for zada_unzip_device: one call takes
+// every entry of a method through the launches of the method's batch call.  res [k].crc is in/out (the running register), rc ZADA_OK or ZADA_E_DATA;
+// the first entry that fails is described in the context's error text under its number `index`, unless *described says one already is.
+struct ReaderJob { uint64_t in, out, n_in, cap; int32_t format; uint32_t eos; uint64_t lit_elems; int32_t index, pad; };   // format: Inflate (8 / 9); eos, lit_elems: LZMA
+struct ReaderRes { int32_t rc; uint32_t crc; uint64_t out_len, in_used; };
+int inflate_run_jobs(Ctx *c, uint32_t E, const ReaderJob *jobs, ReaderRes *res, bool *described);
+int bunzip2_run_jobs(Ctx *c, uint32_t E, const ReaderJob *jobs, ReaderRes *res, bool *described);
+int unlzma_run_jobs(Ctx *c, uint32_t E, const ReaderJob *jobs, ReaderRes *res, bool *described);
+uint64_t unlzma_hbm_elems(const uint8_t *h9, uint64_t n_in);   // ReaderJob::lit_elems of an LZMA entry, from the first nine bytes of its payload
 void crypt_update_keys(uint32_t keys[3], uint8_t by);
 uint8_t crypt_code(const uint32_t keys[3]);
 constexpr uint64_t CRYPT_WAVE_MAX = 256u << 10;     // a batch's entries of up to this many bytes: one wave each, in one launch

@@ -307,6 +307,26 @@ static void ulz_describe(Ctx *c, const UlzResult &R, int entry) {
   c->err = buf;
 }
 
+// ulz_run for zada_unzip_device (zada_internal.h)
+uint64_t unlzma_hbm_elems(const uint8_t *h9, uint64_t n_in) { return ulz_hbm_elems(h9, n_in); }
+int unlzma_run_jobs(Ctx *c, uint32_t E, const ReaderJob *rj, ReaderRes *rr, bool *described) {
+  if (E == 0) return 0;
+  UlzState *S = ulz_state(c);
+  if (!S) { c->err = "unlzma: no memory for the tables"; return ZADA_E_NOMEM; }
+  std::vector<UlzJob> jobs(E);
+  std::vector<uint32_t> regs(E);
+  std::vector<UlzResult> res;
+  for (uint32_t k = 0; k < E; k++) { jobs[k] = UlzJob{rj[k].in, rj[k].out, rj[k].n_in, rj[k].cap, 0, rj[k].lit_elems, rj[k].eos ? 1u : 0u, 0}; regs[k] = rr[k].crc; }
+  S->last_entries.clear();
+  const int rc = ulz_run(c, S, jobs, regs.data(), res);
+  if (rc) return rc;
+  for (uint32_t k = 0; k < E; k++) {
+    if (res[k].rc) { rr[k] = ReaderRes{ZADA_E_DATA, regs[k], 0, 0}; if (!*described) { ulz_describe(c, res[k], rj[k].index); *described = true; } }
+    else rr[k] = ReaderRes{ZADA_OK, res[k].crc, res[k].out_len, res[k].in_used};
+  }
+  return 0;
+}
+
 }  // namespace zada
 
 using namespace zada;
