@@ -358,6 +358,42 @@ typedef struct { int32_t rc; uint32_t crc; uint64_t out_len, in_used; } zada_unz
 int zada_unzip_device(zada_ctx *ctx, const void *d_archive, uint64_t archive_len, void *d_out, uint64_t out_bytes,
                       int count, const zada_unzip_entry *ent, const uint32_t keys0[3], zada_unzip_result *res);
 
+/* ---- The writer: an archive made from entries in device memory, into device memory -------------------------------------
+ * `count` entries where they lie in device memory become ONE complete Zip archive in d_archive: local headers, payloads, central directory and end
+ * records, byte for byte what Zip.Create writes for the same inputs (Create_Archive, Add_Stream entry after entry in the order given, Finish:
+ * zip-create.adb:36-58, 194-297, 645-756).  No entry byte crosses the host.  ent [i]:
+ *   d_data, n      : the entry's bytes, a device address at any byte alignment (may be NULL when n = 0); never written
+ *   name, name_len : HOST memory: the bytes that go into the headers (at most 65 535)
+ *   time           : the DOS time of the headers
+ *   flags          : bit 0: the Language-encoding flag bit (0x0800) is set in the headers
+ * method is Store (0) or Deflate_Fixed .. Deflate_R (6 .. 11); every other method is ZADA_E_INVALID with a text that names it.  An entry whose
+ * Deflate stream is not shorter than its input is stored with zip type 0 (Compress_Data's fallback, zip-compress.adb:224-237).  The form of a local
+ * header is decided on the provisional sizes (zip-create.adb:231-241); the Zip64 local and central extensions, the Zip64 end record and locator,
+ * Check_Size (:161-179) and the promotion at 65 535 or more entries are the reference's.  archive_base is the number of bytes that precede d_archive
+ * in the file the caller will write: every offset in the headers counts from it (normally 0).
+ * Entries of up to 4 MiB are taken in groups of consecutive entries bounded by the knob "batch_mib", each group through the launches of
+ * zada_deflate_batch -- gathered from their addresses by one kernel, their streams and headers placed by another, only 12 bytes per entry coming to
+ * the host in between --; a larger entry, or a group of one, runs alone through the launches of zada_deflate_device.  Store is a copy with the CRC-32
+ * in one pass, in pieces of 16 KiB as in zada_unzip_device.
+ * res [i]: the entry's final CRC-32, compressed size and zip type (0 or 8), and the offset of its local header (counted with archive_base).
+ * *archive_len: the archive's length.  zada_zip_bound is an upper bound on it, computed on the host without a context; the call needs only
+ * cap >= *archive_len.  Nothing is written outside [d_archive, d_archive + cap).  If the archive does not fit, the call returns ZADA_E_INVALID
+ * ("archive buffer too small") and the contents of the buffer are unspecified.
+ * Argument checks come before anything touches the device, each ZADA_E_INVALID with the entry's index in zada_last_error: a null d_data with n > 0, a
+ * name longer than 65 535 bytes, an input range that overlaps [d_archive, d_archive + cap); an entry of 1 TiB or more is ZADA_E_TOO_LARGE.
+ * count = 0 gives the 22-byte end record.  The call synchronises the context's stream before it returns, and forgets a stopped LZMA stream as every
+ * entry point does. */
+typedef struct {
+  const void *d_data; uint64_t n;
+  const uint8_t *name; uint32_t name_len;
+  uint32_t time;
+  uint32_t flags;
+} zada_zip_entry;
+typedef struct { int32_t rc; uint16_t zip_type; uint16_t pad; uint32_t crc; uint64_t csize, offset; } zada_zip_result;
+uint64_t zada_zip_bound(int count, const zada_zip_entry *ent, uint64_t archive_base);
+int zada_zip_device(zada_ctx *ctx, int method, int count, const zada_zip_entry *ent, void *d_archive, uint64_t cap, uint64_t archive_base,
+                    uint64_t *archive_len, zada_zip_result *res);
+
 /* ---- One stream over several contexts (GPUs) -------------------------------------------------------------------
  * The reference compresses an entry as ONE sequential stream (a 32 KiB window, a lazy-match state machine, a flush of the
  * LZ buffer every 65 536 atoms and the block chooser's state all run through it: lz77.adb:827-933,

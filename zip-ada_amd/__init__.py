@@ -215,6 +215,10 @@ def load_library():
         L.zada_unlzma_last_records.argtypes = [vp, vp, u64]
     if hasattr(L, "zada_unzip_device"):              # (likewise: the archive reader on device memory)
         L.zada_unzip_device.argtypes = [vp, vp, u64, vp, u64, i32, vp, u32p, vp]
+    if hasattr(L, "zada_zip_device"):                # (likewise: the archive writer on device memory)
+        L.zada_zip_bound.restype = u64
+        L.zada_zip_bound.argtypes = [i32, vp, u64]
+        L.zada_zip_device.argtypes = [vp, i32, i32, vp, vp, u64, u64, u64p, vp]
     L.zada_bz2_last_blocks.restype = ctypes.c_uint64
     L.zada_bz2_last_blocks.argtypes = [vp, vp, u64]
     L.zada_crc32_combine.restype = ctypes.c_uint32
@@ -882,6 +886,34 @@ class Encoder:
             self._err(rc, "zada_unzip_device")
         return rc, res
 
+    # ---- the archive writer on device memory (include/zada.h "an archive made from entries in device memory") ----
+    @staticmethod
+    def zip_dtypes():
+        """(dtype of zada_zip_entry, dtype of zada_zip_result) as numpy structured types."""
+        import numpy as np
+        return (np.dtype([("d_data", "<u8"), ("n", "<u8"), ("name", "<u8"), ("name_len", "<u4"), ("time", "<u4"), ("flags", "<u4"), ("pad", "<u4")]),
+                np.dtype([("rc", "<i4"), ("zip_type", "<u2"), ("pad", "<u2"), ("crc", "<u4"), ("pad2", "<u4"), ("csize", "<u8"), ("offset", "<u8")]))
+
+    def zip_bound(self, entries, archive_base=0):
+        """zada_zip_bound: an upper bound on the archive zip_device makes of `entries` (only n and name_len are read)."""
+        import numpy as np
+        ent = np.ascontiguousarray(entries, dtype=self.zip_dtypes()[0])
+        return int(self.lib.zada_zip_bound(len(ent), ent.ctypes.data if len(ent) else None, archive_base))
+
+    def zip_device(self, entries, d_archive_ptr, cap, method=Method.Deflate_3, archive_base=0):
+        """zada_zip_device: `entries` is a numpy structured array of zip_dtypes () [0] rows (d_data: device addresses; name: HOST addresses the caller keeps
+        alive).  Returns (the archive's length, the structured array of results).  Whatever the call refuses raises ZadaError."""
+        import numpy as np
+        dt_e, dt_r = self.zip_dtypes()
+        ent = np.ascontiguousarray(entries, dtype=dt_e)
+        res = np.zeros(len(ent), dtype=dt_r)
+        alen = ctypes.c_uint64(0)
+        rc = self.lib.zada_zip_device(self.ctx, method, len(ent), ent.ctypes.data if len(ent) else None, d_archive_ptr, cap, archive_base, ctypes.byref(alen),
+                                      res.ctypes.data if len(ent) else None)
+        if rc != 0:
+            self._err(rc, "zada_zip_device")
+        return alen.value, res
+
     def lz77_tokens(self, data, method=Method.Deflate_3):
         import numpy as np
         n = len(data)
@@ -1090,6 +1122,49 @@ class ZipCreate:
         self.buf += hdr + nm + ext + payload
         self.entries.append(e)
         return e["csize"], zt
+
+    def write_device(self, names, tensors, file_time=None, unicode_name=True):
+        """add_streams + finish for entries that lie in device memory: tensors are contiguous torch.uint8 tensors on the encoder's device (empty ones
+        are allowed).  ONE zada_zip_device call writes the complete archive -- the bytes add_streams and finish write for the same inputs -- into a
+        tensor on that device; no entry byte crosses the host.  Returns the archive as a view of that tensor; self.entries is what add_compressed
+        would have recorded (self.buf stays empty).  Only on a ZipCreate that has no entries yet, with method Store or a Deflate method.
+        The view keeps the whole allocation of zada_zip_bound bytes alive -- the inputs' size plus the headers, however small the archive turns out:
+        .clone() it to let the rest go.  A name longer than 65 535 bytes is refused by the C call (ZadaError with the entry's index), where
+        add_compressed fails in struct.pack."""
+        import numpy as np
+        import torch
+        if self.entries or self.buf:
+            raise ValueError("ZipCreate.write_device: the archive already has entries")
+        names, tensors = list(names), list(tensors)
+        if len(names) != len(tensors):
+            raise ValueError("ZipCreate.write_device: %d names for %d tensors" % (len(names), len(tensors)))
+        dev = torch.device("cuda", self.enc.device)
+        for t in tensors:
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_contiguous() or (t.numel() and t.device != dev):
+                raise ZadaError("ZipCreate.write_device: contiguous torch.uint8 tensors on %s are needed" % dev)
+        nms = [nm.replace("\\", "/").encode("utf-8") for nm in names]
+        n = len(nms)
+        tab = np.zeros(n, dtype=self.enc.zip_dtypes()[0])
+        blob = np.frombuffer(b"".join(nms) + b"\0", dtype=np.uint8)          # the names one behind the other: the table points into it
+        nlen = np.fromiter((len(nm) for nm in nms), np.uint64, n)
+        tab["name"] = np.uint64(blob.ctypes.data) + np.cumsum(nlen) - nlen
+        tab["name_len"] = np.minimum(nlen, 0xFFFFFFFF)
+        tab["n"] = np.fromiter((t.numel() for t in tensors), np.uint64, n)
+        tab["d_data"] = np.fromiter((t.data_ptr() if t.numel() else 0 for t in tensors), np.uint64, n)
+        tab["time"] = self.DEFAULT_TIME if file_time is None else file_time
+        tab["flags"] = 1 if unicode_name else 0
+        cap = self.enc.zip_bound(tab, self._bias)
+        out = torch.empty(cap, dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        alen, res = self.enc.zip_device(tab, out.data_ptr(), cap, self.method, self._bias)
+        flag = 0x0800 if unicode_name else 0
+        for k, nm in enumerate(nms):
+            r = res[k]
+            usize = int(tab["n"][k])
+            self._check_size(usize)
+            self.entries.append(dict(name=nm, flag=flag, zip_type=int(r["zip_type"]), time=int(tab["time"][k]), crc=int(r["crc"]), csize=int(r["csize"]), usize=usize,
+                                     offset=int(r["offset"])))
+        return out[:alen]
 
     def finish(self):
         cd_off = len(self.buf) + self._bias

@@ -803,7 +803,7 @@ static int deflate_spans(Ctx *c, int method, const uint8_t *d_src, const uint8_t
       }
       rc = entropy_emit(c, nullptr);
       if (rc) return rc;
-      if (base_bytes + nb > cap) { c->err = "output buffer too small"; return ZADA_E_INVALID; }
+      if (base_bytes + nb > cap) { c->err = ERR_OUTPUT_TOO_SMALL; return ZADA_E_INVALID; }
       if (d_dst) hipMemcpyAsync(d_dst + base_bytes, W.out, nb, hipMemcpyDeviceToDevice, st);
       else if (copy_out(c, h_dst + base_bytes, W.out, nb)) return ZADA_E_HIP_;
       if ((cc.pos & 7) && nb) hipMemcpyAsync(&shared, W.out + nb - 1, 1, hipMemcpyDeviceToHost, st);
@@ -914,41 +914,50 @@ static void parallel_entries(uint32_t E, uint64_t bytes, F &&fn) {
   for (auto &x : th) x.join();
 }
 
-// entries idx[0 .. E) of the caller's arrays through one launch sequence
-static int batch_core(Ctx *c, int method, const int *idx, uint32_t E, const uint8_t *const *in, const uint64_t *n, uint8_t *const *out,
-                      const uint64_t *cap, uint64_t *out_len, uint32_t *crc, int *rc_out) {
-  const int level = method_level(method);
-  Workspace &W = c->ws;
-  hipStream_t st = c->stream;
-  // ---- layout
-  std::vector<uint32_t> start(E + 1), fl0(E + 1), chunk0(E + 1), len(E + 1), crc_in(E + 1);
+// A batch's layout and tables, from the entries' lengths alone: every entry on whole 32 KiB segments of the LZ buffer.  Books the workspaces and the
+// pinned table buffer and fills the tables in it (batch_launch uploads them).  len [e], crc_in [e]: entry e of the batch (crc_in null: a fresh register).
+int batch_layout(Ctx *c, uint32_t E, const uint64_t *n, const uint32_t *crc_in, BatchLayout &L) {
+  L.E = E;
+  L.start.resize(E + 1); L.len.resize(E + 1);
+  std::vector<uint32_t> fl0(E + 1), chunk0(E + 1), reg(E + 1);
   uint64_t total = 0, nfs = 0;
   for (uint32_t e = 0; e < E; e++) {
-    const uint64_t ln = n[idx[e]], slot = ((ln ? ln : 1) + 32767) & ~32767ull;
-    start[e] = (uint32_t)total; len[e] = (uint32_t)ln; chunk0[e] = (uint32_t)(total / PCHUNK); fl0[e] = (uint32_t)nfs;
-    crc_in[e] = crc ? crc[idx[e]] : 0xFFFFFFFFu;
+    const uint64_t ln = n[e], slot = ((ln ? ln : 1) + 32767) & ~32767ull;
+    L.start[e] = (uint32_t)total; L.len[e] = (uint32_t)ln; chunk0[e] = (uint32_t)(total / PCHUNK); fl0[e] = (uint32_t)nfs;
+    reg[e] = crc_in ? crc_in[e] : 0xFFFFFFFFu;
     total += slot; nfs += ln ? (ln + FLUSH - 1) / FLUSH : 1;
   }
-  start[E] = (uint32_t)total; fl0[E] = (uint32_t)nfs; chunk0[E] = (uint32_t)(total / PCHUNK); len[E] = 0;
-  const uint32_t nseg = (uint32_t)(total >> 15);
+  L.start[E] = (uint32_t)total; fl0[E] = (uint32_t)nfs; chunk0[E] = (uint32_t)(total / PCHUNK); L.len[E] = 0;
+  L.total = total; L.nfs = nfs; L.nseg = (uint32_t)(total >> 15);
   int rc = ensure_lz_workspace(c, total + 4096);
   if (!rc) rc = ensure_entropy_workspace(c, total, nfs);
-  if (!rc) rc = ensure_batch_workspace(c, E, nfs, nseg);
-  if (!rc) rc = grow_pinned((void **)&c->bstage, &c->cap_bstage, total + total / 8 + (1u << 20));
-  const uint64_t tabw = (uint64_t)nseg + 6ull * (E + 1) + 64;
+  if (!rc) rc = ensure_batch_workspace(c, E, nfs, L.nseg);
+  const uint64_t tabw = (uint64_t)L.nseg + 6ull * (E + 1) + 64;
   uint64_t capw = c->cap_btab * 4;
   if (!rc) { rc = grow_pinned((void **)&c->btab, &capw, tabw * 4); c->cap_btab = capw / 4; }
   if (rc) return rc;
-  // ---- pack the entries and the tables (pinned), one copy each
+  uint32_t *t_ent = c->btab + L.nseg;
+  memcpy(t_ent, chunk0.data(), (E + 1) * 4); memcpy(t_ent + (E + 1), fl0.data(), (E + 1) * 4); memcpy(t_ent + 2 * (E + 1), L.start.data(), (E + 1) * 4);
+  memcpy(t_ent + 3 * (E + 1), L.len.data(), (E + 1) * 4); memcpy(t_ent + 4 * (E + 1), reg.data(), (E + 1) * 4);
+  return 0;
+}
+// the segment table's rows of entry e (pinned; the caller fills them entry by entry, next to whatever else it does per entry)
+static inline void batch_segends(Ctx *c, const BatchLayout &L, uint32_t e) {
+  uint32_t *t_seg = c->btab;
+  for (uint32_t s = L.start[e] >> 15; s < (L.start[e + 1] >> 15); s++) t_seg[s] = (L.start[e] + L.len[e]) | (s == (L.start[e] >> 15) ? 0x80000000u : 0u);
+}
+void batch_segends_all(Ctx *c, const BatchLayout &L) { for (uint32_t e = 0; e < L.E; e++) batch_segends(c, L, e); }
+
+// The launch sequence of a batch whose entries are (or will be, in stream order) in their slots of W.in: the tables go up, CRC-32, the LZ stage of all
+// entries, the entropy stage with every entry a stream of its own; then the verdicts -- sizes, places, CRCs: 12 bytes per entry -- are on their way
+// to the pinned table buffer (*h_bytes, *h_base, *h_crc: valid once the stream is synchronised).  The streams lie in W.out, *obytes of them.
+int batch_launch(Ctx *c, int method, const BatchLayout &L, uint64_t *obytes, uint32_t **h_bytes, uint32_t **h_base, uint32_t **h_crc) {
+  const int level = method_level(method);
+  Workspace &W = c->ws;
+  hipStream_t st = c->stream;
+  const uint32_t E = L.E, nseg = L.nseg;
+  const uint64_t total = L.total, nfs = L.nfs;
   uint32_t *t_seg = c->btab, *t_ent = c->btab + nseg;
-  parallel_entries(E, total, [&](uint32_t e) {
-    if (len[e]) memcpy(c->bstage + start[e], in[idx[e]], len[e]);
-    for (uint32_t s = start[e] >> 15; s < (start[e + 1] >> 15); s++) t_seg[s] = (start[e] + len[e]) | (s == (start[e] >> 15) ? 0x80000000u : 0u);
-  });
-  memcpy(t_ent, chunk0.data(), (E + 1) * 4); memcpy(t_ent + (E + 1), fl0.data(), (E + 1) * 4); memcpy(t_ent + 2 * (E + 1), start.data(), (E + 1) * 4);
-  memcpy(t_ent + 3 * (E + 1), len.data(), (E + 1) * 4); memcpy(t_ent + 4 * (E + 1), crc_in.data(), (E + 1) * 4);
-  c->tbegin(); c->tmark("begin");
-  hipMemcpyAsync(W.in, c->bstage, total, hipMemcpyHostToDevice, st);
   hipMemcpyAsync(W.segend, t_seg, (size_t)nseg * 4, hipMemcpyHostToDevice, st);
   hipMemcpyAsync(W.ent_chunk0, t_ent, (size_t)(E + 1) * 4, hipMemcpyHostToDevice, st);
   hipMemcpyAsync(W.ent_fl0, t_ent + (E + 1), (size_t)(E + 1) * 4, hipMemcpyHostToDevice, st);
@@ -973,7 +982,7 @@ static int batch_core(Ctx *c, int method, const int *idx, uint32_t E, const uint
   job.nbuf = total; job.tok_lo = 0; job.tok_hi = (uint32_t)total; job.final = true; job.entry_known = true; job.entry = ExitState{0, SYNC_F};
   job.dst_atoms = W.ea_atoms + LB_CAP; job.dst_apos = W.ea_apos + LB_CAP; job.apos_bias = 0; job.cap_atoms = W.cap_atoms; job.segend = W.segend;
   ShardResult res;
-  rc = lz_shard(c, level, job, &res);
+  int rc = lz_shard(c, level, job, &res);
   if (rc) return rc == -2 ? ZADA_E_NOMEM : rc;
   R.T = res.ntok; R.T_total = res.ntok; R.G = 0; R.n_lb = R.n_la = 0; R.nflush = (uint32_t)nfs; R.foff = 0; R.j0 = 0; R.placed = true;
   // ---- entropy stage, every entry a stream of its own
@@ -984,12 +993,42 @@ static int batch_core(Ctx *c, int method, const int *idx, uint32_t E, const uint
   rc = entropy_choose(c);
   if (!rc) rc = entropy_emit(c, nullptr);
   if (rc) return rc;
-  // ---- results: sizes, places, CRCs; then the streams
-  const uint64_t obytes = (R.co.total_bits + 7) / 8;
-  uint32_t *h_bytes = c->btab, *h_base = c->btab + (E + 1), *h_crc = c->btab + 2 * (E + 1);
-  hipMemcpyAsync(h_bytes, W.ent_bytes, (size_t)E * 4, hipMemcpyDeviceToHost, st);
-  hipMemcpyAsync(h_base, W.ent_base, (size_t)E * 4, hipMemcpyDeviceToHost, st);
-  hipMemcpyAsync(h_crc, W.ent_crc, (size_t)E * 4, hipMemcpyDeviceToHost, st);
+  // ---- results: sizes, places, CRCs
+  *obytes = (R.co.total_bits + 7) / 8;
+  *h_bytes = c->btab; *h_base = c->btab + (E + 1); *h_crc = c->btab + 2 * (E + 1);
+  hipMemcpyAsync(*h_bytes, W.ent_bytes, (size_t)E * 4, hipMemcpyDeviceToHost, st);
+  hipMemcpyAsync(*h_base, W.ent_base, (size_t)E * 4, hipMemcpyDeviceToHost, st);
+  hipMemcpyAsync(*h_crc, W.ent_crc, (size_t)E * 4, hipMemcpyDeviceToHost, st);
+  return 0;
+}
+
+// entries idx[0 .. E) of the caller's arrays through one launch sequence: packed by host threads into a pinned buffer, copied up, compressed
+// (batch_launch), copied back and unpacked
+static int batch_core(Ctx *c, int method, const int *idx, uint32_t E, const uint8_t *const *in, const uint64_t *n, uint8_t *const *out,
+                      const uint64_t *cap, uint64_t *out_len, uint32_t *crc, int *rc_out) {
+  Workspace &W = c->ws;
+  hipStream_t st = c->stream;
+  // ---- layout
+  std::vector<uint64_t> ln(E);
+  std::vector<uint32_t> reg(E);
+  for (uint32_t e = 0; e < E; e++) { ln[e] = n[idx[e]]; reg[e] = crc ? crc[idx[e]] : 0xFFFFFFFFu; }
+  BatchLayout L;
+  int rc = batch_layout(c, E, ln.data(), reg.data(), L);
+  const uint64_t total = L.total;
+  if (!rc) rc = grow_pinned((void **)&c->bstage, &c->cap_bstage, total + total / 8 + (1u << 20));
+  if (rc) return rc;
+  // ---- pack the entries and the tables (pinned), one copy each
+  parallel_entries(E, total, [&](uint32_t e) {
+    if (L.len[e]) memcpy(c->bstage + L.start[e], in[idx[e]], L.len[e]);
+    batch_segends(c, L, e);
+  });
+  c->tbegin(); c->tmark("begin");
+  hipMemcpyAsync(W.in, c->bstage, total, hipMemcpyHostToDevice, st);
+  uint64_t obytes = 0;
+  uint32_t *h_bytes, *h_base, *h_crc;
+  rc = batch_launch(c, method, L, &obytes, &h_bytes, &h_base, &h_crc);
+  if (rc) return rc;
+  // ---- then the streams
   if (obytes) hipMemcpyAsync(c->bstage, W.out, obytes, hipMemcpyDeviceToHost, st);
   if (hip_check(c, hipStreamSynchronize(st), "batch out")) return ZADA_E_HIP_;
   c->tmark("end"); c->tend();
@@ -1026,6 +1065,7 @@ static void ctx_release(zada_ctx *z) {
   bunzip2_destroy(&z->c);
   unlzma_destroy(&z->c);
   unzip_destroy(&z->c);
+  zip_destroy(&z->c);
   lzma_free(&z->c);
   free_workspace(&z->c);
   for (hipEvent_t e : z->c.ev_pool) hipEventDestroy(e);
@@ -1916,11 +1956,11 @@ int zada_crc32_device(zada_ctx *z, const void *d_in, uint64_t n, uint32_t *raw) 
 }
 uint64_t zada_bz2_last_blocks(zada_ctx *z, uint64_t *dst, uint64_t cap_items) { return z ? bz2_last_blocks(&z->c, dst, cap_items) : 0; }
 
-int zada_deflate_device(zada_ctx *z, int method, const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len,
-                        uint32_t *crc_inout) {
-  int rc = prepare(z);
-  if (rc) return rc;
-  Ctx *c = &z->c;
+}  // extern "C"
+namespace zada {
+// one stream from device memory into device memory (zada_deflate_device; a large entry, or a group of one, of zada_zip_device)
+int deflate_device_one(Ctx *c, int method, const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout) {
+  int rc;
   if (n > ((uint64_t)c->knob_span_mib << 20) && ((uintptr_t)d_in & 15) == 0) {
     uint64_t ol = 0;
     rc = finish_call(c, deflate_spans(c, method, (const uint8_t *)d_in, nullptr, n, (uint8_t *)d_out, nullptr, cap, &ol, crc_inout, nullptr, nullptr));
@@ -1939,11 +1979,20 @@ int zada_deflate_device(zada_ctx *z, int method, const void *d_in, uint64_t n, v
   if (rc < 0) return rc;
   if (out_len) *out_len = ol;
   if (rc == ZADA_OK) {
-    if (ol > cap) { c->err = "output buffer too small"; return ZADA_E_INVALID; }
+    if (ol > cap) { c->err = ERR_OUTPUT_TOO_SMALL; return ZADA_E_INVALID; }
     hipMemcpyAsync(d_out, c->ws.out, ol, hipMemcpyDeviceToDevice, c->stream);
     if (hip_check(c, hipStreamSynchronize(c->stream), "copy out")) return ZADA_E_HIP;
   }
   return rc;
+}
+}  // namespace zada
+extern "C" {
+
+int zada_deflate_device(zada_ctx *z, int method, const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len,
+                        uint32_t *crc_inout) {
+  int rc = prepare(z);
+  if (rc) return rc;
+  return deflate_device_one(&z->c, method, d_in, n, d_out, cap, out_len, crc_inout);
 }
 
 // ---- one stream over several contexts (GPUs): see "Ranges" above and INTEGRATION.md ----

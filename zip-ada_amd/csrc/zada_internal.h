@@ -266,6 +266,7 @@ struct Ctx {
   void *bzd = nullptr;                               // BZip2 reader state (zada_bunzip2.hip), made on first use
   void *ulz = nullptr;                               // LZMA reader state (zada_unlzma.hip), made on first use
   void *uz = nullptr;                                // archive reader state (zada_unzip.hip), made on first use
+  void *zw = nullptr;                                // archive writer state (zada_zip.hip), made on first use
   int knob_unzip_piece = 14;                         // "unzip_piece" (test knob): log2 of the bytes of one piece of a stored entry (8 .. 14)
   void *lz_tab = nullptr; size_t cap_lz_tab = 0;     // LZMA (zada_lzma.hip): job table + results
   void *lz_save = nullptr; size_t cap_lz_save = 0;   // ... the coder's state between the launches of one stream
@@ -333,6 +334,9 @@ struct Ctx {
 
 extern thread_local std::string *tls_err;          // error text of a worker thread (see hip_check)
 int hip_check(Ctx *c, hipError_t e, const char *what);
+// the text of deflate_spans and deflate_device_one when the stream is longer than the capacity they got (zada_zip_device tells this refusal from
+// every other ZADA_E_INVALID by it)
+constexpr const char *ERR_OUTPUT_TOO_SMALL = "output buffer too small";
 void bz2_destroy(Ctx *c);
 // ZipCrypto (zada_crypt.hip): CRC_Crypto.Encode over device memory, keys in and out
 void crypt_destroy(Ctx *c);
@@ -341,6 +345,10 @@ int inflate_crc_entries(Ctx *c, uint32_t E, const uint64_t *out, const uint64_t 
 void bunzip2_destroy(Ctx *c);                       // the BZip2 reader (zada_bunzip2.hip)
 void unlzma_destroy(Ctx *c);                        // the LZMA reader (zada_unlzma.hip)
 void unzip_destroy(Ctx *c);                         // the archive reader (zada_unzip.hip)
+void zip_destroy(Ctx *c);                           // the archive writer (zada_zip.hip)
+// ... its stored entries for the archive writer: entry k's len [k] > 0 bytes at device address src [k] copied to dst [k] and summed in one pass, in
+// pieces of 16 KiB (k_uz_store / k_uz_fold); crc [k] is in/out, the running register
+int unzip_store_entries(Ctx *c, uint32_t ns, const uint64_t *src, const uint64_t *dst, const uint64_t *len, uint32_t *crc);
 // The readers' runners (inf_run, bzd_run, ulz_run) on jobs whose streams and outputs are device addresses, for zada_unzip_device: one call takes
 // every entry of a method through the launches of the method's batch call.  res [k].crc is in/out (the running register), rc ZADA_OK or ZADA_E_DATA;
 // the first entry that fails is described in the context's error text under its number `index`, unless *described says one already is.
@@ -427,6 +435,13 @@ constexpr int RICH_LEVEL = 11;
 int rich_shard(Ctx *c, const ShardJob &job, ShardResult *res);
 
 int ensure_batch_workspace(Ctx *c, uint64_t entries, uint64_t fslots, uint64_t segs);
+// A batch of small entries (zada_api.hip): the layout and tables from the lengths, then the launch sequence on entries that lie in their slots of
+// W.in -- shared by zada_deflate_batch (host pointers: packed and copied up) and zada_zip_device (device pointers: gathered by k_zw_pack).
+struct BatchLayout { uint32_t E = 0, nseg = 0; uint64_t total = 0, nfs = 0; std::vector<uint32_t> start, len; };   // start / len: E + 1 values, the entry's offset in W.in and its bytes
+int batch_layout(Ctx *c, uint32_t E, const uint64_t *n, const uint32_t *crc_in, BatchLayout &L);
+void batch_segends_all(Ctx *c, const BatchLayout &L);
+int batch_launch(Ctx *c, int method, const BatchLayout &L, uint64_t *obytes, uint32_t **h_bytes, uint32_t **h_base, uint32_t **h_crc);
+int deflate_device_one(Ctx *c, int method, const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout);
 int batch_geometry(Ctx *c, uint32_t E, const uint32_t *d_total_atoms);
 int entropy_analyze(Ctx *c);
 int entropy_choose(Ctx *c);

@@ -284,6 +284,65 @@ struct UzCarve {
 
 #define UZ_HIP(call, what) do { if (hip_check(c, (call), what)) return ZADA_E_HIP_; } while (0)
 
+// the stored entries se [0 .. ns) (len slen [s] > 0; first / npieces are filled here) through k_uz_store and k_uz_fold, in pieces of 2 ** plog bytes;
+// crc [s]: the registers behind them.  zip: the archive writer calls (its errors name that entry point).
+static int uz_store_run(Ctx *c, UzState *S, std::vector<UzStoreEnt> &se, const std::vector<uint64_t> &slen, std::vector<uint32_t> &crc, uint32_t plog, bool zip) {
+  hipStream_t st = c->stream;
+  const uint32_t ns = (uint32_t)se.size();
+  std::vector<uint32_t> sid(ns), fold;
+  for (uint32_t s = 0; s < ns; s++) sid[s] = s;
+  uint64_t total = 0;
+  for (uint32_t s = 0; s < ns; s++) total += uz_piece_count(slen[s], plog);
+  if (total >= (1ull << 31)) {
+    c->err = zip ? "zada_zip_device: more pieces of stored entries than 2 ** 31" : "zada_unzip_device: more pieces of stored entries than 2 ** 31";
+    return ZADA_E_TOO_LARGE;
+  }
+  std::vector<UzPiece> pieces;
+  std::vector<uint64_t> first;
+  uz_pieces(slen.data(), sid.data(), ns, plog, pieces, first);
+  for (uint32_t s = 0; s < ns; s++) {
+    se[s].first = (uint32_t)first[s]; se[s].npieces = (uint32_t)(first[s + 1] - first[s]);
+    if (se[s].npieces > 1) fold.push_back(s);
+  }
+  const uint32_t NP = (uint32_t)pieces.size(), nf = (uint32_t)fold.size();
+  UzCarve pc;
+  const uint64_t p_ent = pc.take((uint64_t)ns * sizeof(UzStoreEnt)), p_pc = pc.take((uint64_t)NP * sizeof(UzPiece)), p_fold = pc.take((uint64_t)nf * 4),
+                 p_raw = pc.take((uint64_t)NP * 4), p_crc = pc.take((uint64_t)ns * 4);
+  const int rc = uz_grow(c, S->ptab, pc.at, zip ? "hipMalloc (zip piece tables)" : "hipMalloc (unzip piece tables)");
+  if (rc) return rc;
+  uint8_t *T = S->ptab.p;
+  hipMemcpyAsync(T + p_ent, se.data(), (size_t)ns * sizeof(UzStoreEnt), hipMemcpyHostToDevice, st);
+  hipMemcpyAsync(T + p_pc, pieces.data(), (size_t)NP * sizeof(UzPiece), hipMemcpyHostToDevice, st);
+  if (nf) hipMemcpyAsync(T + p_fold, fold.data(), (size_t)nf * 4, hipMemcpyHostToDevice, st);
+  c->tmark("unzip:store begin");
+  hipLaunchKernelGGL(k_uz_store, dim3(NP), dim3(UZ_WAVE), 0, st, (const UzPiece *)(T + p_pc), (const UzStoreEnt *)(T + p_ent), (const UzOps *)S->d_ops, (uint32_t *)(T + p_raw),
+                     (uint32_t *)(T + p_crc));
+  c->tmark("unzip:k_uz_store");
+  if (nf) {
+    hipLaunchKernelGGL(k_uz_fold, dim3(nf), dim3(UZ_WAVE), 0, st, (const UzStoreEnt *)(T + p_ent), (const uint32_t *)(T + p_fold), (const uint32_t *)(T + p_raw), (const UzOps *)S->d_ops,
+                       plog, (uint32_t *)(T + p_crc));
+    c->tmark("unzip:k_uz_fold");
+  }
+  crc.resize(ns);
+  hipMemcpyAsync(crc.data(), T + p_crc, (size_t)ns * 4, hipMemcpyDeviceToHost, st);
+  UZ_HIP(hipGetLastError(), zip ? "zip store launch" : "unzip store launch");
+  UZ_HIP(hipStreamSynchronize(st), zip ? "zip store" : "unzip store");
+  return 0;
+}
+int unzip_store_entries(Ctx *c, uint32_t ns, const uint64_t *src, const uint64_t *dst, const uint64_t *len, uint32_t *crc) {
+  if (!ns) return 0;
+  UzState *S = uz_state(c);
+  if (!S) { c->err = "zip: no memory for the tables"; return ZADA_E_NOMEM; }
+  std::vector<UzStoreEnt> se(ns);
+  std::vector<uint64_t> slen(len, len + ns);
+  for (uint32_t s = 0; s < ns; s++) se[s] = UzStoreEnt{src[s], dst[s], len[s], crc[s], 0, 0, 0};
+  std::vector<uint32_t> out;
+  const int rc = uz_store_run(c, S, se, slen, out, UZ_PIECE_DEFAULT, true);      // (pieces of 16 KiB, as zw_groups counts them: not the reader's test knob)
+  if (rc) return rc;
+  for (uint32_t s = 0; s < ns; s++) crc[s] = out[s];
+  return 0;
+}
+
 // entries idx [0 .. n) of the table, entry idx [k]'s output at device address out [k]
 static int uz_group(Ctx *c, UzState *S, const uint8_t *archive, const zada_unzip_entry *ent, zada_unzip_result *res, const std::vector<int> &idx,
                     const std::vector<uint64_t> &out, const uint32_t *keys0, bool *described) {
@@ -386,53 +445,21 @@ static int uz_group(Ctx *c, UzState *S, const uint8_t *archive, const zada_unzip
   // the stored entries
   std::vector<UzStoreEnt> se;
   std::vector<uint64_t> slen;
-  std::vector<uint32_t> sid, sk, fold;
+  std::vector<uint32_t> sk;
   for (uint32_t k = 0; k < n; k++) {
     const zada_unzip_entry &e = ent[idx[k]];
     if (done[k] || e.method != 0) continue;
     const uint64_t len = uz_payload(e);
     res[idx[k]].out_len = len; res[idx[k]].in_used = e.n_in;
     if (len == 0) continue;
-    sid.push_back((uint32_t)se.size()); slen.push_back(len); sk.push_back(k);
+    slen.push_back(len); sk.push_back(k);
     se.push_back(UzStoreEnt{src[k], out[k], len, res[idx[k]].crc, 0, 0, uz_encrypted(e) ? 1u : 0u});
   }
-  const uint32_t ns = (uint32_t)se.size();
-  if (ns) {
-    const uint32_t plog = (uint32_t)c->knob_unzip_piece;
-    uint64_t total = 0;
-    for (uint32_t s = 0; s < ns; s++) total += uz_piece_count(slen[s], plog);
-    if (total >= (1ull << 31)) { c->err = "zada_unzip_device: more pieces of stored entries than 2 ** 31"; return ZADA_E_TOO_LARGE; }
-    std::vector<UzPiece> pieces;
-    std::vector<uint64_t> first;
-    uz_pieces(slen.data(), sid.data(), ns, plog, pieces, first);
-    for (uint32_t s = 0; s < ns; s++) {
-      se[s].first = (uint32_t)first[s]; se[s].npieces = (uint32_t)(first[s + 1] - first[s]);
-      if (se[s].npieces > 1) fold.push_back(s);
-    }
-    const uint32_t NP = (uint32_t)pieces.size(), nf = (uint32_t)fold.size();
-    UzCarve pc;
-    const uint64_t p_ent = pc.take((uint64_t)ns * sizeof(UzStoreEnt)), p_pc = pc.take((uint64_t)NP * sizeof(UzPiece)), p_fold = pc.take((uint64_t)nf * 4),
-                   p_raw = pc.take((uint64_t)NP * 4), p_crc = pc.take((uint64_t)ns * 4);
-    const int rc = uz_grow(c, S->ptab, pc.at, "hipMalloc (unzip piece tables)");
+  if (!se.empty()) {
+    std::vector<uint32_t> crc;
+    const int rc = uz_store_run(c, S, se, slen, crc, (uint32_t)c->knob_unzip_piece, false);
     if (rc) return rc;
-    uint8_t *T = S->ptab.p;
-    hipMemcpyAsync(T + p_ent, se.data(), (size_t)ns * sizeof(UzStoreEnt), hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(T + p_pc, pieces.data(), (size_t)NP * sizeof(UzPiece), hipMemcpyHostToDevice, st);
-    if (nf) hipMemcpyAsync(T + p_fold, fold.data(), (size_t)nf * 4, hipMemcpyHostToDevice, st);
-    c->tmark("unzip:store begin");
-    hipLaunchKernelGGL(k_uz_store, dim3(NP), dim3(UZ_WAVE), 0, st, (const UzPiece *)(T + p_pc), (const UzStoreEnt *)(T + p_ent), (const UzOps *)S->d_ops, (uint32_t *)(T + p_raw),
-                       (uint32_t *)(T + p_crc));
-    c->tmark("unzip:k_uz_store");
-    if (nf) {
-      hipLaunchKernelGGL(k_uz_fold, dim3(nf), dim3(UZ_WAVE), 0, st, (const UzStoreEnt *)(T + p_ent), (const uint32_t *)(T + p_fold), (const uint32_t *)(T + p_raw), (const UzOps *)S->d_ops,
-                         plog, (uint32_t *)(T + p_crc));
-      c->tmark("unzip:k_uz_fold");
-    }
-    std::vector<uint32_t> crc(ns);
-    hipMemcpyAsync(crc.data(), T + p_crc, (size_t)ns * 4, hipMemcpyDeviceToHost, st);
-    UZ_HIP(hipGetLastError(), "unzip store launch");
-    UZ_HIP(hipStreamSynchronize(st), "unzip store");
-    for (uint32_t s = 0; s < ns; s++) res[idx[sk[s]]].crc = crc[s];
+    for (uint32_t s = 0; s < (uint32_t)se.size(); s++) res[idx[sk[s]]].crc = crc[s];
   }
   return 0;
 }
