@@ -393,6 +393,34 @@ typedef struct { int32_t rc; uint16_t zip_type; uint16_t pad; uint32_t crc; uint
 uint64_t zada_zip_bound(int count, const zada_zip_entry *ent, uint64_t archive_base);
 int zada_zip_device(zada_ctx *ctx, int method, int count, const zada_zip_entry *ent, void *d_archive, uint64_t cap, uint64_t archive_base,
                     uint64_t *archive_len, zada_zip_result *res);
+/* The writer with every method Zip.Create takes but Shrink and Reduce, and with a password.  zada_zip_device_ex is zada_zip_device -- the same
+ * entries, results, checks and texts (under its own name), the same bytes for Store and the Deflate methods without a password -- and besides:
+ *   method   : also BZip2_1 .. _3 (zip type 12), LZMA_0 .. LZMA_for_AU (zip type 14, the headers carry LZMA_EOS_Flag_Bit 0x0002) and
+ *              Preselection_1 / _2: per entry zada_preselect (method, zada_guess_type_from_name (name), 1, n), the name being the bytes of the table
+ *              (copied: they are not NUL-terminated there); res [i].zip_type tells the outcome.  Shrink_1, Reduce_1 .. 4 and anything out of range
+ *              stay ZADA_E_INVALID with a text that names them.
+ *   crypt    : NULL, or the password of every entry (HOST memory; one byte per Character'Pos as for zada_crypt_init_keys) and random11 = count x 11
+ *              bytes, the eleven random bytes of every entry's encryption header in the order of the table -- the library draws no random numbers, as
+ *              with zada_compress_data_pw.  The headers carry Encryption_Flag_Bit 0x0001, the payload is the 12-byte encryption header (made on the
+ *              host from random11 and the entry's final CRC-32: zada_crypt_header) and the encoded stream -- or the encoded input where the entry
+ *              fell back to Store --, and csize counts the 12 bytes.  crypt with a null random11 (count > 0), or a null password with pw_len > 0, is
+ *              ZADA_E_INVALID.  So is, with its index, an entry of 4 GiB - 11 .. 4 GiB - 1 bytes: its local header has no Zip64 extension (the form
+ *              is decided on the uncompressed size) and the compressed size with the 12 bytes does not fit its four bytes; Zip.Create cannot
+ *              write such an entry either.
+ * The archive is byte for byte what ZipCreate.add_streams + finish write for the same inputs on host bytes.  Consecutive entries of up to 4 MiB form
+ * groups bounded by "batch_mib" (at most 1 GiB of slots), by "bz_batch_mib" for the BZip2 entries among them and by "lzma_lit_mib" for the literal
+ * tables in HBM; a BZip2 entry longer than one block (zada_bzip2_batch's rule), any entry above 4 MiB and a group of one run alone through the
+ * single-stream path of their method, the stream written to its place and, with a password, encoded there (zada_crypt_encode_device).  In a group
+ * every distinct method runs ONE launch sequence -- that of zada_deflate_batch, zada_bzip2_batch or zada_lzma_batch on entries gathered from
+ * their addresses --, in ascending method order; with several methods the streams that beat their input wait in a holding buffer of the context (at
+ * most the group's input bytes) while the next method reuses the workspace, and the group is placed once.  With a password the payloads are placed
+ * by an out-of-place Encode, one wave per entry: it reads the stream -- or the stored entry's own bytes -- and writes the cipher text to its place
+ * at whatever alignment.  An LZMA_3* entry the coder refuses ends the call with ZADA_E_REFERENCE and the entry's index in zada_last_error.
+ * zada_zip_bound_ex is the bound for the call (encrypted != 0: 12 bytes more per entry); no entry byte crosses the host and inputs are never written. */
+typedef struct { const uint8_t *password; uint64_t pw_len; const uint8_t *random11; } zada_zip_crypt;
+uint64_t zada_zip_bound_ex(int count, const zada_zip_entry *ent, uint64_t archive_base, int encrypted);
+int zada_zip_device_ex(zada_ctx *ctx, int method, int count, const zada_zip_entry *ent, void *d_archive, uint64_t cap, uint64_t archive_base,
+                       const zada_zip_crypt *crypt, uint64_t *archive_len, zada_zip_result *res);
 
 /* ---- One stream over several contexts (GPUs) -------------------------------------------------------------------
  * The reference compresses an entry as ONE sequential stream (a 32 KiB window, a lazy-match state machine, a flush of the

@@ -219,6 +219,10 @@ def load_library():
         L.zada_zip_bound.restype = u64
         L.zada_zip_bound.argtypes = [i32, vp, u64]
         L.zada_zip_device.argtypes = [vp, i32, i32, vp, vp, u64, u64, u64p, vp]
+    if hasattr(L, "zada_zip_device_ex"):             # (likewise: every method, and passwords)
+        L.zada_zip_bound_ex.restype = u64
+        L.zada_zip_bound_ex.argtypes = [i32, vp, u64, i32]
+        L.zada_zip_device_ex.argtypes = [vp, i32, i32, vp, vp, u64, u64, vp, u64p, vp]
     L.zada_bz2_last_blocks.restype = ctypes.c_uint64
     L.zada_bz2_last_blocks.argtypes = [vp, vp, u64]
     L.zada_crc32_combine.restype = ctypes.c_uint32
@@ -914,6 +918,38 @@ class Encoder:
             self._err(rc, "zada_zip_device")
         return alen.value, res
 
+    def zip_bound_ex(self, entries, archive_base=0, encrypted=False):
+        """zada_zip_bound_ex: the bound for zip_device_ex (encrypted: 12 bytes of encryption header more per entry)."""
+        import numpy as np
+        ent = np.ascontiguousarray(entries, dtype=self.zip_dtypes()[0])
+        return int(self.lib.zada_zip_bound_ex(len(ent), ent.ctypes.data if len(ent) else None, archive_base, 1 if encrypted else 0))
+
+    def zip_device_ex(self, entries, d_archive_ptr, cap, method, archive_base=0, password=None, headers=None):
+        """zada_zip_device_ex: zip_device with every method Zip.Create takes but Shrink and Reduce, and with a password (bytes, or str taken as Latin-1).
+        headers: eleven bytes per entry for the encryption headers -- one bytes object, or a list of them --, os.urandom by default.  An LZMA_3* entry
+        the coder refuses raises ReferenceDefect."""
+        import numpy as np
+        dt_e, dt_r = self.zip_dtypes()
+        ent = np.ascontiguousarray(entries, dtype=dt_e)
+        res = np.zeros(len(ent), dtype=dt_r)
+        alen = ctypes.c_uint64(0)
+        crypt = None
+        if password is not None:
+            pw = _password(password)
+            if headers is None:
+                headers = os.urandom(11 * len(ent))
+            elif not isinstance(headers, (bytes, bytearray)):
+                headers = b"".join(bytes(h) for h in headers)
+            if len(headers) != 11 * len(ent):
+                raise ValueError("zip_device_ex: %d header bytes for %d entries" % (len(headers), len(ent)))
+            keep = (ctypes.create_string_buffer(pw, len(pw)), ctypes.create_string_buffer(bytes(headers), max(len(headers), 1)))
+            crypt = (ctypes.c_uint64 * 3)(ctypes.addressof(keep[0]), len(pw), ctypes.addressof(keep[1]))
+        rc = self.lib.zada_zip_device_ex(self.ctx, method, len(ent), ent.ctypes.data if len(ent) else None, d_archive_ptr, cap, archive_base,
+                                         ctypes.addressof(crypt) if crypt is not None else None, ctypes.byref(alen), res.ctypes.data if len(ent) else None)
+        if rc != 0:
+            self._err(rc, "zada_zip_device_ex")
+        return alen.value, res
+
     def lz77_tokens(self, data, method=Method.Deflate_3):
         import numpy as np
         n = len(data)
@@ -1131,17 +1167,28 @@ class ZipCreate:
         The view keeps the whole allocation of zada_zip_bound bytes alive -- the inputs' size plus the headers, however small the archive turns out:
         .clone() it to let the rest go.  A name longer than 65 535 bytes is refused by the C call (ZadaError with the entry's index), where
         add_compressed fails in struct.pack."""
+        import torch
+        tab, nms, _blob, dev = self._device_table(names, tensors, file_time, unicode_name, "ZipCreate.write_device")
+        cap = self.enc.zip_bound(tab, self._bias)
+        out = torch.empty(cap, dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        alen, res = self.enc.zip_device(tab, out.data_ptr(), cap, self.method, self._bias)
+        self._device_entries(tab, nms, res, 0x0800 if unicode_name else 0)
+        return out[:alen]
+
+    def _device_table(self, names, tensors, file_time, unicode_name, who):
+        """The table of zada_zip_entry rows of write_device / write_device_ex (and the names' bytes it points into, which the caller keeps alive)."""
         import numpy as np
         import torch
         if self.entries or self.buf:
-            raise ValueError("ZipCreate.write_device: the archive already has entries")
+            raise ValueError("%s: the archive already has entries" % who)
         names, tensors = list(names), list(tensors)
         if len(names) != len(tensors):
-            raise ValueError("ZipCreate.write_device: %d names for %d tensors" % (len(names), len(tensors)))
+            raise ValueError("%s: %d names for %d tensors" % (who, len(names), len(tensors)))
         dev = torch.device("cuda", self.enc.device)
         for t in tensors:
             if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_contiguous() or (t.numel() and t.device != dev):
-                raise ZadaError("ZipCreate.write_device: contiguous torch.uint8 tensors on %s are needed" % dev)
+                raise ZadaError("%s: contiguous torch.uint8 tensors on %s are needed" % (who, dev))
         nms = [nm.replace("\\", "/").encode("utf-8") for nm in names]
         n = len(nms)
         tab = np.zeros(n, dtype=self.enc.zip_dtypes()[0])
@@ -1153,17 +1200,31 @@ class ZipCreate:
         tab["d_data"] = np.fromiter((t.data_ptr() if t.numel() else 0 for t in tensors), np.uint64, n)
         tab["time"] = self.DEFAULT_TIME if file_time is None else file_time
         tab["flags"] = 1 if unicode_name else 0
-        cap = self.enc.zip_bound(tab, self._bias)
-        out = torch.empty(cap, dtype=torch.uint8, device=dev)
-        torch.cuda.current_stream(dev).synchronize()
-        alen, res = self.enc.zip_device(tab, out.data_ptr(), cap, self.method, self._bias)
-        flag = 0x0800 if unicode_name else 0
+        return tab, nms, blob, dev
+
+    def _device_entries(self, tab, nms, res, flag):
         for k, nm in enumerate(nms):
             r = res[k]
             usize = int(tab["n"][k])
+            zt = int(r["zip_type"])
             self._check_size(usize)
-            self.entries.append(dict(name=nm, flag=flag, zip_type=int(r["zip_type"]), time=int(tab["time"][k]), crc=int(r["crc"]), csize=int(r["csize"]), usize=usize,
-                                     offset=int(r["offset"])))
+            self.entries.append(dict(name=nm, flag=flag | (0x0002 if zt == 14 else 0), zip_type=zt, time=int(tab["time"][k]),
+                                     crc=int(r["crc"]), csize=int(r["csize"]), usize=usize, offset=int(r["offset"])))
+
+    def write_device_ex(self, names, tensors, file_time=None, unicode_name=True, password=None, _headers=None):
+        """write_device through zada_zip_device_ex: any method of this ZipCreate but Shrink and Reduce -- BZip2, LZMA, Preselection_1 / _2 by the
+        entries' names and sizes -- and, with a password (bytes, or str taken as Latin-1), encrypted entries; _headers (test hook): eleven bytes per
+        entry.  The archive is the one add_streams + finish write for the same inputs; self.entries is what add_compressed would have recorded,
+        flag bits included.  write_device's rules hold: contiguous torch.uint8 tensors on the encoder's device, empty ones allowed, only on a
+        ZipCreate without entries.  Returns the archive as a view of a tensor of zada_zip_bound_ex bytes."""
+        import torch
+        pw = None if password is None else _password(password)
+        tab, nms, _blob, dev = self._device_table(names, tensors, file_time, unicode_name, "ZipCreate.write_device_ex")
+        cap = self.enc.zip_bound_ex(tab, self._bias, pw is not None)
+        out = torch.empty(cap, dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        alen, res = self.enc.zip_device_ex(tab, out.data_ptr(), cap, self.method, self._bias, password=pw, headers=_headers)
+        self._device_entries(tab, nms, res, (0x0800 if unicode_name else 0) | (0x0001 if pw else 0))
         return out[:alen]
 
     def finish(self):

@@ -1304,19 +1304,9 @@ static int bzip2_core(Ctx *c, int method, const uint8_t *d_in, uint64_t n, uint8
   return rc;
 }
 int zada_bzip2_device(zada_ctx *z, int method, const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout) {
-  int rc = prepare(z);
+  const int rc = prepare(z);
   if (rc) return rc;
-  Ctx *c = &z->c;
-  const uint8_t *src = (const uint8_t *)d_in;
-  if (((uintptr_t)d_in & 15) != 0 && n) {
-    if ((rc = ensure_rin(c, n))) return rc;
-    hipMemcpyAsync(c->ws.rin_own, d_in, n, hipMemcpyDeviceToDevice, c->stream);
-    src = c->ws.rin_own;
-  }
-  uint64_t ol = 0;
-  rc = finish_call(c, bzip2_core(c, method, src, n, (uint8_t *)d_out, cap, &ol, crc_inout, nullptr, nullptr));
-  if (out_len && rc >= 0) *out_len = ol;
-  return rc;
+  return bzip2_device_one(&z->c, method, d_in, n, d_out, cap, out_len, crc_inout);
 }
 int zada_bzip2(zada_ctx *z, int method, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout,
                zada_feedback_fn fb, void *user) {
@@ -1336,33 +1326,22 @@ int zada_bzip2(zada_ctx *z, int method, const uint8_t *in, uint64_t n, uint8_t *
 // entries idx[0 .. E) of the caller's arrays, each short enough for one block, through one launch sequence
 static int bzip2_batch_core(Ctx *c, int method, const int *idx, uint32_t E, const uint8_t *const *in, const uint64_t *n, uint8_t *const *out, const uint64_t *cap,
                             uint64_t *out_len, uint32_t *crc, int *rc_out) {
-  hipStream_t st = c->stream;
-  std::vector<uint64_t> start(E); std::vector<uint32_t> start32(E + 1), len(E + 1), crc_in(E + 1);
-  uint64_t total = 0;
-  for (uint32_t e = 0; e < E; e++) {
-    start[e] = total; start32[e] = (uint32_t)total; len[e] = (uint32_t)n[idx[e]]; crc_in[e] = crc ? crc[idx[e]] : 0xFFFFFFFFu;
-    total += (n[idx[e]] + 63) & ~63ull;
-  }
-  if (total >= (1ull << 32)) return ZADA_E_TOO_LARGE;
-  const uint64_t out_cap = total + total / 4 + 128ull * E + (1u << 20);
-  int rc = ensure_rin(c, total + 64 + 16ull * (E + 1));
+  std::vector<uint64_t> ln(E);
+  std::vector<uint32_t> reg(E);
+  for (uint32_t e = 0; e < E; e++) { ln[e] = n[idx[e]]; reg[e] = crc ? crc[idx[e]] : 0xFFFFFFFFu; }
+  DevBatch D;
+  int rc = bzip2_batch_layout(c, method, E, ln.data(), reg.data(), D);
+  const uint64_t total = D.total, out_cap = total + total / 4 + 128ull * E + (1u << 20);
   if (!rc) rc = grow_pinned((void **)&c->bstage, &c->cap_bstage, (total > out_cap ? total : out_cap) + 64);
   if (rc) return rc;
-  parallel_entries(E, total, [&](uint32_t e) { if (len[e]) memcpy(c->bstage + start[e], in[idx[e]], len[e]); });
+  parallel_entries(E, total, [&](uint32_t e) { if (D.len[e]) memcpy(c->bstage + D.start[e], in[idx[e]], D.len[e]); });
   c->tbegin(); c->tmark("bz:begin");
-  uint8_t *d_arena = c->ws.rin_own;
-  uint32_t *d_tab = (uint32_t *)(d_arena + ((total + 63) & ~63ull));          // starts, lengths, CRC registers behind the entries
-  hipMemcpyAsync(d_arena, c->bstage, total, hipMemcpyHostToDevice, st);
-  hipMemcpyAsync(d_tab, start32.data(), 4ull * E, hipMemcpyHostToDevice, st);
-  hipMemcpyAsync(d_tab + E, len.data(), 4ull * E, hipMemcpyHostToDevice, st);
-  hipMemcpyAsync(d_tab + 2 * E, crc_in.data(), 4ull * E, hipMemcpyHostToDevice, st);
-  hipLaunchKernelGGL(k_batch_crc, dim3(E), dim3(64), 0, st, E, d_arena, d_tab, d_tab + E, d_tab + 2 * E);
-  hipMemcpyAsync(crc_in.data(), d_tab + 2 * E, 4ull * E, hipMemcpyDeviceToHost, st);
-  if (hip_check(c, hipStreamSynchronize(st), "bzip2 batch in")) return ZADA_E_HIP;
-  std::vector<uint64_t> off(E), bytes(E);
-  rc = bz2_batch_encode(c, method - ZADA_BZIP2_1, d_arena, E, start.data(), len.data(), c->bstage, out_cap, off.data(), bytes.data());
+  hipMemcpyAsync(D.d_in, c->bstage, total, hipMemcpyHostToDevice, c->stream);
+  rc = bzip2_batch_launch(c, method, D, c->bstage, out_cap);
   c->tmark("bz:end"); c->tend();
   if (rc) return rc;
+  const std::vector<uint64_t> &off = D.off, &bytes = D.bytes;
+  const std::vector<uint32_t> &crc_in = D.reg;
   std::atomic<int> bad(0);
   parallel_entries(E, out_cap, [&](uint32_t e) {
     const int i = idx[e];
@@ -1601,10 +1580,13 @@ static int lzma_run(Ctx *c, std::vector<LzmaJob> &jobs, const uint8_t *d_in, uin
   for (uint32_t e = 0; e < E; e++) if (!(res[2 * e + 1] >> 62 & 1) && res[2 * e + 1] != jobs[e].n) { c->err = "LZMA: the coder did not consume the entry"; return ZADA_E_HIP; }
   return 0;
 }
-static bool lzma_refused(Ctx *c, const std::vector<uint64_t> &res, uint32_t e) {
-  if (!(res[2 * (size_t)e + 1] >> 62 & 1)) return false;
+static void lzma_refused_text(Ctx *c) {
   c->err = "LZMA_3: the reference's matcher reports a match that is none on this entry (positions read behind pending bytes no window fill took up, "
            "lz77.adb:1000-1017, 1262-1290): its own stream does not decode to the input";
+}
+static bool lzma_refused(Ctx *c, const std::vector<uint64_t> &res, uint32_t e) {
+  if (!(res[2 * (size_t)e + 1] >> 62 & 1)) return false;
+  lzma_refused_text(c);
   return true;
 }
 static int lzma_tokens(Ctx *c, int level, const uint8_t *d_in, uint64_t n, uint64_t *ntok) {     // IZ_6 / IZ_10, lzma-encoding.adb:118-122
@@ -1660,19 +1642,9 @@ static int lzma_core(Ctx *c, int method, const uint8_t *d_in, uint64_t n, uint8_
   return res[0] >= n ? ZADA_INEFFICIENT : ZADA_OK;                   // zip-compress.adb:479-486
 }
 int zada_lzma_device(zada_ctx *z, int method, const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout) {
-  int rc = prepare(z);
+  const int rc = prepare(z);
   if (rc) return rc;
-  Ctx *c = &z->c;
-  const uint8_t *src = (const uint8_t *)d_in;
-  if (((uintptr_t)d_in & 15) != 0 && n) {
-    if ((rc = ensure_rin(c, n))) return rc;
-    hipMemcpyAsync(c->ws.rin_own, d_in, n, hipMemcpyDeviceToDevice, c->stream);
-    src = c->ws.rin_own;
-  }
-  uint64_t ol = 0;
-  rc = finish_call(c, lzma_core(c, method, src, n, (uint8_t *)d_out, cap, &ol, crc_inout, nullptr, nullptr));
-  if (out_len && rc >= 0) *out_len = ol;
-  return rc;
+  return lzma_device_one(&z->c, method, d_in, n, d_out, cap, out_len, crc_inout);
 }
 int zada_lzma(zada_ctx *z, int method, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout,
               zada_feedback_fn fb, void *user) {
@@ -1770,141 +1742,40 @@ int zada_lzma_match_sets(zada_ctx *z, const uint8_t *in, uint64_t n, uint8_t *cn
   return 0;
 }
 // Many entries in one call: every entry is a stream of ONE launch of k_lzma_encode -- the only parallelism LZMA's chain of
-// adaptive probabilities leaves (see zada_lzma.hip).  This one: Level_0 and Level_3 (no tokens from the LZ stage).
+// adaptive probabilities leaves (see zada_lzma.hip).  Packed by host threads into a pinned buffer, copied up, coded (lzma_batch_layout /
+// lzma_batch_launch below: 64-byte slots for Level_0 and Level_3, the LZ stage's 32 KiB slots for Level_1 and Level_2), copied back and unpacked.
 static int lzma_batch_core(Ctx *c, int method, const int *idx, uint32_t E, const uint8_t *const *in, const uint64_t *n, uint8_t *const *out, const uint64_t *cap,
                            uint64_t *out_len, uint32_t *crc, int *rc_out) {
   hipStream_t st = c->stream;
-  std::vector<uint64_t> start(E), ostart(E); std::vector<uint32_t> start32(E + 1), len(E + 1), crc_in(E + 1);
-  uint64_t total = 0, ototal = 0;
-  for (uint32_t e = 0; e < E; e++) {
-    start[e] = total; start32[e] = (uint32_t)total; len[e] = (uint32_t)n[idx[e]]; crc_in[e] = crc ? crc[idx[e]] : 0xFFFFFFFFu;
-    total += ((n[idx[e]] ? n[idx[e]] : 1) + 63) & ~63ull;                        // (64-byte slots: Level_0 / Level_3 never see the LZ stage)
-    ostart[e] = ototal; ototal += (n[idx[e]] + n[idx[e]] / 8 + 128 + 63) & ~63ull;
-  }
-  if (total >= (1ull << 32)) return ZADA_E_TOO_LARGE;
-  int rc = ensure_rin(c, total + ototal + 64 + 16ull * (E + 1));
+  std::vector<uint64_t> ln(E);
+  std::vector<uint32_t> reg(E);
+  for (uint32_t e = 0; e < E; e++) { ln[e] = n[idx[e]]; reg[e] = crc ? crc[idx[e]] : 0xFFFFFFFFu; }
+  DevBatch D;
+  int rc = lzma_batch_layout(c, method, E, ln.data(), reg.data(), D);
+  const uint64_t total = D.total, ototal = D.ototal;
   if (!rc) rc = grow_pinned((void **)&c->bstage, &c->cap_bstage, (total > ototal ? total : ototal) + 64);
   if (rc) return rc;
-  parallel_entries(E, total, [&](uint32_t e) { if (len[e]) memcpy(c->bstage + start[e], in[idx[e]], len[e]); });
+  parallel_entries(E, total, [&](uint32_t e) { if (D.len[e]) memcpy(c->bstage + D.start[e], in[idx[e]], D.len[e]); });
   c->tbegin(); c->tmark("lzma:begin");
-  uint8_t *d_arena = c->ws.rin_own, *d_out = d_arena + total;
-  uint32_t *d_tab = (uint32_t *)(d_out + ototal);
-  hipMemcpyAsync(d_arena, c->bstage, total, hipMemcpyHostToDevice, st);
-  hipMemcpyAsync(d_tab, start32.data(), 4ull * E, hipMemcpyHostToDevice, st);
-  hipMemcpyAsync(d_tab + E, len.data(), 4ull * E, hipMemcpyHostToDevice, st);
-  hipMemcpyAsync(d_tab + 2 * E, crc_in.data(), 4ull * E, hipMemcpyHostToDevice, st);
-  hipLaunchKernelGGL(k_batch_crc, dim3(E), dim3(64), 0, st, E, d_arena, d_tab, d_tab + E, d_tab + 2 * E);
-  hipMemcpyAsync(crc_in.data(), d_tab + 2 * E, 4ull * E, hipMemcpyDeviceToHost, st);
-  if (hip_check(c, hipStreamSynchronize(st), "LZMA batch in")) return ZADA_E_HIP;
-  std::vector<LzmaJob> jobs(E);
-  for (uint32_t e = 0; e < E; e++) {
-    LzmaJob &J = jobs[e];
-    memset(&J, 0, sizeof J);
-    J.in_off = start[e]; J.n = len[e]; J.out_off = ostart[e]; J.cap = (len[e] + len[e] / 8 + 128ull); J.zip_prefix = 1;
-    lzma_job_method(J, method);
-  }
-  c->tmark("lzma:tokens");
-  std::vector<uint64_t> res;
-  if ((rc = lzma_run(c, jobs, d_arena, total, nullptr, d_out, res))) return rc;
-  hipMemcpyAsync(c->bstage, d_out, ototal, hipMemcpyDeviceToHost, st);
+  hipMemcpyAsync(D.d_in, c->bstage, total, hipMemcpyHostToDevice, st);
+  if ((rc = lzma_batch_launch(c, method, D))) return rc;
+  hipMemcpyAsync(c->bstage, D.d_out, ototal, hipMemcpyDeviceToHost, st);
   if (hip_check(c, hipStreamSynchronize(st), "LZMA batch out")) return ZADA_E_HIP;
   c->tmark("lzma:end"); c->tend();
   std::atomic<int> bad(0);
   std::atomic<int> refused(0);
   parallel_entries(E, ototal, [&](uint32_t e) {
     const int i = idx[e];
-    const uint64_t bytes = res[2 * e];
+    const uint64_t bytes = D.bytes[e];
     out_len[i] = bytes;
-    if (crc) crc[i] = crc_in[e];
-    if (res[2 * (size_t)e + 1] >> 62 & 1) { rc_out[i] = ZADA_E_REFERENCE; out_len[i] = 0; refused = 1; return; }
+    if (crc) crc[i] = D.reg[e];
+    if (D.refused[e]) { rc_out[i] = ZADA_E_REFERENCE; out_len[i] = 0; refused = 1; return; }
     rc_out[i] = bytes >= n[i] ? ZADA_INEFFICIENT : ZADA_OK;
-    if (bytes <= cap[i] && bytes <= jobs[e].cap) memcpy(out[i], c->bstage + ostart[e], bytes);
+    if (bytes <= cap[i] && bytes <= D.cap[e]) memcpy(out[i], c->bstage + D.off[e], bytes);
     else if (rc_out[i] == ZADA_OK) { rc_out[i] = ZADA_E_INVALID; bad = 1; }
   });
   if (bad) c->err = "output buffer too small";
-  if (refused) for (uint32_t e = 0; e < E; e++) if (lzma_refused(c, res, e)) break;     // (the error text)
-  return 0;
-}
-// Level_1 / Level_2 batches: the tokens of ALL entries from one pass of the LZ stage (the batch layout of batch_core above:
-// 32 KiB slots, the segment table that ends every entry's searches at its own end), then one launch of the coder.
-static int lzma_batch_iz(Ctx *c, int method, const int *idx, uint32_t E, const uint8_t *const *in, const uint64_t *n, uint8_t *const *out, const uint64_t *cap,
-                         uint64_t *out_len, uint32_t *crc, int *rc_out) {
-  const int level = LZMA_PARAM[method - ZADA_LZMA_0].level, iz_level = level == 1 ? 6 : 10;
-  Workspace &W = c->ws;
-  hipStream_t st = c->stream;
-  std::vector<uint32_t> start(E + 1), len(E + 1), crc_in(E + 1);
-  std::vector<uint64_t> ostart(E);
-  uint64_t total = 0, nfs = 0, ototal = 0;
-  for (uint32_t e = 0; e < E; e++) {
-    const uint64_t ln = n[idx[e]], slot = ((ln ? ln : 1) + 32767) & ~32767ull;
-    start[e] = (uint32_t)total; len[e] = (uint32_t)ln; crc_in[e] = crc ? crc[idx[e]] : 0xFFFFFFFFu;
-    total += slot; nfs += ln ? (ln + FLUSH - 1) / FLUSH : 1;
-    ostart[e] = ototal; ototal += (ln + ln / 8 + 128 + 63) & ~63ull;
-  }
-  start[E] = (uint32_t)total; len[E] = 0;
-  if (total >= (1ull << 31)) return ZADA_E_TOO_LARGE;
-  const uint32_t nseg = (uint32_t)(total >> 15);
-  int rc = ensure_lz_workspace(c, total + 4096);
-  if (!rc) rc = ensure_entropy_workspace(c, total, nfs);
-  if (!rc) rc = ensure_batch_workspace(c, E, nfs, nseg);
-  if (!rc) rc = ensure_rin(c, ototal + 64);
-  if (!rc) rc = grow_pinned((void **)&c->bstage, &c->cap_bstage, (total > ototal ? total : ototal) + 64);
-  const uint64_t tabw = (uint64_t)nseg + 3ull * (E + 1) + 64;
-  uint64_t capw = c->cap_btab * 4;
-  if (!rc) { rc = grow_pinned((void **)&c->btab, &capw, tabw * 4); c->cap_btab = capw / 4; }
-  if (rc) return rc;
-  uint32_t *t_seg = c->btab, *t_ent = c->btab + nseg;
-  parallel_entries(E, total, [&](uint32_t e) {
-    if (len[e]) memcpy(c->bstage + start[e], in[idx[e]], len[e]);
-    for (uint32_t s = start[e] >> 15; s < (start[e + 1] >> 15); s++) t_seg[s] = (start[e] + len[e]) | (s == (start[e] >> 15) ? 0x80000000u : 0u);
-  });
-  memcpy(t_ent, start.data(), (E + 1) * 4); memcpy(t_ent + (E + 1), len.data(), (E + 1) * 4); memcpy(t_ent + 2 * (E + 1), crc_in.data(), (E + 1) * 4);
-  c->tbegin(); c->tmark("lzma:begin");
-  hipMemcpyAsync(W.in, c->bstage, total, hipMemcpyHostToDevice, st);
-  hipMemcpyAsync(W.segend, t_seg, (size_t)nseg * 4, hipMemcpyHostToDevice, st);
-  hipMemcpyAsync(W.ent_start, t_ent, (size_t)(E + 1) * 4, hipMemcpyHostToDevice, st);
-  hipMemcpyAsync(W.ent_len, t_ent + (E + 1), (size_t)(E + 1) * 4, hipMemcpyHostToDevice, st);
-  hipMemcpyAsync(W.ent_crc, t_ent + 2 * (E + 1), (size_t)(E + 1) * 4, hipMemcpyHostToDevice, st);
-  {
-    PadArgs pa; pa.in_end = W.in + total; pa.n_in = IN_PAD;
-    for (int l = 0; l < NLEVELS; l++) pa.link_end[l] = W.lprev[l] + (total >= 2 ? total - 2 : 0);
-    hipLaunchKernelGGL(k_pad_init, dim3(1), dim3(256), 0, st, pa);
-  }
-  c->rg = Range();
-  c->last_nblocks = 0; c->demand_rounds = 0; c->parse_rounds = 0;
-  hipLaunchKernelGGL(k_batch_crc, dim3(E), dim3(64), 0, st, E, W.in, W.ent_start, W.ent_len, W.ent_crc);
-  ShardJob job;
-  job.nbuf = total; job.tok_lo = 0; job.tok_hi = (uint32_t)total; job.final = true; job.entry_known = true; job.entry = ExitState{0, SYNC_F};
-  job.dst_atoms = W.ea_atoms + LB_CAP; job.dst_apos = W.ea_apos + LB_CAP; job.apos_bias = 0; job.cap_atoms = W.cap_atoms; job.segend = W.segend;
-  ShardResult sres;
-  rc = lz_shard(c, iz_level, job, &sres);
-  if (rc) return rc == -2 ? ZADA_E_NOMEM : rc;
-  c->tmark("lzma:tokens");
-  std::vector<LzmaJob> jobs(E);
-  for (uint32_t e = 0; e < E; e++) {
-    LzmaJob &J = jobs[e];
-    memset(&J, 0, sizeof J);
-    J.in_off = start[e]; J.n = len[e]; J.out_off = ostart[e]; J.cap = len[e] + len[e] / 8 + 128ull; J.zip_prefix = 1;
-    lzma_job_method(J, method);
-  }
-  std::vector<uint64_t> res;
-  uint8_t *d_out = c->ws.rin_own;
-  if ((rc = lzma_run(c, jobs, W.in, total, W.ea_atoms + LB_CAP, d_out, res, W.ea_apos + LB_CAP, sres.ntok, W.ent_start))) return rc;
-  hipMemcpyAsync(crc_in.data(), W.ent_crc, 4ull * E, hipMemcpyDeviceToHost, st);
-  hipMemcpyAsync(c->bstage, d_out, ototal, hipMemcpyDeviceToHost, st);
-  if (hip_check(c, hipStreamSynchronize(st), "LZMA batch out")) return ZADA_E_HIP;
-  c->tmark("lzma:end"); c->tend();
-  std::atomic<int> bad(0);
-  parallel_entries(E, ototal, [&](uint32_t e) {
-    const int i = idx[e];
-    const uint64_t bytes = res[2 * e];
-    out_len[i] = bytes;
-    if (crc) crc[i] = crc_in[e];
-    rc_out[i] = bytes >= n[i] ? ZADA_INEFFICIENT : ZADA_OK;
-    if (bytes <= cap[i] && bytes <= jobs[e].cap) memcpy(out[i], c->bstage + ostart[e], bytes);
-    else if (rc_out[i] == ZADA_OK) { rc_out[i] = ZADA_E_INVALID; bad = 1; }
-  });
-  if (bad) c->err = "output buffer too small";
+  if (refused) lzma_batch_refused(c, D);                                                // (the error text)
   return 0;
 }
 int zada_lzma_batch(zada_ctx *z, int method, int count, const uint8_t *const *in, const uint64_t *n, uint8_t *const *out, const uint64_t *cap, uint64_t *out_len,
@@ -1920,9 +1791,7 @@ int zada_lzma_batch(zada_ctx *z, int method, int count, const uint8_t *const *in
   const uint64_t lit = lzma_lit_bytes(method), lit_cap = (uint64_t)c->knob_lzma_lit_mib << 20;   // (the HBM literal tables of a group: "lzma_lit_mib")
   auto flush_group = [&]() {
     if (group.empty()) return;
-    const bool iz = level == 1 || level == 2;
-    int r = finish_call(c, iz ? lzma_batch_iz(c, method, group.data(), (uint32_t)group.size(), in, n, out, cap, out_len, crc, rc)
-                              : lzma_batch_core(c, method, group.data(), (uint32_t)group.size(), in, n, out, cap, out_len, crc, rc));
+    int r = finish_call(c, lzma_batch_core(c, method, group.data(), (uint32_t)group.size(), in, n, out, cap, out_len, crc, rc));
     if (r < 0) { for (int i : group) rc[i] = r; worst = r; }
     else { for (int i : group) if (rc[i] < 0) worst = rc[i]; }
     group.clear(); gbytes = 0; glit = 0;
@@ -1984,6 +1853,176 @@ int deflate_device_one(Ctx *c, int method, const void *d_in, uint64_t n, void *d
     if (hip_check(c, hipStreamSynchronize(c->stream), "copy out")) return ZADA_E_HIP;
   }
   return rc;
+}
+int bzip2_device_one(Ctx *c, int method, const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout) {
+  int rc;
+  const uint8_t *src = (const uint8_t *)d_in;
+  if (((uintptr_t)d_in & 15) != 0 && n) {
+    if ((rc = ensure_rin(c, n))) return rc;
+    hipMemcpyAsync(c->ws.rin_own, d_in, n, hipMemcpyDeviceToDevice, c->stream);
+    src = c->ws.rin_own;
+  }
+  uint64_t ol = 0;
+  rc = finish_call(c, bzip2_core(c, method, src, n, (uint8_t *)d_out, cap, &ol, crc_inout, nullptr, nullptr));
+  if (out_len && rc >= 0) *out_len = ol;
+  return rc;
+}
+int lzma_device_one(Ctx *c, int method, const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout) {
+  int rc;
+  const uint8_t *src = (const uint8_t *)d_in;
+  if (((uintptr_t)d_in & 15) != 0 && n) {
+    if ((rc = ensure_rin(c, n))) return rc;
+    hipMemcpyAsync(c->ws.rin_own, d_in, n, hipMemcpyDeviceToDevice, c->stream);
+    src = c->ws.rin_own;
+  }
+  uint64_t ol = 0;
+  rc = finish_call(c, lzma_core(c, method, src, n, (uint8_t *)d_out, cap, &ol, crc_inout, nullptr, nullptr));
+  if (out_len && rc >= 0) *out_len = ol;
+  return rc;
+}
+
+// ---- BZip2 and LZMA batches as layout and launch (zada_internal.h, DevBatch) ----
+// BZip2: entries short enough for one block, on 64-byte slots of rin_own, the tables of k_batch_crc behind them
+int bzip2_batch_layout(Ctx *c, int method, uint32_t E, const uint64_t *n, const uint32_t *crc_in, DevBatch &D) {
+  (void)method;
+  D = DevBatch();
+  D.E = E; D.kind = 0;
+  D.start.resize(E); D.off.resize(E); D.bytes.resize(E); D.len.resize(E + 1); D.reg.resize(E + 1);
+  uint64_t total = 0;
+  for (uint32_t e = 0; e < E; e++) {
+    D.start[e] = total; D.len[e] = (uint32_t)n[e]; D.reg[e] = crc_in ? crc_in[e] : 0xFFFFFFFFu;
+    total += (n[e] + 63) & ~63ull;
+  }
+  D.total = total;
+  if (total >= (1ull << 32)) return ZADA_E_TOO_LARGE;
+  const int rc = ensure_rin(c, total + 64 + 16ull * (E + 1));
+  if (rc) return rc;
+  D.d_in = c->ws.rin_own;
+  return 0;
+}
+int bzip2_batch_launch(Ctx *c, int method, DevBatch &D, uint8_t *h_out, uint64_t h_cap) {
+  hipStream_t st = c->stream;
+  const uint32_t E = D.E;
+  std::vector<uint32_t> start32(E + 1);
+  for (uint32_t e = 0; e < E; e++) start32[e] = (uint32_t)D.start[e];
+  uint8_t *d_arena = D.d_in;
+  uint32_t *d_tab = (uint32_t *)(d_arena + ((D.total + 63) & ~63ull));        // starts, lengths, CRC registers behind the entries
+  hipMemcpyAsync(d_tab, start32.data(), 4ull * E, hipMemcpyHostToDevice, st);
+  hipMemcpyAsync(d_tab + E, D.len.data(), 4ull * E, hipMemcpyHostToDevice, st);
+  hipMemcpyAsync(d_tab + 2 * E, D.reg.data(), 4ull * E, hipMemcpyHostToDevice, st);
+  hipLaunchKernelGGL(k_batch_crc, dim3(E), dim3(64), 0, st, E, d_arena, d_tab, d_tab + E, d_tab + 2 * E);
+  hipMemcpyAsync(D.reg.data(), d_tab + 2 * E, 4ull * E, hipMemcpyDeviceToHost, st);
+  if (hip_check(c, hipStreamSynchronize(st), "bzip2 batch in")) return ZADA_E_HIP;
+  return bz2_batch_encode(c, method - ZADA_BZIP2_1, d_arena, E, D.start.data(), D.len.data(), h_out, h_cap, D.off.data(), D.bytes.data(), &D.d_out);
+}
+// LZMA.  Level_0 / Level_3 never see the LZ stage: 64-byte slots in rin_own, the output slots and k_batch_crc's tables behind them.  Level_1 / Level_2:
+// the tokens of ALL entries from one pass of the LZ stage (the batch layout of batch_layout: 32 KiB slots in the LZ buffer, the segment table that ends
+// every entry's searches at its own end), the output slots in rin_own.
+int lzma_batch_layout(Ctx *c, int method, uint32_t E, const uint64_t *n, const uint32_t *crc_in, DevBatch &D) {
+  const int level = LZMA_PARAM[method - ZADA_LZMA_0].level;
+  const bool iz = level == 1 || level == 2;
+  D = DevBatch();
+  D.E = E; D.kind = iz ? 2 : 1;
+  D.start.resize(E + 1); D.off.resize(E); D.bytes.resize(E); D.cap.resize(E); D.len.resize(E + 1); D.reg.resize(E + 1); D.refused.assign(E, 0);
+  uint64_t total = 0, ototal = 0, nfs = 0;
+  for (uint32_t e = 0; e < E; e++) {
+    const uint64_t ln = n[e];
+    D.start[e] = total; D.len[e] = (uint32_t)ln; D.reg[e] = crc_in ? crc_in[e] : 0xFFFFFFFFu;
+    total += iz ? ((ln ? ln : 1) + 32767) & ~32767ull : ((ln ? ln : 1) + 63) & ~63ull;
+    nfs += ln ? (ln + FLUSH - 1) / FLUSH : 1;
+    D.off[e] = ototal; D.cap[e] = ln + ln / 8 + 128; ototal += (ln + ln / 8 + 128 + 63) & ~63ull;
+  }
+  D.start[E] = total; D.len[E] = 0;
+  D.total = total; D.ototal = ototal; D.nfs = nfs;
+  Workspace &W = c->ws;
+  if (!iz) {
+    if (total >= (1ull << 32)) return ZADA_E_TOO_LARGE;
+    const int rc = ensure_rin(c, total + ototal + 64 + 16ull * (E + 1));
+    if (rc) return rc;
+    D.d_in = W.rin_own; D.d_out = W.rin_own + total;
+    return 0;
+  }
+  if (total >= (1ull << 31)) return ZADA_E_TOO_LARGE;
+  const uint32_t nseg = (uint32_t)(total >> 15);
+  int rc = ensure_lz_workspace(c, total + 4096);
+  if (!rc) rc = ensure_entropy_workspace(c, total, nfs);
+  if (!rc) rc = ensure_batch_workspace(c, E, nfs, nseg);
+  if (!rc) rc = ensure_rin(c, ototal + 64);
+  const uint64_t tabw = (uint64_t)nseg + 3ull * (E + 1) + 64;
+  uint64_t capw = c->cap_btab * 4;
+  if (!rc) { rc = grow_pinned((void **)&c->btab, &capw, tabw * 4); c->cap_btab = capw / 4; }
+  if (rc) return rc;
+  uint32_t *t_seg = c->btab, *t_ent = c->btab + nseg;
+  for (uint32_t e = 0; e < E; e++) {
+    const uint32_t s0 = (uint32_t)(D.start[e] >> 15), s1 = (uint32_t)(D.start[e + 1] >> 15);
+    for (uint32_t s = s0; s < s1; s++) t_seg[s] = ((uint32_t)D.start[e] + D.len[e]) | (s == s0 ? 0x80000000u : 0u);
+    t_ent[e] = (uint32_t)D.start[e];
+  }
+  t_ent[E] = (uint32_t)total;
+  memcpy(t_ent + (E + 1), D.len.data(), (E + 1) * 4); memcpy(t_ent + 2 * (E + 1), D.reg.data(), (E + 1) * 4);
+  D.d_in = W.in; D.d_out = W.rin_own;
+  return 0;
+}
+int lzma_batch_launch(Ctx *c, int method, DevBatch &D) {
+  const int level = LZMA_PARAM[method - ZADA_LZMA_0].level;
+  Workspace &W = c->ws;
+  hipStream_t st = c->stream;
+  const uint32_t E = D.E;
+  const uint64_t total = D.total;
+  int rc;
+  std::vector<LzmaJob> jobs(E);
+  for (uint32_t e = 0; e < E; e++) {
+    LzmaJob &J = jobs[e];
+    memset(&J, 0, sizeof J);
+    J.in_off = D.start[e]; J.n = D.len[e]; J.out_off = D.off[e]; J.cap = D.cap[e]; J.zip_prefix = 1;
+    lzma_job_method(J, method);
+  }
+  std::vector<uint64_t> res;
+  if (D.kind == 1) {
+    std::vector<uint32_t> start32(E + 1);
+    for (uint32_t e = 0; e < E; e++) start32[e] = (uint32_t)D.start[e];
+    uint32_t *d_tab = (uint32_t *)(D.d_out + D.ototal);
+    hipMemcpyAsync(d_tab, start32.data(), 4ull * E, hipMemcpyHostToDevice, st);
+    hipMemcpyAsync(d_tab + E, D.len.data(), 4ull * E, hipMemcpyHostToDevice, st);
+    hipMemcpyAsync(d_tab + 2 * E, D.reg.data(), 4ull * E, hipMemcpyHostToDevice, st);
+    hipLaunchKernelGGL(k_batch_crc, dim3(E), dim3(64), 0, st, E, D.d_in, d_tab, d_tab + E, d_tab + 2 * E);
+    hipMemcpyAsync(D.reg.data(), d_tab + 2 * E, 4ull * E, hipMemcpyDeviceToHost, st);
+    if (hip_check(c, hipStreamSynchronize(st), "LZMA batch in")) return ZADA_E_HIP;
+    c->tmark("lzma:tokens");
+    if ((rc = lzma_run(c, jobs, D.d_in, total, nullptr, D.d_out, res))) return rc;
+  } else {
+    const uint32_t nseg = (uint32_t)(total >> 15);
+    const uint32_t *t_seg = c->btab, *t_ent = c->btab + nseg;
+    hipMemcpyAsync(W.segend, t_seg, (size_t)nseg * 4, hipMemcpyHostToDevice, st);
+    hipMemcpyAsync(W.ent_start, t_ent, (size_t)(E + 1) * 4, hipMemcpyHostToDevice, st);
+    hipMemcpyAsync(W.ent_len, t_ent + (E + 1), (size_t)(E + 1) * 4, hipMemcpyHostToDevice, st);
+    hipMemcpyAsync(W.ent_crc, t_ent + 2 * (E + 1), (size_t)(E + 1) * 4, hipMemcpyHostToDevice, st);
+    {
+      PadArgs pa; pa.in_end = W.in + total; pa.n_in = IN_PAD;
+      for (int l = 0; l < NLEVELS; l++) pa.link_end[l] = W.lprev[l] + (total >= 2 ? total - 2 : 0);
+      hipLaunchKernelGGL(k_pad_init, dim3(1), dim3(256), 0, st, pa);
+    }
+    c->rg = Range();
+    c->last_nblocks = 0; c->demand_rounds = 0; c->parse_rounds = 0;
+    hipLaunchKernelGGL(k_batch_crc, dim3(E), dim3(64), 0, st, E, W.in, W.ent_start, W.ent_len, W.ent_crc);
+    ShardJob job;
+    job.nbuf = total; job.tok_lo = 0; job.tok_hi = (uint32_t)total; job.final = true; job.entry_known = true; job.entry = ExitState{0, SYNC_F};
+    job.dst_atoms = W.ea_atoms + LB_CAP; job.dst_apos = W.ea_apos + LB_CAP; job.apos_bias = 0; job.cap_atoms = W.cap_atoms; job.segend = W.segend;
+    ShardResult sres;
+    rc = lz_shard(c, level == 1 ? 6 : 10, job, &sres);
+    if (rc) return rc == -2 ? ZADA_E_NOMEM : rc;
+    c->tmark("lzma:tokens");
+    if ((rc = lzma_run(c, jobs, W.in, total, W.ea_atoms + LB_CAP, D.d_out, res, W.ea_apos + LB_CAP, sres.ntok, W.ent_start))) return rc;
+    hipMemcpyAsync(D.reg.data(), W.ent_crc, 4ull * E, hipMemcpyDeviceToHost, st);
+    if (hip_check(c, hipStreamSynchronize(st), "LZMA batch CRCs")) return ZADA_E_HIP;
+  }
+  for (uint32_t e = 0; e < E; e++) { D.bytes[e] = res[2 * (size_t)e]; D.refused[e] = (uint8_t)(res[2 * (size_t)e + 1] >> 62 & 1); }
+  return 0;
+}
+bool lzma_batch_refused(Ctx *c, const DevBatch &D) {
+  for (uint32_t e = 0; e < D.E; e++)
+    if (D.refused[e]) { lzma_refused_text(c); return true; }
+  return false;
 }
 }  // namespace zada
 extern "C" {

@@ -2993,8 +2993,10 @@ int bz2_encode_device(Ctx *c, int option, const uint8_t *d_in, uint64_t n, int64
 //      its own with ONE block (the caller only sends entries short enough for that), so the entries are simply the blocks of a
 //      call; each gets its own header, choice (from bit 32) and footer.  h_out: host buffer for the streams, entry q's at
 //      out_off[q] (4-byte aligned), out_bytes[q] long.  Returns ZADA_E_TOO_LARGE if h_out (cap bytes) cannot take them.
+//      d_streams (may be null): receives the device address the offsets count from; the streams stay there until the next BZip2 call on the context.
+//      h_out = null: they are not copied to the host at all (cap is not looked at).
 int bz2_batch_encode(Ctx *c, int option, const uint8_t *d_arena, uint32_t E, const uint64_t *starts, const uint32_t *lens, uint8_t *h_out, uint64_t cap,
-                     uint64_t *out_off, uint64_t *out_bytes) {
+                     uint64_t *out_off, uint64_t *out_bytes, uint8_t **d_streams) {
   Bz2State *B = bz_state(c);
   hipStream_t st = c->stream;
   int rc;
@@ -3021,7 +3023,7 @@ int bz2_batch_encode(Ctx *c, int option, const uint8_t *d_arena, uint32_t E, con
   }
   woff[E] = w;
   bz_set_trace(B, choice.data());
-  if (4 * w > cap) { bz_reset_call(c); return ZADA_E_TOO_LARGE; }
+  if (h_out && 4 * w > cap) { bz_reset_call(c); return ZADA_E_TOO_LARGE; }
   if ((rc = dbuf_ensure(c, B->outw, 4 * w + 64)) || (rc = dbuf_ensure(c, B->extra, 16ull * E + 64))) return rc;
   BZ_HIP(hipMemsetAsync(B->outw.p, 0, 4 * w + 64, st));
   BZ_HIP(hipMemcpyAsync(B->extra.p, extra.data(), 16ull * E, hipMemcpyHostToDevice, st));
@@ -3055,8 +3057,9 @@ int bz2_batch_encode(Ctx *c, int option, const uint8_t *d_arena, uint32_t E, con
   }
   c->tmark("bz:assemble");
   hipLaunchKernelGGL(k_bz_words_to_bytes, dim3((uint32_t)((w + 255) / 256)), dim3(256), 0, st, B->outw.as<uint32_t>(), w, B->outw.as<uint32_t>());
-  BZ_HIP(hipMemcpyAsync(h_out, B->outw.p, 4 * w, hipMemcpyDeviceToHost, st));
+  if (h_out) BZ_HIP(hipMemcpyAsync(h_out, B->outw.p, 4 * w, hipMemcpyDeviceToHost, st));
   BZ_HIP(hipStreamSynchronize(st));
+  if (d_streams) *d_streams = (uint8_t *)B->outw.p;
   bz_reset_call(c);
   return 0;
 }

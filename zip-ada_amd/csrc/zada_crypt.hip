@@ -254,6 +254,78 @@ __global__ void __launch_bounds__(ZC_WAVE) k_zc_entries(uint8_t *__restrict__ ar
   if (lane == 0) { keys[3 * e] = key0; keys[3 * e + 1] = key1; keys[3 * e + 2] = key2; }
 }
 
+// `left` bytes of the padded rows to dst at any alignment, touching only those bytes: head and tail byte-wise, the 16-byte words of dst in between put
+// together from the rows (a word may run from one row into the next).
+__device__ __forceinline__ void zc_stage_out_any(const uint8_t *rows, uint8_t *dst, uint32_t left) {
+  const uint32_t lane = threadIdx.x;
+  auto at = [&](uint32_t o) -> uint32_t { return rows[(o / ZC_SUB) * ZC_ROW + (o % ZC_SUB)]; };
+  uint32_t hd = (16u - (uint32_t)((uintptr_t)dst & 15u)) & 15u;
+  if (hd > left) hd = left;
+  if (lane < hd) dst[lane] = (uint8_t)at(lane);
+  const uint32_t words = (left - hd) / 16u;
+  uint4 *d = (uint4 *)(dst + hd);
+  for (uint32_t w = lane; w < words; w += ZC_WAVE) {
+    const uint32_t o = hd + 16u * w;
+    uint32_t x[4];
+#pragma unroll
+    for (uint32_t q = 0; q < 4; q++) x[q] = at(o + 4 * q) | at(o + 4 * q + 1) << 8 | at(o + 4 * q + 2) << 16 | at(o + 4 * q + 3) << 24;
+    d[w] = make_uint4(x[0], x[1], x[2], x[3]);
+  }
+  for (uint32_t i = hd + words * 16u + lane; i < left; i += ZC_WAVE) dst[i] = (uint8_t)at(i);
+}
+
+// Encode out of place, for the archive writer (zada_zip_device_ex): one wave per job reads the job's bytes -- a stream in the workspace, or a stored
+// entry's own bytes, which are never written -- and writes their cipher text to its place in the archive, both at any alignment.  The bytes in front
+// of the source's first 16-byte boundary (at most 15) are coded one after the other from the job's keys, by every lane alike; from there on the source
+// is staged with aligned 16-byte loads, strip after strip of one tile through the four rounds of k_zc_entries, the keys carried from strip to strip.
+__global__ void __launch_bounds__(ZC_WAVE) k_zc_place(const ZcPlaceJob *__restrict__ jobs, const ZcOps *__restrict__ ops, uint32_t count) {
+  __shared__ uint32_t tab[256];
+  __shared__ uint32_t m[6][32];
+  __shared__ uint32_t pw[6];
+  __shared__ __attribute__((aligned(16))) uint8_t rows[ZC_WAVE * ZC_ROW];
+  const uint32_t e = blockIdx.x;
+  if (e >= count) return;
+  zc_load_crc_table(tab);
+  zc_load_ops(m, pw, ops, 0, 6);
+  const ZcPlaceJob J = jobs[e];
+  const uint8_t *src = (const uint8_t *)J.src;
+  uint8_t *dst = (uint8_t *)J.dst;
+  uint64_t n = J.len;
+  uint32_t key0 = J.keys[0], key1 = J.keys[1], key2 = J.keys[2];
+  const uint32_t lane = threadIdx.x, o = lane * ZC_SUB;
+  __syncthreads();
+  uint32_t h = (16u - (uint32_t)((uintptr_t)src & 15u)) & 15u;
+  if (h > n) h = (uint32_t)n;
+  for (uint32_t i = 0; i < h; i++) {
+    const uint8_t x = zc_byte<3>(src[i], tab, key0, key1, key2);
+    if (lane == 0) dst[i] = x;
+  }
+  src += h; dst += h; n -= h;
+  uint8_t *row = rows + lane * ZC_ROW;
+  for (uint64_t s0 = 0; s0 < n; s0 += ZC_TILE) {
+    const uint32_t left = n - s0 < ZC_TILE ? (uint32_t)(n - s0) : ZC_TILE;
+    __syncthreads();
+    zc_stage_in(rows, src + s0, left, true);
+    __syncthreads();
+    const uint32_t len = o >= left ? 0u : left - o < ZC_SUB ? left - o : ZC_SUB;
+    uint32_t a = 0, b = 0, c = 0, incl;
+    zc_pass<0>(row, len, tab, a, b, c);
+    const uint32_t s_0 = zc_wave_scan<false>(a, key0, m, pw, 6, &incl);
+    a = s_0; b = 0;
+    zc_pass<1>(row, len, tab, a, b, c);
+    const uint32_t s_1 = zc_wave_scan<true>(b, key1, m, pw, 6, &incl);
+    a = s_0; b = s_1; c = 0;
+    zc_pass<2>(row, len, tab, a, b, c);
+    const uint32_t s_2 = zc_wave_scan<false>(c, key2, m, pw, 6, &incl);
+    a = s_0; b = s_1; c = s_2;
+    zc_pass<3>(row, len, tab, a, b, c);
+    const int last = (int)((left - 1) / ZC_SUB);                                         // the lane of the strip's last byte
+    key0 = __shfl(a, last, 64); key1 = __shfl(b, last, 64); key2 = __shfl(c, last, 64);
+    __syncthreads();
+    zc_stage_out_any(rows, dst + s0, left);
+  }
+}
+
 // ---- host side ----
 static uint32_t zc_table[256];
 static ZcOps zc_ops;
@@ -291,6 +363,7 @@ struct ZcState {
   uint64_t cap_bytes = 0;                               // bytes of one piece the sub / agg arrays serve
   uint8_t *io = nullptr; uint64_t cap_io = 0;           // zada_compress_data_pw's input and stream, a batch's arena
   uint64_t *ent = nullptr; uint32_t *ent_keys = nullptr; uint64_t cap_ent = 0;
+  ZcPlaceJob *place = nullptr; uint64_t cap_place = 0;  // the jobs of k_zc_place
 };
 static ZcState *zc_state(Ctx *c) {
   if (c->zc) return (ZcState *)c->zc;
@@ -315,6 +388,7 @@ void crypt_destroy(Ctx *c) {
   if (S->io) hipFree(S->io);
   if (S->ent) hipFree(S->ent);
   if (S->ent_keys) hipFree(S->ent_keys);
+  if (S->place) hipFree(S->place);
   hipFree(S->d_ops); hipFree(S->d_keys);
   delete S;
   c->zc = nullptr;
@@ -381,6 +455,24 @@ int crypt_encode_device(Ctx *c, uint32_t keys[3], uint8_t *d_buf, uint64_t n) {
   if (hip_check(c, hipMemcpyAsync(k, S->d_keys, 12, hipMemcpyDeviceToHost, st), "crypt keys out") || hip_check(c, hipStreamSynchronize(st), "crypt")) return ZADA_E_HIP_;
   memcpy(keys, k, 12);
   return 0;
+}
+
+int crypt_encode_place(Ctx *c, uint32_t E, const ZcPlaceJob *jobs) {
+  if (E == 0) return 0;
+  ZcState *S = zc_state(c);
+  if (!S) { c->err = "crypt: no memory for the tables"; return ZADA_E_NOMEM; }
+  if (S->cap_place < E) {
+    hipStreamSynchronize(c->stream);
+    if (S->place) hipFree(S->place);
+    S->place = nullptr; S->cap_place = 0;
+    const uint64_t cap = (uint64_t)E + E / 4 + 1024;
+    if (hipMalloc((void **)&S->place, cap * sizeof(ZcPlaceJob)) != hipSuccess) { (void)hipGetLastError(); c->err = "hipMalloc (crypt place jobs)"; return ZADA_E_NOMEM; }
+    S->cap_place = cap;
+  }
+  if (hip_check(c, hipMemcpy(S->place, jobs, (size_t)E * sizeof(ZcPlaceJob), hipMemcpyHostToDevice), "crypt place jobs")) return ZADA_E_HIP_;
+  hipLaunchKernelGGL(k_zc_place, dim3(E), dim3(ZC_WAVE), 0, c->stream, (const ZcPlaceJob *)S->place, (const ZcOps *)S->d_ops, E);
+  c->tmark("zip:k_zc_place");
+  return hip_check(c, hipGetLastError(), "crypt place launch");
 }
 
 // entries idx[0 .. E) of the caller's arrays, each of at most CRYPT_WAVE_MAX bytes, through one launch: packed into an arena, one wave per entry

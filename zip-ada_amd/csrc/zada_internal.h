@@ -363,12 +363,17 @@ uint8_t crypt_code(const uint32_t keys[3]);
 constexpr uint64_t CRYPT_WAVE_MAX = 256u << 10;     // a batch's entries of up to this many bytes: one wave each, in one launch
 int crypt_io(Ctx *c, uint64_t bytes, uint8_t **p);
 int crypt_encode_device(Ctx *c, uint32_t keys[3], uint8_t *d_buf, uint64_t n);
+// Encode OUT OF PLACE for the archive writer: job e reads len bytes at device address src (any alignment, never written) and writes their cipher text
+// to device address dst (any alignment, only those len bytes), from keys.  One wave per job in one launch on the context's stream; the call does not
+// wait for it (the jobs are copied before it returns).
+struct ZcPlaceJob { uint64_t src, dst, len; uint32_t keys[3], pad; };
+int crypt_encode_place(Ctx *c, uint32_t E, const ZcPlaceJob *jobs);
 int crypt_encode_small(Ctx *c, const int *idx, uint32_t E, uint32_t (*keys)[3], uint8_t *const *buf, const uint64_t *n);
 int bz2_encode_device(Ctx *c, int option, const uint8_t *d_in, uint64_t n, int64_t size_hint, uint8_t *d_out, uint64_t cap, uint64_t *out_len,
                       int (*fb)(int, void *), void *user);
 uint64_t bz2_last_blocks(Ctx *c, uint64_t *dst, uint64_t cap_items);
 int bz2_batch_encode(Ctx *c, int option, const uint8_t *d_arena, uint32_t E, const uint64_t *starts, const uint32_t *lens, uint8_t *h_out, uint64_t cap,
-                     uint64_t *out_off, uint64_t *out_bytes);
+                     uint64_t *out_off, uint64_t *out_bytes, uint8_t **d_streams = nullptr);
 int bz2_range_open(Ctx *c, int option, const uint8_t *d_buf, uint64_t buf_len, uint64_t buf_off, uint64_t stream_total, uint64_t start, uint64_t own_end,
                    uint64_t *next_start, uint64_t *nblocks);
 int bz2_range_encode(Ctx *c);
@@ -442,6 +447,27 @@ int batch_layout(Ctx *c, uint32_t E, const uint64_t *n, const uint32_t *crc_in, 
 void batch_segends_all(Ctx *c, const BatchLayout &L);
 int batch_launch(Ctx *c, int method, const BatchLayout &L, uint64_t *obytes, uint32_t **h_bytes, uint32_t **h_base, uint32_t **h_crc);
 int deflate_device_one(Ctx *c, int method, const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout);
+// ... and the same for one BZip2 / LZMA stream (zada_bzip2_device / zada_lzma_device behind their argument checks)
+int bzip2_device_one(Ctx *c, int method, const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout);
+int lzma_device_one(Ctx *c, int method, const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout);
+// A BZip2 or LZMA batch cut into layout and launch, as batch_layout / batch_launch cut a Deflate batch: the layout books the buffers and says where
+// entry e's slot lies (d_in + start [e]); the caller fills the slots on the context's stream -- zada_bzip2_batch / zada_lzma_batch with one copy
+// from the host, zada_zip_device_ex with k_zw_pack --; the launch leaves entry e's stream, bytes [e] long, at d_out + off [e] IN DEVICE MEMORY
+// (LZMA: of a payload longer than cap [e] only the first cap [e] bytes), its CRC register in reg [e], and has synchronised the stream.
+struct DevBatch {
+  uint32_t E = 0;
+  int kind = 0;                                    // 0: BZip2; 1: LZMA level 0 / 3 (64-byte slots in rin_own); 2: LZMA level 1 / 2 (32 KiB slots in the LZ buffer)
+  uint64_t total = 0, ototal = 0, nfs = 0;         // bytes of slots; LZMA: bytes of output slots; kind 2: flush slots
+  uint8_t *d_in = nullptr, *d_out = nullptr;
+  std::vector<uint64_t> start, off, bytes, cap;    // per entry
+  std::vector<uint32_t> len, reg;                  // (E + 1 values)
+  std::vector<uint8_t> refused;                    // LZMA_3: ZADA_E_REFERENCE for this entry
+};
+int bzip2_batch_layout(Ctx *c, int method, uint32_t E, const uint64_t *n, const uint32_t *crc_in, DevBatch &D);
+int bzip2_batch_launch(Ctx *c, int method, DevBatch &D, uint8_t *h_out, uint64_t h_cap);     // h_out: the streams also go to the host (pinned), null: they stay
+int lzma_batch_layout(Ctx *c, int method, uint32_t E, const uint64_t *n, const uint32_t *crc_in, DevBatch &D);
+int lzma_batch_launch(Ctx *c, int method, DevBatch &D);
+bool lzma_batch_refused(Ctx *c, const DevBatch &D);                                          // sets the error text of the first refused entry
 int batch_geometry(Ctx *c, uint32_t E, const uint32_t *d_total_atoms);
 int entropy_analyze(Ctx *c);
 int entropy_choose(Ctx *c);

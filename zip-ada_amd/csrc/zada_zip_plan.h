@@ -27,13 +27,14 @@ inline const char *zw_method_name(int m) {
 }
 
 // what zw_check found wrong with entry *bad
-enum ZwWhy { ZW_W_NONE = 0, ZW_W_NULL_DATA, ZW_W_NAME, ZW_W_TOO_LARGE, ZW_W_OVERLAP };
+enum ZwWhy { ZW_W_NONE = 0, ZW_W_NULL_DATA, ZW_W_NAME, ZW_W_TOO_LARGE, ZW_W_OVERLAP, ZW_W_CRYPT_SIZE };
 inline const char *zw_why_text(int why) {
   switch (why) {
     case ZW_W_NULL_DATA: return "null d_data with n > 0";
     case ZW_W_NAME: return "a name longer than 65 535 bytes (or a null name)";
     case ZW_W_TOO_LARGE: return "an entry of 1 TiB or more";
     case ZW_W_OVERLAP: return "its input overlaps the archive buffer";
+    case ZW_W_CRYPT_SIZE: return "an encrypted entry of 4 GiB - 11 .. 4 GiB - 1 bytes (with the 12 header bytes its compressed size has no place in a local header without Zip64 extension)";
     default: return "";
   }
 }
@@ -109,8 +110,10 @@ inline void zw_check_size(ZwArchive &A, uint64_t v) { if (!A.zip64 && v >= (1ull
 inline uint32_t zw_local_len(const zada_zip_entry &e, uint64_t offset) { return 30 + e.name_len + (zw_needs_zip64(e.n, e.n, offset) ? 20u : 0u); }
 // The entry's local header appended to `blob`, the entry added to the directory; returns the header's length.  The header's form is decided on the
 // provisional sizes -- the uncompressed size for both (zip-create.adb:231-241) --, its extension carries the final ones.
-inline uint32_t zw_add(ZwArchive &A, const zada_zip_entry &e, uint32_t crc, uint64_t csize, uint64_t usize, uint16_t zip_type, std::vector<uint8_t> &blob) {
-  ZwDirEnt d{csize, usize, A.base + A.pos, crc, e.time, (uint16_t)((e.flags & 1u) ? 0x0800 : 0), zip_type, e.name, e.name_len};
+// more_flags: LZMA_EOS_Flag_Bit 0x0002 (zip type 14) and Encryption_Flag_Bit 0x0001 (zip-create.adb:221-223, 266-278), as add_compressed sets them.
+inline uint32_t zw_add(ZwArchive &A, const zada_zip_entry &e, uint32_t crc, uint64_t csize, uint64_t usize, uint16_t zip_type, std::vector<uint8_t> &blob,
+                       uint16_t more_flags = 0) {
+  ZwDirEnt d{csize, usize, A.base + A.pos, crc, e.time, (uint16_t)(((e.flags & 1u) ? 0x0800 : 0) | more_flags), zip_type, e.name, e.name_len};
   zw_check_size(A, usize);
   const bool z64 = zw_needs_zip64(usize, usize, d.offset);
   const size_t at = blob.size();
@@ -188,6 +191,79 @@ inline void zw_single_place(ZwArchive &A, const zada_zip_entry *ent, int i, bool
   jobs.push_back(ZwJob{at, dst, hl, ZW_SRC_BLOB, (uint32_t)i});
   if (csize) jobs.push_back(ZwJob{0, dst + hl, csize, stored ? (uint32_t)ZW_SRC_DATA : (uint32_t)ZW_SRC_STREAM, (uint32_t)i});
   if (res) res[i] = zada_zip_result{ZADA_OK, zt, 0, crc, csize, A.base + dst};
+}
+
+// ---- zada_zip_device_ex: every method but Shrink and Reduce, a method per entry (Preselection), passwords ----
+inline bool zw_method_ok_ex(int m) { return m == 0 || (m >= ZADA_DEFLATE_FIXED && m <= ZADA_PRESELECTION_2); }
+inline bool zw_is_bzip2(int m) { return m >= ZADA_BZIP2_1 && m <= ZADA_BZIP2_3; }
+inline bool zw_is_lzma(int m) { return m >= ZADA_LZMA_0 && m <= ZADA_LZMA_FOR_AU; }
+inline uint16_t zw_zip_type(int m) { return m == 0 ? 0 : m <= ZADA_DEFLATE_R ? 8 : zw_is_bzip2(m) ? 12 : 14; }      // of a single method
+// the longest entry that is one block whatever it holds (zada_bzip2_batch's rule)
+inline uint64_t zw_bz_one_block(int m) { return ((m == ZADA_BZIP2_1 ? 100000ull : m == ZADA_BZIP2_2 ? 400000ull : 900000ull) - 16) * 4 / 5; }
+// zw_check for zada_zip_device_ex: with a password an entry of 4 GiB - 11 .. 4 GiB - 1 bytes is refused as well.  The form of its local header is decided
+// on the uncompressed size, below 0xFFFFFFFF, so it has no Zip64 extension, and the compressed size with the 12 header bytes -- of the stored entry at
+// the least -- does not fit the header's four bytes (ZipCreate.add_compressed cannot pack it either).  The first bad entry in table order is reported.
+inline int zw_check_ex(const zada_zip_entry *ent, int count, uint64_t d_archive, uint64_t cap, bool encrypted, int *bad, int *why) {
+  const int rc = zw_check(ent, count, d_archive, cap, bad, why);
+  const int upto = rc ? *bad : count;
+  if (encrypted)
+    for (int i = 0; i < upto; i++)
+      if (ent[i].n > ZW_M32 - 12 && ent[i].n < ZW_M32) { *bad = i; *why = ZW_W_CRYPT_SIZE; return ZADA_E_INVALID; }
+  return rc;
+}
+// zw_bound with the 12 bytes of an encryption header per entry.  The central extension also looks at the compressed size, which may reach n + 12.
+inline uint64_t zw_bound_ex(int count, const zada_zip_entry *ent, uint64_t archive_base, bool encrypted) {
+  uint64_t local = 0, central = 0;
+  const uint64_t x = encrypted ? 12 : 0;
+  for (int i = 0; i < count; i++) {
+    const bool z64 = zw_needs_zip64(ent[i].n, ent[i].n, archive_base + local);
+    local += 30 + (uint64_t)ent[i].name_len + (z64 ? 20 : 0) + ent[i].n + x;
+    central += 46 + (uint64_t)ent[i].name_len + (zw_needs_zip64(ent[i].n + x, ent[i].n, archive_base + local) ? 28 : 0);
+  }
+  return local + central + 56 + 20 + 22;
+}
+// The groups when every entry has its method m [i] (a single method: the same for all; never a Preselection method).  Method Store (for all): zw_groups'
+// Store groups.  Otherwise an entry above ZW_ENTRY_MAX, or a BZip2 entry longer than one block, ends the group before it and runs alone; the others
+// are collected while their slots stay within `limit` bytes, the BZip2 entries' within bz_limit and the HBM literal tables (lit [i] bytes, 0: none)
+// within lit_limit; a group of one takes the single-stream path.
+inline void zw_groups_ex(const zada_zip_entry *ent, int count, const int *m, const uint64_t *lit, uint64_t limit, uint64_t bz_limit, uint64_t lit_limit,
+                         std::vector<ZwGroup> &out) {
+  out.clear();
+  int g0 = 0;
+  uint64_t bytes = 0, bz = 0, lt = 0;
+  auto flush = [&](int g1) {
+    if (g1 > g0) out.push_back(ZwGroup{g0, g1, g1 - g0 == 1 ? ZW_G_SINGLE : ZW_G_BATCH});
+    g0 = g1; bytes = bz = lt = 0;
+  };
+  for (int i = 0; i < count; i++) {
+    const uint64_t slot = zw_slot(ent[i].n), b = zw_is_bzip2(m[i]) ? slot : 0, l = lit ? lit[i] : 0;
+    if (ent[i].n > ZW_ENTRY_MAX || (b && ent[i].n > zw_bz_one_block(m[i]))) { flush(i); flush(i + 1); continue; }
+    if (bytes + slot > limit || bz + b > bz_limit || lt + l > lit_limit) flush(i);
+    bytes += slot; bz += b; lt += l;
+  }
+  flush(count);
+}
+// What the launches of entry i's method left: a stream of `bytes` bytes at device address src (bytes >= n, or zip_type 0: none that counts), the running
+// CRC register, the zip type of its method.
+struct ZwVerdict { uint64_t src, bytes; uint32_t reg; uint16_t zip_type, pad; };
+// zw_group_place for verdicts of any method.  hdr12: null, or 12 bytes per entry (k counted from g0), the encoded encryption header that goes behind
+// the local header; the payload's job then starts 12 bytes further on and csize counts them.  A job of kind ZW_SRC_STREAM carries the stream's device
+// address in src.
+inline void zw_group_place_ex(ZwArchive &A, const zada_zip_entry *ent, int g0, int g1, const ZwVerdict *v, const uint8_t *hdr12, std::vector<uint8_t> &blob,
+                              std::vector<ZwJob> &jobs, zada_zip_result *res) {
+  for (int i = g0; i < g1; i++) {
+    const zada_zip_entry &e = ent[i];
+    const ZwVerdict &V = v[i - g0];
+    const bool stored = V.zip_type == 0 || V.bytes >= e.n;
+    const uint64_t payload = stored ? e.n : V.bytes, csize = payload + (hdr12 ? 12 : 0), dst = A.pos, at = blob.size();
+    const uint32_t crc = V.reg ^ 0xFFFFFFFFu;
+    const uint16_t zt = stored ? 0 : V.zip_type;
+    uint32_t hl = zw_add(A, e, crc, csize, e.n, zt, blob, (uint16_t)((zt == 14 ? 0x0002 : 0) | (hdr12 ? 0x0001 : 0)));
+    if (hdr12) { blob.insert(blob.end(), hdr12 + 12 * (size_t)(i - g0), hdr12 + 12 * (size_t)(i - g0) + 12); hl += 12; }
+    jobs.push_back(ZwJob{at, dst, hl, ZW_SRC_BLOB, (uint32_t)i});
+    if (payload) jobs.push_back(ZwJob{stored ? 0 : V.src, dst + hl, payload, stored ? (uint32_t)ZW_SRC_DATA : (uint32_t)ZW_SRC_STREAM, (uint32_t)i});
+    if (res) res[i] = zada_zip_result{ZADA_OK, zt, 0, crc, csize, A.base + dst};
+  }
 }
 
 // A job cut into the pieces one wave moves: at most ZW_PIECE bytes each.
