@@ -214,7 +214,7 @@ int zada_compress_data_pw(zada_ctx *ctx, int method, int content_hint, const uin
  * -- a Huffman code is found only by decoding the one before it, a match reads what earlier tokens wrote --, so ENTRIES are what runs in
  * parallel: one wave per entry (csrc/zada_inflate.hip), use zada_inflate_batch for many of them.  ONE STREAM ALONE RUNS AT ONE
  * WAVE'S PACE (as one LZMA stream does): 8.3 MB/s for one 64 MiB Deflate_3 stream of the benchmark corpus, where one zlib thread on the host
- * does 434 MB/s, against 19.8 GB/s for 10 000 entries of 16 KiB in one launch (profiles/inflate/NOTES.md); cutting one stream over many waves is not done.
+ * does 434 MB/s, against 19.8 GB/s for 10 000 entries of 16 KiB in one launch (profiles/inflate/NOTES.md); zada_inflate_par below cuts one large stream over many waves.
  *   crc_inout : the running CRC-32 register (Init before, Final after: zip-crc_crypto.adb:49-76), updated over the bytes written, on the
  *               device.  May be NULL.
  *   cap       : the uncompressed size the directory promises; a stream that writes more is ZADA_E_DATA.  cap = 0 with the stream of an
@@ -240,6 +240,34 @@ int zada_inflate_device(zada_ctx *ctx, int format, const void *d_in, uint64_t n_
  * stay on the device and only sizes, CRCs and verdicts come back (UnZip's test_only). */
 int zada_inflate_batch(zada_ctx *ctx, int count, const int *format, const uint8_t *const *in, const uint64_t *n_in,
                        uint8_t *const *out, const uint64_t *cap, uint64_t *out_len, uint64_t *in_used, uint32_t *crc, int *rc);
+/* ---- One large Deflate stream on many waves (csrc/zada_inflate_par.hip, csrc/zada_inflate_par_logic.h) ----
+ * zada_inflate_device's contract -- the same bytes, *out_len, *in_used, CRC register, return code and zada_last_error text for the same input,
+ * valid or damaged -- by two-stage decoding with window markers: the compressed stream is cut into chunks of "inflate_par_chunk_kib" KiB, a wave
+ * per chunk finds a candidate block start and counts what the chunk decodes to, the host chains the chunks from the exact first one (a chunk
+ * whose start is not the end of the one before is scouted again from that end: "inflate_par_repair_pct" bounds how many), a wave per live chunk
+ * decodes into 16-bit symbols in a workspace of 2 bytes per output byte, references into earlier chunks as markers, and two more kernels
+ * resolve the markers and write the bytes.  The CRC-32 goes through the encoder's chunked kernels.  A stream that is damaged, takes too many
+ * repairs, has fewer than two live chunks, is Deflate64 (format 9) or whose workspace cannot be had runs on zada_inflate_device's one wave
+ * instead, with nothing written to d_out before; zada_inflate_par_last says which way the last call went.  Opt-in: no other entry point takes
+ * this path unless the knob "inflate_par_min_kib" (0 = off) is set, which sends the Deflate entries of zada_unzip_device whose compressed size
+ * is at least that many KiB through it, one after the other.  EXPERIMENTAL: see profiles/inflate_par/NOTES.md for what it gains. */
+int zada_inflate_par(zada_ctx *ctx, int format, const uint8_t *in, uint64_t n_in, uint8_t *out, uint64_t cap,
+                     uint64_t *out_len, uint64_t *in_used, uint32_t *crc_inout);
+int zada_inflate_par_device(zada_ctx *ctx, int format, const void *d_in, uint64_t n_in, void *d_out, uint64_t cap,
+                            uint64_t *out_len, uint64_t *in_used, uint32_t *crc_inout);
+enum { ZADA_INFP_NONE = 0, ZADA_INFP_DAMAGED = 1, ZADA_INFP_REPAIRS = 2, ZADA_INFP_SINGLE_CHUNK = 3, ZADA_INFP_FORMAT = 4, ZADA_INFP_MEMORY = 5 };
+typedef struct zada_inflate_par_info {
+  uint64_t chunks;        /* chunks the stream was cut into */
+  uint64_t live_chunks;   /* ... on the chain: decoded by a wave of their own */
+  uint64_t repairs;       /* chunks scouted again from an exact start */
+  uint64_t scout_rounds;  /* launches of the scout */
+  uint64_t marker_bytes;  /* output bytes that were markers before the window / finish kernels resolved them */
+  int32_t fell_back;      /* streams that ran on the one wave instead (0 or 1; zada_unzip_device: summed over the call's large entries, as every field is) */
+  int32_t reason;         /* ZADA_INFP_*: why the last of them did */
+  uint64_t streams;       /* streams that came this way (1; zada_unzip_device: the call's large Deflate entries) */
+} zada_inflate_par_info;
+/* the record of the last zada_inflate_par* call, or of the last zada_unzip_device call with "inflate_par_min_kib" set, on this context */
+int zada_inflate_par_last(zada_ctx *ctx, zada_inflate_par_info *info);
 /* CRC_Crypto.Decode (zip-crc_crypto.adb:130-137) of `count` buffers in place, each from its own keys (in and out): what opens the entries
  * zada_compress_data_pw writes (the first 12 bytes decode to the encryption header, whose last byte is the entry's check byte).  Unlike
  * Encode it is serial -- key 0 is a CRC over the PLAIN text, known only byte by byte -- so there is no scan: one lane per buffer. */

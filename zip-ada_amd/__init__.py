@@ -201,6 +201,9 @@ def load_library():
         L.zada_inflate_device.argtypes = [vp, i32, vp, u64, vp, u64, u64p, u64p, u32p]
         L.zada_inflate_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.zada_crypt_decode_batch.argtypes = [vp, i32, vp, vp, vp]
+        L.zada_inflate_par.argtypes = [vp, i32, vp, u64, vp, u64, u64p, u64p, u32p]
+        L.zada_inflate_par_device.argtypes = [vp, i32, vp, u64, vp, u64, u64p, u64p, u32p]
+        L.zada_inflate_par_last.argtypes = [vp, vp]
     if hasattr(L, "zada_bunzip2"):                   # (likewise: the BZip2 reader)
         L.zada_bunzip2.argtypes = [vp, vp, u64, vp, u64, u64p, u64p, u32p]
         L.zada_bunzip2_device.argtypes = [vp, vp, u64, vp, u64, u64p, u64p, u32p]
@@ -286,7 +289,7 @@ class Encoder:
             pass
 
     def set_knob(self, name, value):
-        """Tuning / test knobs ("budget", "max_demand_rounds", "inner_budget", "shard_kib", "span_mib", "batch_mib", "bunzip_batch_mib"); none changes a byte of output.
+        """Tuning / test knobs ("budget", "max_demand_rounds", "inner_budget", "shard_kib", "span_mib", "batch_mib", "bunzip_batch_mib", "inflate_par_chunk_kib", "inflate_par_repair_pct", "inflate_par_min_kib"); none changes a byte of output.
         "lzma_dict" is the reference's dictionary_size parameter for LZMA_3 (0 = the entry's size, what Zip.Compress.LZMA_E passes)."""
         if self.lib.zada_set_knob(self.ctx, name.encode(), int(value)) != 0:
             raise ZadaError("unknown knob %r" % name)
@@ -720,6 +723,42 @@ class Encoder:
         if rc != 0:
             self._err(rc, "zada_inflate_device")
         return ol.value, iu.value, c.value
+
+    # ---- one large Deflate stream on many waves (include/zada.h "One large Deflate stream"; experimental) ----
+    INFLATE_PAR_REASONS = ("none", "damaged", "repairs", "single chunk", "format", "memory")
+
+    def inflate_par(self, payload, size, format=8, crc=0xFFFFFFFF):
+        """inflate (payload, size) with the stream cut into chunks of "inflate_par_chunk_kib", a wave per chunk (zada_inflate_par): the same
+        result and the same DataError.  size is the cap, as the directory promises it.  Returns (bytes, input bytes used, running CRC register);
+        inflate_par_last () says whether the stream ran that way."""
+        n, cap = len(payload), int(size)
+        out = ctypes.create_string_buffer(max(cap, 1))
+        ol, iu, c = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(crc)
+        rc = self.lib.zada_inflate_par(self.ctx, format, _addr(payload) if n else None, n, ctypes.addressof(out), cap, ctypes.byref(ol), ctypes.byref(iu), ctypes.byref(c))
+        if rc != 0:
+            self._err(rc, "zada_inflate_par")
+        return out.raw[:ol.value], iu.value, c.value
+
+    def inflate_par_device(self, d_in_ptr, n_in, d_out_ptr, cap, format=8, crc=0xFFFFFFFF):
+        """inflate_device on many waves (zada_inflate_par_device).  Returns (bytes written, input bytes used, running CRC register); raises DataError."""
+        ol, iu, c = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(crc)
+        rc = self.lib.zada_inflate_par_device(self.ctx, format, d_in_ptr, n_in, d_out_ptr, cap, ctypes.byref(ol), ctypes.byref(iu), ctypes.byref(c))
+        if rc != 0:
+            self._err(rc, "zada_inflate_par_device")
+        return ol.value, iu.value, c.value
+
+    def inflate_par_last(self):
+        """The record of the last inflate_par* call (or of the last unzip_device call with "inflate_par_min_kib" set, summed over its large entries):
+        dict of chunks, live_chunks, repairs, scout_rounds, marker_bytes, fell_back, reason (a word of INFLATE_PAR_REASONS), streams."""
+        import numpy as np
+        r = np.zeros(1, dtype=np.dtype([("chunks", "<u8"), ("live_chunks", "<u8"), ("repairs", "<u8"), ("scout_rounds", "<u8"), ("marker_bytes", "<u8"),
+                                        ("fell_back", "<i4"), ("reason", "<i4"), ("streams", "<u8")]))
+        rc = self.lib.zada_inflate_par_last(self.ctx, r.ctypes.data)
+        if rc != 0:
+            self._err(rc, "zada_inflate_par_last")
+        d = {k: int(r[k][0]) for k in r.dtype.names}
+        d["reason"] = self.INFLATE_PAR_REASONS[d["reason"]]
+        return d
 
     # ---- the reader: BZip2.Decoding.Decompress (bzip2-decoding.adb; include/zada.h "BZip2.Decoding") ----
     def bunzip2(self, payload, size=None, crc=0xFFFFFFFF):
@@ -1403,15 +1442,22 @@ class UnZip:
     checks and errors; the default leaves them UnsupportedMethod.  UnZip (encoder, lzma=True) likewise decodes LZMA (14) entries: all of a call
     through ONE unlzma_batch (one wave per entry), eos = bit 1 of the entry's flags, cap = its uncompressed size; an entry whose stream ended on a
     marker with fewer bytes than promised is a SizeError.  Without lzma=True, LZMA entries are UnsupportedMethod.
-    extract_device does the same for an archive that lies in device memory (ZipInfo.load_device), into device memory, in ONE zada_unzip_device call."""
+    extract_device does the same for an archive that lies in device memory (ZipInfo.load_device), into device memory, in ONE zada_unzip_device call.
+    UnZip (encoder, parallel_inflate=KiB) -- experimental -- sends Deflate entries whose compressed size is at least that many KiB through
+    Encoder.inflate_par, one stream on many waves: extract calls it entry by entry (last_parallel lists their records), extract_device sets the knob
+    "inflate_par_min_kib" around its call (Encoder.inflate_par_last then holds the sums).  Results, exceptions and texts are the default's."""
 
     _NAMES = {1: "Shrink", 2: "Reduce_1", 3: "Reduce_2", 4: "Reduce_3", 5: "Reduce_4", 6: "Implode", 12: "BZip2", 14: "LZMA", 98: "PPMd", 99: "AES"}
     _STREAMS = {8: "Deflate", 9: "Deflate64", 12: "BZip2", 14: "LZMA"}
 
-    def __init__(self, encoder, bzip2=False, lzma=False):
+    def __init__(self, encoder, bzip2=False, lzma=False, parallel_inflate=None):
         self.enc = encoder
         self.bzip2 = bool(bzip2)
         self.lzma = bool(lzma)
+        if parallel_inflate is not None and int(parallel_inflate) < 1:
+            raise ZadaError("UnZip: parallel_inflate is a size in KiB, at least 1, or None")
+        self.parallel_inflate = None if parallel_inflate is None else int(parallel_inflate)
+        self.last_parallel = []                            # extract: (name, inflate_par_last ()) of the entries that went through inflate_par
 
     def _unsupported(self, e):
         """The UnsupportedMethod of an entry this reader's gates exclude, or None."""
@@ -1486,6 +1532,17 @@ class UnZip:
             for k, (rc, out, ol, _, reg) in zip(todo, got):
                 ex = self._verdict(ents[k], rc, ol, reg)
                 res[k] = ex if ex is not None else None if test_only else out
+        self.last_parallel = []
+        if self.parallel_inflate is not None:
+            for k, e in enumerate(ents):
+                if k in res or e.method != 8 or len(payload[k]) < self.parallel_inflate << 10:
+                    continue
+                try:
+                    out, used, reg = self.enc.inflate_par(payload[k], e.usize)
+                    settle([k], [(0, out, len(out), used, reg)])
+                except DataError:
+                    settle([k], [(E_DATA, None, 0, 0, 0)])
+                self.last_parallel.append((e.name, self.enc.inflate_par_last()))
         todo = [k for k in range(len(ents)) if k not in res and ents[k].method in (8, 9)]
         if todo:
             settle(todo, self.enc.inflate_batch([payload[k] for k in todo], [ents[k].usize for k in todo], [ents[k].method for k in todo], deliver=not test_only))
@@ -1548,7 +1605,13 @@ class UnZip:
             out = None if test_only else torch.empty(max(total, 1), dtype=torch.uint8, device=t.device)
             keys0 = self.enc.crypt_init_keys(password) if password is not None and crypt.any() else None
             torch.cuda.current_stream(t.device).synchronize()
-            _, r = self.enc.unzip_device(t.data_ptr(), t.numel(), None if out is None else out.data_ptr(), 0 if out is None else total, tab, keys0)
+            if self.parallel_inflate is not None:
+                self.enc.set_knob("inflate_par_min_kib", self.parallel_inflate)
+            try:
+                _, r = self.enc.unzip_device(t.data_ptr(), t.numel(), None if out is None else out.data_ptr(), 0 if out is None else total, tab, keys0)
+            finally:
+                if self.parallel_inflate is not None:
+                    self.enc.set_knob("inflate_par_min_kib", 0)
             good = (r["rc"] == 0) & (r["out_len"] == usize) & ((r["crc"] ^ np.uint32(0xFFFFFFFF)) == col(lambda e: e.crc, np.uint32))
             if out is not None:                                # every good entry's view in one split: cuts in front of and behind each
                 cuts = np.stack((tab["out_off"], tab["out_off"] + np.where(good, usize, 0).astype(np.uint64)), axis=1).reshape(-1)

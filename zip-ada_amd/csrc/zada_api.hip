@@ -1062,6 +1062,7 @@ static void ctx_release(zada_ctx *z) {
   bz2_destroy(&z->c);
   crypt_destroy(&z->c);
   inflate_destroy(&z->c);
+  inflate_par_destroy(&z->c);
   bunzip2_destroy(&z->c);
   unlzma_destroy(&z->c);
   unzip_destroy(&z->c);
@@ -1132,6 +1133,9 @@ int zada_set_knob(zada_ctx *z, const char *name, int value) {
   else if (!strcmp(name, "bz_small_wg")) { if (value < 0 || value > 1) return ZADA_E_INVALID; z->c.knob_bz_small_wg = value; }
   else if (!strcmp(name, "bz_lists")) { if (value < -1) return ZADA_E_INVALID; z->c.knob_bz_lists = value; }
   else if (!strcmp(name, "batch_mib")) { if (value < 1 || value > 1024) return ZADA_E_INVALID; z->c.knob_batch_mib = value; }
+  else if (!strcmp(name, "inflate_par_chunk_kib")) { if (value < 4 || value > 65536) return ZADA_E_INVALID; z->c.knob_infp_chunk_kib = value; }
+  else if (!strcmp(name, "inflate_par_repair_pct")) { if (value < 0 || value > 100) return ZADA_E_INVALID; z->c.knob_infp_repair_pct = value; }
+  else if (!strcmp(name, "inflate_par_min_kib")) { if (value < 0) return ZADA_E_INVALID; z->c.knob_infp_min_kib = value; }
   else if (!strcmp(name, "unzip_piece")) { if (value < 8 || value > 14) return ZADA_E_INVALID; z->c.knob_unzip_piece = value; }
   else if (!strcmp(name, "atoms_pct")) { if (value < 1 || value > 100) return ZADA_E_INVALID; z->c.knob_atoms_pct = value; z->c.ws.cap_atoms = 0; }   // (the next call books the entropy workspace anew)
   else if (!strcmp(name, "fix_stride")) { if (value < 0 || value > (int)PTOK_STRIDE) return ZADA_E_INVALID; z->c.knob_fix_stride = value; z->c.ws.cap_n = 0; }

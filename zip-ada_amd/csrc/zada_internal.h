@@ -11,6 +11,8 @@
 #include "zada_logic.h"
 #include "zada_sizing.h"
 
+struct zada_inflate_par_info;
+
 namespace zada {
 
 constexpr int ZADA_E_HIP_ = -3;
@@ -263,6 +265,10 @@ struct Ctx {
   void *bz = nullptr;                                // BZip2 state (zada_bz2.hip), made on first use
   void *zc = nullptr;                                // ZipCrypto state (zada_crypt.hip), made on first use
   void *inf = nullptr;                               // Inflate state (zada_inflate.hip), made on first use
+  void *infp = nullptr;                              // parallel Inflate state (zada_inflate_par.hip), made on first use
+  int knob_infp_chunk_kib = 64;                      // "inflate_par_chunk_kib": KiB of compressed stream per chunk (4 .. 65 536)
+  int knob_infp_repair_pct = 25;                     // "inflate_par_repair_pct": repairs a stream may take, in chunks per hundred (+ INFP_REPAIR_FLOOR)
+  int knob_infp_min_kib = 0;                         // "inflate_par_min_kib": zada_unzip_device sends Deflate entries of at least this many KiB of stream through the parallel path (0 = off)
   void *bzd = nullptr;                               // BZip2 reader state (zada_bunzip2.hip), made on first use
   void *ulz = nullptr;                               // LZMA reader state (zada_unlzma.hip), made on first use
   void *uz = nullptr;                                // archive reader state (zada_unzip.hip), made on first use
@@ -342,6 +348,10 @@ void bz2_destroy(Ctx *c);
 void crypt_destroy(Ctx *c);
 void inflate_destroy(Ctx *c);                       // Inflate (zada_inflate.hip)
 int inflate_crc_entries(Ctx *c, uint32_t E, const uint64_t *out, const uint64_t *out_len, uint32_t *regs);   // ... its k_inf_crc over outputs in device memory
+void inflate_par_destroy(Ctx *c);                   // parallel Inflate (zada_inflate_par.hip)
+// ... one stream through it.  0: done; 1: not taken (the record says why), nothing was written to d_out and the caller runs the one-wave decoder; < 0: an error
+int inflate_par_try(Ctx *c, int format, const void *d_in, uint64_t n_in, void *d_out, uint64_t cap, uint64_t *out_len, uint64_t *in_used, uint32_t *crc_inout);
+void inflate_par_record(Ctx *c, ::zada_inflate_par_info *get, const ::zada_inflate_par_info *set);   // the record zada_inflate_par_last gives: read and / or replaced
 void bunzip2_destroy(Ctx *c);                       // the BZip2 reader (zada_bunzip2.hip)
 void unlzma_destroy(Ctx *c);                        // the LZMA reader (zada_unlzma.hip)
 void unzip_destroy(Ctx *c);                         // the archive reader (zada_unzip.hip)
