@@ -450,6 +450,87 @@ uint64_t zada_zip_bound_ex(int count, const zada_zip_entry *ent, uint64_t archiv
 int zada_zip_device_ex(zada_ctx *ctx, int method, int count, const zada_zip_entry *ent, void *d_archive, uint64_t cap, uint64_t archive_base,
                        const zada_zip_crypt *crypt, uint64_t *archive_len, zada_zip_result *res);
 
+/* ---- ReZip: an archive in device memory recompressed into device memory, the smallest stream per entry (tools/rezip_lib.adb) ------
+ * What `rezip -int` does: every entry of the source archive is extracted (zada_unzip_device's launches; size and CRC-32 are held against the row:
+ * a mismatch ends the call with ZADA_E_DATA and the entry's index), compressed with each considered approach, and the new archive keeps per entry the
+ * smallest stream -- the source's own stream ("original") when nothing beats it.  No entry byte crosses the host; the source is never written.
+ * ent [i], in the order the entries are to be written: in_off, n_in the payload in the source (d_src, src_len); usize, crc the directory's; method the
+ * source's zip type (0, 8, 9, 12, 14); flags, version, time the LOCAL header's bit flag, version needed and DOS time (kept in the new headers: the
+ * flag and 0xFFF5, bit 1 set again when the winner ends on a marker); name, name_len the bytes of the new headers (HOST memory).
+ * approaches: a bit per approach in the reference's order: 0 original (always taken as set), 1 Preselection_2, 2 Preselection_1, 3 Shrink_1, 4 Reduce_4,
+ *   5 Deflate_3, 6 Deflate_R, 7 BZip2_3, 8 BZip2_2, 9 BZip2_1, 10 LZMA_3, 11 LZMA_2.  ZADA_RZ_DEFAULT is every approach built here.  Bits 3 and 4 are
+ *   ZADA_E_INVALID by name: Shrink_1 and Reduce_4 have no encoder here -- a divergence from `rezip -int`, which tries them on entries of at most
+ *   6 000 and 9 000 bytes and may choose their stream there.
+ * formats: a bit per zip type the result may hold: 0 Store, 1 Deflate, 2 Deflate64, 3 BZip2, 4 LZMA (ZADA_RZ_ALL_FORMATS, _DEFLATE_OR_STORE,
+ *   _FAST_DECOMPRESSION as rezip_lib.ads:46-54).  A single-method approach is considered when its format is in the set, the Preselections only with
+ *   all formats; an original whose format is not in the set is forced out, even at a larger size (rezip_lib.adb:876-886).
+ * The choice is the considered approach with the smallest (size, rank); a stream not shorter than its input counts as Store of usize bytes
+ * (Compress_Data's fallback).  Every distinct method of a group of entries (groups bounded by "batch_mib"; an entry above 4 MiB alone) runs ONE
+ * zada_zip_device_ex launch sequence over exactly the entries that need it, in ascending method order, into a holding buffer of the context: at
+ * most (distinct methods) x (the group's bytes + 76 per entry + 98); a beaten stream's room is not reused before the group ends.  The group is placed
+ * once by the table-driven copy: headers, winners from the holding buffer, "original" winners straight from the source's bytes.
+ * An LZMA_3 entry the coder refuses (ZADA_E_REFERENCE) drops that approach for that entry (res [i].flags bit 1); it does not end the call.
+ * An entry whose name is empty or ends in '/' or '\' is dropped (res [i].flags bit 0).  More than 65 534 kept entries are ZADA_E_TOO_LARGE.
+ * Headers are ReZip's, not Zip.Create's: made-by 20, no extra field but the Zip64 extension (20 bytes local, 28 central) where
+ * Needs_Local_Zip_64_Header_Extension says so, the Zip64 end records only when an entry needed it, then the comment (comment_len = 0: deleted).
+ * archive_base is added to every offset.  Divergence: the CRC-32 of the headers is always ent [i].crc, which the extraction has confirmed; the
+ * reference keeps the local header's field when it runs no encoder (a source written with data descriptors then keeps 0 there).
+ * Divergence: a duplicate among the names of the table is refused -- so two names a caller has made equal by lowering their case, which the
+ * reference, lowering after Zip.Load has accepted them, writes both.
+ * res [i]: the winning approach, zip type, CRC-32, compressed size, offset of the local header.  sizes (may be NULL): count x 12 values, the size
+ * every approach reached, all ones where it was not tried.  Argument checks, each ZADA_E_INVALID with the entry's index: a range beyond the source, an
+ * unknown source method, an encrypted entry, a duplicate name, an archive buffer that overlaps the source; 1 TiB is ZADA_E_TOO_LARGE.  Nothing is
+ * written outside [d_archive, d_archive + cap); "archive buffer too small" is ZADA_E_INVALID; zada_rezip_bound is an upper bound on *archive_len.
+ * The call synchronises before it returns; zada_last_timing holds the launches of all groups, equal names added up. */
+enum { ZADA_RZ_DEFAULT = 0x0FE7, ZADA_RZ_ALL_FORMATS = 0x1F, ZADA_RZ_DEFLATE_OR_STORE = 0x03, ZADA_RZ_FAST_DECOMPRESSION = 0x17 };
+typedef struct {
+  uint64_t in_off, n_in, usize;
+  uint32_t crc, time;
+  uint16_t method, flags, version, pad;
+  uint32_t name_len;
+  const uint8_t *name;
+} zada_rezip_entry;
+typedef struct { int32_t rc, approach; uint16_t zip_type, flags; uint32_t crc; uint64_t csize, offset; } zada_rezip_result;
+uint64_t zada_rezip_bound(int count, const zada_rezip_entry *ent, uint64_t comment_len);
+int zada_rezip_device(zada_ctx *ctx, const void *d_src, uint64_t src_len, int count, const zada_rezip_entry *ent, uint32_t approaches, uint32_t formats,
+                      void *d_archive, uint64_t cap, uint64_t archive_base, const uint8_t *comment, uint32_t comment_len, uint64_t *archive_len,
+                      zada_rezip_result *res, uint64_t *sizes);
+
+/* ---- Comp_Zip: two archives that lie in device memory, compared entry by entry (tools/comp_zip_prc.adb) -----------------
+ * zada_compare_device: the first offset at which the n bytes at device addresses d_a and d_b differ, or n if they are equal, in *first_diff.  Both
+ * addresses may have any byte alignment, in any relation to each other; neither buffer is written, and no byte in front of d_a / d_b or at or behind
+ * d_a + n / d_b + n counts (the kernel's 16-byte loads stay inside the 16-byte words that hold a byte of the buffers).  The buffers are cut into
+ * pieces of 16 KiB, one wave each: 16-byte loads from d_a's word boundary on -- the other side through aligned loads too, two words funnelled into
+ * one where the alignments differ --, xor, the first set bit's byte, a minimum across the wave and one 64-bit atomic minimum per piece that found a
+ * difference; a piece behind a difference already known ends at once.  n = 0 gives 0; a null address with n > 0 is ZADA_E_INVALID, n of 1 TiB or
+ * more ZADA_E_TOO_LARGE.  The call synchronises the context's stream before it returns.
+ *
+ * zada_compzip_device: `count` pairs of entries, a [i] a row of archive 1's directory and b [i] the row of the same name in archive 2 (rows as for
+ * zada_unzip_device; out_off is ignored) or a row with ZADA_CZ_ABSENT in its flags where archive 2 has no such entry.  Group by group -- consecutive
+ * pairs, both sides of a group within "batch_mib" MiB of workspace of the context, or a single pair -- both sides are extracted through
+ * zada_unzip_device's launches into two arenas in which a pair's two copies lie at the same offset (the same 16-byte phase: the aligned path of the
+ * kernel above), then compared by ONE launch of that kernel over a table of the group's pieces.  No entry byte crosses the host; the archives are never
+ * written; keys0 are the keys of the password of both archives (NULL: none; an encrypted row is then ZADA_E_INVALID).
+ * res [i]: rc_a, rc_b what the decoders said (ZADA_OK, ZADA_E_DATA, ZADA_E_PASSWORD), crc_a, crc_b the CRC-32 registers of the decoded bytes
+ * (started from 0xFFFFFFFF; the caller compares them with the directory), len_a, len_b the decoded lengths, and the verdict of Compare_1_file
+ * (comp_zip_prc.adb:102-143) on the decoded bytes:
+ *   ZADA_CZ_OK        : equal; compared = their length
+ *   ZADA_CZ_DIFFERENT : "Difference at position" `position` (1-based)
+ *   ZADA_CZ_SHORTER   : "Shorter in" archive 2 "at position" `position` = len_b + 1
+ *   ZADA_CZ_LONGER    : "Longer in" archive 2
+ *   ZADA_CZ_MISSING   : b [i] is absent; nothing of the pair is extracted
+ *   ZADA_CZ_DAMAGED   : rc_a or rc_b is not ZADA_OK (the reference ends with the reader's exception there); nothing is compared
+ * `compared` counts the equal bytes in front of the verdict.  A damaged entry is its pair's verdict, not the call's failure: the call returns ZADA_OK
+ * unless an argument is refused -- the checks of zada_unzip_device without the output ranges, each with the pair's index and the archive's number in
+ * zada_last_error -- or the device fails.  It synchronises the context's stream before it returns; zada_last_timing then holds the launches of every group and side
+ * (zada_unzip_device's phases and compzip:k_cz_compare), the times of equal names added up. */
+enum { ZADA_CZ_OK = 0, ZADA_CZ_DIFFERENT = 1, ZADA_CZ_SHORTER = 2, ZADA_CZ_LONGER = 3, ZADA_CZ_MISSING = 4, ZADA_CZ_DAMAGED = 5 };
+enum { ZADA_CZ_ABSENT = 0x80 };   /* zada_unzip_entry.flags of a row of archive 2: no entry of that name */
+typedef struct { int32_t verdict, rc_a, rc_b; uint32_t crc_a, crc_b, pad; uint64_t len_a, len_b, position, compared; } zada_compzip_result;
+int zada_compare_device(zada_ctx *ctx, const void *d_a, const void *d_b, uint64_t n, uint64_t *first_diff);
+int zada_compzip_device(zada_ctx *ctx, const void *d_archive_a, uint64_t len_a, const void *d_archive_b, uint64_t len_b, int count,
+                        const zada_unzip_entry *a, const zada_unzip_entry *b, const uint32_t keys0[3], zada_compzip_result *res);
+
 /* ---- One stream over several contexts (GPUs) -------------------------------------------------------------------
  * The reference compresses an entry as ONE sequential stream (a 32 KiB window, a lazy-match state machine, a flush of the
  * LZ buffer every 65 536 atoms and the block chooser's state all run through it: lz77.adb:827-933,

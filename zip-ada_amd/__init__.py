@@ -119,6 +119,11 @@ class UserAbort(Exception):
     """zip-compress.ads:149."""
 
 
+RZ_APPROACHES = ("original", "presel_2", "presel_1", "shrink", "reduce_4", "deflate_3", "deflate_r", "bzip2_3", "bzip2_2", "bzip2_1", "lzma_3", "lzma_2")
+RZ_DEFAULT = 0x0FE7                                  # zada.h ZADA_RZ_DEFAULT: every approach built here (not shrink, not reduce_4)
+RZ_ALL_FORMATS, RZ_DEFLATE_OR_STORE, RZ_FAST_DECOMPRESSION = 0x1F, 0x03, 0x17       # bits: Store, Deflate, Deflate64, BZip2, LZMA (rezip_lib.ads:46-54)
+RZ_NOT_TRIED = 0xFFFFFFFFFFFFFFFF
+
 _lib = None
 
 
@@ -226,6 +231,13 @@ def load_library():
         L.zada_zip_bound_ex.restype = u64
         L.zada_zip_bound_ex.argtypes = [i32, vp, u64, i32]
         L.zada_zip_device_ex.argtypes = [vp, i32, i32, vp, vp, u64, u64, vp, u64p, vp]
+    if hasattr(L, "zada_rezip_device"):              # (likewise: ReZip on device memory)
+        L.zada_rezip_bound.restype = u64
+        L.zada_rezip_bound.argtypes = [i32, vp, u64]
+        L.zada_rezip_device.argtypes = [vp, vp, u64, i32, vp, ctypes.c_uint32, ctypes.c_uint32, vp, u64, u64, vp, ctypes.c_uint32, u64p, vp, vp]
+    if hasattr(L, "zada_compare_device"):            # (likewise: Comp_Zip on device memory)
+        L.zada_compare_device.argtypes = [vp, vp, vp, u64, u64p]
+        L.zada_compzip_device.argtypes = [vp, vp, u64, vp, u64, i32, vp, vp, u32p, vp]
     L.zada_bz2_last_blocks.restype = ctypes.c_uint64
     L.zada_bz2_last_blocks.argtypes = [vp, vp, u64]
     L.zada_crc32_combine.restype = ctypes.c_uint32
@@ -989,6 +1001,71 @@ class Encoder:
             self._err(rc, "zada_zip_device_ex")
         return alen.value, res
 
+    # ---- ReZip on device memory (include/zada.h "an archive in device memory recompressed into device memory") ----
+    @staticmethod
+    def rezip_dtypes():
+        """(dtype of zada_rezip_entry, dtype of zada_rezip_result) as numpy structured types."""
+        import numpy as np
+        return (np.dtype([("in_off", "<u8"), ("n_in", "<u8"), ("usize", "<u8"), ("crc", "<u4"), ("time", "<u4"), ("method", "<u2"), ("flags", "<u2"), ("version", "<u2"),
+                          ("pad", "<u2"), ("name_len", "<u4"), ("pad2", "<u4"), ("name", "<u8")]),
+                np.dtype([("rc", "<i4"), ("approach", "<i4"), ("zip_type", "<u2"), ("flags", "<u2"), ("crc", "<u4"), ("csize", "<u8"), ("offset", "<u8")]))
+
+    def rezip_bound(self, entries, comment_len=0):
+        """zada_rezip_bound: an upper bound on the archive rezip_device makes of `entries`."""
+        import numpy as np
+        ent = np.ascontiguousarray(entries, dtype=self.rezip_dtypes()[0])
+        return int(self.lib.zada_rezip_bound(len(ent), ent.ctypes.data if len(ent) else None, comment_len))
+
+    def rezip_device(self, d_src_ptr, src_len, entries, d_archive_ptr, cap, approaches=RZ_DEFAULT, formats=RZ_ALL_FORMATS, archive_base=0, comment=b""):
+        """zada_rezip_device: `entries` is a numpy structured array of rezip_dtypes () [0] rows (name: HOST addresses the caller keeps alive).  Returns
+        (the archive's length, the structured array of results, the count x 12 matrix of sizes by approach, all ones where not tried)."""
+        import numpy as np
+        dt_e, dt_r = self.rezip_dtypes()
+        ent = np.ascontiguousarray(entries, dtype=dt_e)
+        res = np.zeros(len(ent), dtype=dt_r)
+        sizes = np.zeros((len(ent), 12), dtype=np.uint64)
+        alen = ctypes.c_uint64(0)
+        keep = ctypes.create_string_buffer(bytes(comment), max(len(comment), 1))
+        rc = self.lib.zada_rezip_device(self.ctx, d_src_ptr, src_len, len(ent), ent.ctypes.data if len(ent) else None, approaches, formats, d_archive_ptr, cap, archive_base,
+                                        ctypes.addressof(keep) if comment else None, len(comment), ctypes.byref(alen), res.ctypes.data if len(ent) else None,
+                                        sizes.ctypes.data if len(ent) else None)
+        if rc != 0:
+            self._err(rc, "zada_rezip_device")
+        return alen.value, res, sizes
+
+    # ---- Comp_Zip on device memory (include/zada.h "two archives that lie in device memory, compared entry by entry") ----
+    def compare_device(self, d_a_ptr, d_b_ptr, n):
+        """zada_compare_device: the first offset at which the n bytes at the two device addresses (any alignment) differ, or n."""
+        first = ctypes.c_uint64(0)
+        rc = self.lib.zada_compare_device(self.ctx, d_a_ptr, d_b_ptr, n, ctypes.byref(first))
+        if rc != 0:
+            self._err(rc, "zada_compare_device")
+        return first.value
+
+    @staticmethod
+    def compzip_dtype():
+        """dtype of zada_compzip_result as a numpy structured type."""
+        import numpy as np
+        return np.dtype([("verdict", "<i4"), ("rc_a", "<i4"), ("rc_b", "<i4"), ("crc_a", "<u4"), ("crc_b", "<u4"), ("pad", "<u4"), ("len_a", "<u8"), ("len_b", "<u8"),
+                         ("position", "<u8"), ("compared", "<u8")])
+
+    def compzip_device(self, d_a_ptr, len_a, d_b_ptr, len_b, rows_a, rows_b, keys0=None):
+        """zada_compzip_device: rows_a / rows_b are numpy structured arrays of unzip_dtypes () [0] rows, pair by pair (CZ_ABSENT in a row of rows_b's
+        flags: archive 2 has no such entry); keys0 the keys of the password or None.  Returns the structured array of results (compzip_dtype ()).
+        An argument the call refuses raises ZadaError."""
+        import numpy as np
+        dt_e = self.unzip_dtypes()[0]
+        ra, rb = np.ascontiguousarray(rows_a, dtype=dt_e), np.ascontiguousarray(rows_b, dtype=dt_e)
+        if len(ra) != len(rb):
+            raise ValueError("compzip_device: %d rows of archive 1, %d of archive 2" % (len(ra), len(rb)))
+        res = np.zeros(len(ra), dtype=self.compzip_dtype())
+        k = (ctypes.c_uint32 * 3)(*keys0) if keys0 is not None else None
+        rc = self.lib.zada_compzip_device(self.ctx, d_a_ptr, len_a, d_b_ptr, len_b, len(ra), ra.ctypes.data if len(ra) else None, rb.ctypes.data if len(ra) else None, k,
+                                          res.ctypes.data if len(ra) else None)
+        if rc != 0:
+            self._err(rc, "zada_compzip_device")
+        return res
+
     def lz77_tokens(self, data, method=Method.Deflate_3):
         import numpy as np
         n = len(data)
@@ -1297,7 +1374,8 @@ class ZipCreate:
 
 class ZipEntry:
     """One entry of an archive's central directory (Zip.Zip_Info's Dir_node)."""
-    __slots__ = ("name", "raw_name", "method", "flags", "crc", "csize", "usize", "header_offset", "data_offset", "dos_time", "encrypted")
+    __slots__ = ("name", "raw_name", "method", "flags", "crc", "csize", "usize", "header_offset", "data_offset", "dos_time", "encrypted",
+                 "local_version", "local_flags", "local_time")      # the local header's version needed, bit flag and DOS time (what ReZip keeps)
 
     def __repr__(self):
         return "ZipEntry(%r, method=%d, csize=%d, usize=%d)" % (self.name, self.method, self.csize, self.usize)
@@ -1424,6 +1502,7 @@ class ZipInfo:
                 if row[:4] != b"PK\x03\x04":
                     raise ZadaError("ZipInfo.load: entry %r: no local header at %d" % (e.name, h))
                 lnl, lxl = struct.unpack_from("<HH", row, 26)
+                e.local_version, e.local_flags, _, e.local_time = struct.unpack_from("<HHHI", row, 4)
                 e.data_offset = h + 30 + lnl + lxl
                 if e.data_offset + e.csize > n:
                     raise ZadaError("ZipInfo.load: entry %r: its data lie beyond the file" % e.name)
@@ -1624,3 +1703,204 @@ class UnZip:
                 else:
                     res[k] = self._verdict(E[j], int(r["rc"][j]), int(r["out_len"][j]), int(r["crc"][j]))
         return self._finish(ents, res, test_only, errors)
+
+
+CZ_OK, CZ_DIFFERENT, CZ_SHORTER, CZ_LONGER, CZ_MISSING, CZ_DAMAGED = range(6)      # zada_compzip_result.verdict
+CZ_ABSENT = 0x80                                                                    # zada_unzip_entry.flags: archive 2 has no entry of that name
+
+
+class CompZipResult:
+    """What Comp_Zip_Prc counts (comp_zip_prc.adb:27-35, 158-172): total_1, total_2, common, size_failures, compare_failures, missing_1_in_2,
+    just_a_directory, missing_2_in_1, total_bytes and total_differences = size_failures + compare_failures + missing_1_in_2 + missing_2_in_1 +
+    damaged.  damaged counts the pairs of which a side did not decode or did not meet its directory's size and CRC-32: the reference ends with the
+    reader's exception there, this one goes on and counts them as differences.
+    entries: per entry of archive 1, in the order of the traversal, (name, verdict, position, compared, error, key) -- verdict one of CZ_*, position
+    the 1-based position of CZ_DIFFERENT / CZ_SHORTER, compared the equal bytes in front of the verdict, error the exception of a CZ_DAMAGED pair, key
+    the name the tool goes by: the raw name's bytes with '\\' turned into '/'.  result [x] finds an entry by its key (bytes) or its display name."""
+    _COUNTERS = ("total_1", "total_2", "common", "size_failures", "compare_failures", "missing_1_in_2", "just_a_directory", "missing_2_in_1", "damaged",
+                 "total_bytes", "total_differences")
+
+    def __init__(self):
+        for nm in self._COUNTERS:
+            setattr(self, nm, 0)
+        self.entries = []
+
+    def __getitem__(self, name):
+        for e in self.entries:
+            if e[5 if isinstance(name, bytes) else 0] == name:
+                return e
+        raise KeyError(name)
+
+    def __repr__(self):
+        return "CompZipResult(%s)" % ", ".join("%s=%d" % (nm, getattr(self, nm)) for nm in self._COUNTERS)
+
+
+def zip_load_order(info, who="Zip.Load"):
+    """The entries of a ZipInfo in the order Zip.Traverse visits them: ascending by the raw name with '\\' turned into '/', compared byte by byte
+    (Normalize and Insert_into_tree, zip.adb:152-166, 195-237, case-sensitive) -- as [(key, ZipEntry)].  Two entries with the same key raise, as Load's
+    error_on_duplicate does."""
+    rows = sorted(((e.raw_name.replace(b"\\", b"/"), k, e) for k, e in enumerate(info.entries)), key=lambda r: (r[0], r[1]))
+    for x, y in zip(rows, rows[1:]):
+        if x[0] == y[0]:
+            raise ZadaError("%s: the same full entry name (%r) appears twice in the archive's directory" % (who, x[2].name))
+    return [(r[0], r[2]) for r in rows]
+
+
+class CompZip:
+    """Comp_Zip_Prc (tools/comp_zip_prc.adb) on two archives that lie in device memory: every entry of archive 1, in Zip.Traverse's order, is looked up
+    by name in archive 2 (case-sensitive, '\\' = '/'), both are extracted on the device and compared there (zada_compzip_device); no entry byte
+    crosses the host.  Every method the reader decodes takes part (Store, Deflate, Deflate64, BZip2, LZMA); any other raises UnsupportedMethod in
+    UnZip's words, an encrypted entry without a password WrongPassword."""
+
+    def __init__(self, encoder):
+        self.enc = encoder
+
+    def compare_device(self, info1, info2, password=None):
+        """info1, info2: ZipInfo.load_device of two tensors on the encoder's device; password: of both archives.  -> CompZipResult"""
+        import numpy as np
+        import torch
+        t1, t2 = info1.device_data, info2.device_data
+        if t1 is None or t2 is None:
+            raise ZadaError("CompZip.compare_device: the ZipInfos were not made by ZipInfo.load_device")
+        for t in (t1, t2):
+            if t.device.type != "cuda" or t.device.index != self.enc.device:
+                raise ZadaError("CompZip.compare_device: an archive tensor lies on %s, not on the encoder's device" % t.device)
+        order1 = zip_load_order(info1, "CompZip.compare_device (archive 1)")
+        dir2 = dict(zip_load_order(info2, "CompZip.compare_device (archive 2)"))
+        reader = UnZip(self.enc, bzip2=True, lzma=True)
+        pairs = [(key, e, dir2.get(key)) for key, e in order1]
+        for _, e1, e2 in pairs:
+            for e in (e1, e2) if e2 is not None else (e1,):        # (the C call looks at every row of archive 1, the missing pairs' too)
+                ex = reader._unsupported(e)
+                if ex is None and e.encrypted and password is None:
+                    ex = WrongPassword("entry %r is encrypted and no password was given" % e.name)
+                if ex is not None:
+                    raise ex
+        n = len(pairs)
+        dt = self.enc.unzip_dtypes()[0]
+
+        def table(ents):
+            # column by column, as in UnZip.extract_device; a missing entry is a row of zeros with CZ_ABSENT
+            col = lambda f, dt=np.uint64: np.fromiter((0 if e is None else f(e) for e in ents), dt, n)
+            tab = np.zeros(n, dtype=dt)
+            crypt, method = col(lambda e: e.encrypted, np.uint8), col(lambda e: e.method, np.uint16)
+            tab["in_off"], tab["n_in"], tab["method"] = col(lambda e: e.data_offset), col(lambda e: e.csize), method
+            # (a stored entry gets room for what is stored, as there)
+            tab["cap"] = np.where(method == 0, col(lambda e: max(e.csize - 12, 0) if e.encrypted else e.csize), col(lambda e: e.usize))
+            tab["flags"] = crypt | col(lambda e: e.flags & 2, np.uint8) | np.fromiter((CZ_ABSENT if e is None else 0 for e in ents), np.uint8, n)
+            tab["check"] = col(lambda e: ((e.dos_time >> 8) if e.flags & 8 else (e.crc >> 24)) & 0xFF, np.uint8)
+            return tab
+        out = CompZipResult()
+        out.total_2 = len(info2.entries)
+        if n:
+            keys0 = self.enc.crypt_init_keys(password) if password is not None else None
+            torch.cuda.current_stream(t1.device).synchronize()
+            r = self.enc.compzip_device(t1.data_ptr(), t1.numel(), t2.data_ptr(), t2.numel(), table([p[1] for p in pairs]), table([p[2] for p in pairs]), keys0)
+        for k, (key, e1, e2) in enumerate(pairs):
+            out.total_1 += 1
+            v, pos, cmpd, err = int(r["verdict"][k]), int(r["position"][k]), int(r["compared"][k]), None
+            if v == CZ_MISSING:
+                if key[-1:] == b"/":                       # (the traversal's names have no '\\' left)
+                    out.just_a_directory += 1
+                out.missing_1_in_2 += 1
+            else:
+                for e, side in ((e1, "a"), (e2, "b")):
+                    rc = int(r["rc_" + side][k])
+                    ex = WrongPassword("entry %r: wrong password" % e.name) if rc == E_PASSWORD else reader._verdict(e, rc, int(r["len_" + side][k]), int(r["crc_" + side][k]))
+                    if ex is not None and err is None:
+                        err = ex
+                if err is not None:
+                    v, pos, cmpd = CZ_DAMAGED, 0, 0
+                    out.damaged += 1
+                elif v in (CZ_SHORTER, CZ_LONGER):
+                    out.size_failures += 1
+                elif v == CZ_DIFFERENT:
+                    out.compare_failures += 1
+                else:
+                    out.total_bytes += cmpd
+            out.entries.append((e1.name, v, pos, cmpd, err, key))
+        out.common = out.total_1 - out.missing_1_in_2
+        out.missing_2_in_1 = out.total_2 - out.common
+        out.total_differences = out.size_failures + out.compare_failures + out.missing_1_in_2 + out.missing_2_in_1 + out.damaged
+        return out
+
+
+class ReZip:
+    """ReZip (tools/rezip_lib.adb, `rezip -int`) on an archive that lies in device memory: every entry is extracted and compressed on the device with
+    each considered approach, and the new archive keeps per entry the smallest stream, the source's own where nothing beats it (zada_rezip_device).
+    Divergences from the reference: Shrink_1 and Reduce_4, which it tries on entries of at most 6 000 and 9 000 bytes, are not built (their approaches
+    are refused by name); an LZMA_3 entry the coder refuses loses that approach instead of getting a stream that does not decode; more than 65 534
+    kept entries are refused; the headers carry the directory's CRC-32; with lower=True two names that differ only in case are refused as duplicates,
+    where the reference writes both."""
+    _FORMATS = {"all": RZ_ALL_FORMATS, "deflate_or_store": RZ_DEFLATE_OR_STORE, "fast_decompression": RZ_FAST_DECOMPRESSION}
+
+    def __init__(self, encoder):
+        self.enc = encoder
+
+    def rezip_device(self, info, formats="all", approaches=None, touch=None, lower=False, delete_comment=False, report=False):
+        """info: ZipInfo.load_device of a tensor on the encoder's device.  formats: "all", "deflate_or_store", "fast_decompression" or a bit set;
+        approaches: None (every built one), a bit mask, or names of RZ_APPROACHES; touch: one DOS time stamp for all entries; lower: names in lower
+        case; delete_comment: the archive comment is left out.  Entries are written in Zip.Load's order (zip_load_order; a duplicate raises).
+        Returns the new archive as a torch.uint8 tensor on the device, or (tensor, report) with report = {"entries": [(name, {approach: size},
+        choice)], "totals": {approach: {"count": wins, "saved": bytes saved against original}}}."""
+        import numpy as np
+        import torch
+        t = info.device_data
+        if t is None:
+            raise ZadaError("ReZip.rezip_device: the ZipInfo was not made by ZipInfo.load_device")
+        if t.device.type != "cuda" or t.device.index != self.enc.device:
+            raise ZadaError("ReZip.rezip_device: the archive tensor lies on %s, not on the encoder's device" % t.device)
+        fmt = self._FORMATS[formats] if isinstance(formats, str) else int(formats)
+        if approaches is None:
+            mask = RZ_DEFAULT
+        elif isinstance(approaches, int):
+            mask = approaches
+        else:
+            mask = 0
+            for a in approaches:
+                mask |= 1 << RZ_APPROACHES.index(a)
+        order = zip_load_order(info, "ReZip.rezip_device")
+        reader = UnZip(self.enc, bzip2=True, lzma=True)
+        for _, e in order:
+            ex = reader._unsupported(e)
+            if ex is not None:
+                raise ex
+        names = [(key.decode("latin-1").lower().encode("latin-1") if lower else key) for key, _ in order]
+        n = len(order)
+        dt = self.enc.rezip_dtypes()[0]
+        tab = np.zeros(n, dtype=dt)
+        blob = np.frombuffer(b"".join(names) + b"\0", dtype=np.uint8)
+        E = [e for _, e in order]
+        col = lambda f, d=np.uint64: np.fromiter((f(e) for e in E), d, n)
+        nlen = np.fromiter((len(nm) for nm in names), np.uint64, n)
+        tab["in_off"], tab["n_in"], tab["usize"], tab["crc"] = col(lambda e: e.data_offset), col(lambda e: e.csize), col(lambda e: e.usize), col(lambda e: e.crc, np.uint32)
+        tab["time"] = col(lambda e: e.local_time, np.uint32) if touch is None else touch
+        tab["method"], tab["flags"], tab["version"] = col(lambda e: e.method, np.uint16), col(lambda e: e.local_flags, np.uint16), col(lambda e: e.local_version, np.uint16)
+        tab["name_len"], tab["name"] = nlen, np.uint64(blob.ctypes.data) + np.cumsum(nlen) - nlen
+        comment = b"" if delete_comment else bytes(info.comment)
+        cap = self.enc.rezip_bound(tab, len(comment))
+        out = torch.empty(cap, dtype=torch.uint8, device=t.device)
+        torch.cuda.current_stream(t.device).synchronize()
+        alen, res, sizes = self.enc.rezip_device(t.data_ptr(), t.numel(), tab, out.data_ptr(), cap, mask, fmt, 0, comment)
+        if not report:
+            return out[:alen]
+        rep = {"entries": [], "totals": {a: {"count": 0, "saved": 0} for a in RZ_APPROACHES}}
+        for k, nm in enumerate(names):
+            if res["flags"][k] & 1:
+                continue
+            row = {a: int(sizes[k][j]) for j, a in enumerate(RZ_APPROACHES) if int(sizes[k][j]) != RZ_NOT_TRIED}
+            choice = RZ_APPROACHES[int(res["approach"][k])]
+            rep["entries"].append((nm, row, choice))
+            rep["totals"][choice]["count"] += 1
+            rep["totals"][choice]["saved"] += row["original"] - row[choice]
+        return out[:alen], rep
+
+    def rezip(self, archive_bytes, **kw):
+        """rezip_device for an archive in host bytes: -> bytes, or (bytes, report)."""
+        import numpy as np
+        import torch
+        t = torch.from_numpy(np.frombuffer(bytes(archive_bytes), dtype=np.uint8).copy()).to(torch.device("cuda", self.enc.device))
+        r = self.rezip_device(ZipInfo.load_device(t), **kw)
+        if isinstance(r, tuple):
+            return r[0].cpu().numpy().tobytes(), r[1]
+        return r.cpu().numpy().tobytes()

@@ -384,6 +384,15 @@ static int zx_store_group(ZxCall &Z, int g0, int g1) {
   return rc;
 }
 
+// k_zw_place for zada_rezip_device (zada_rezip.hip): the pieces of a group -- pad = 1: src counts from the blob -- placed and waited for
+int zip_place_pieces(Ctx *c, const std::vector<uint8_t> &blob, std::vector<ZwPiece> &pieces, const char *mark) {
+  if (!c->zw) c->zw = new (std::nothrow) ZwState();
+  if (!c->zw) { c->err = "zip: no memory for the tables"; return ZADA_E_NOMEM; }
+  ZxCall Z;
+  Z.who = "zada_rezip_device"; Z.c = c; Z.S = (ZwState *)c->zw;
+  return zx_pieces(Z, blob, pieces, mark);
+}
+
 }  // namespace zada
 
 using namespace zada;
