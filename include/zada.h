@@ -531,6 +531,38 @@ int zada_compare_device(zada_ctx *ctx, const void *d_a, const void *d_b, uint64_
 int zada_compzip_device(zada_ctx *ctx, const void *d_archive_a, uint64_t len_a, const void *d_archive_b, uint64_t len_b, int count,
                         const zada_unzip_entry *a, const zada_unzip_entry *b, const uint32_t keys0[3], zada_compzip_result *res);
 
+/* ---- Find_Zip: a string searched in every entry of an archive that lies in device memory (tools/find_zip.adb) ------------
+ * zada_find_device: the n bytes at device address d_buf, at any byte alignment, taken as ONE entry.  text (HOST memory, text_len = 1 .. 1024
+ * bytes, find_zip.adb's max; 0 or more is ZADA_E_INVALID with a text that says so) is the search string; with ZADA_FZ_IGNORE_CASE in flags -- the
+ * reference's constant ignore_case -- the library upper-cases it and every byte of the buffer as Ada.Characters.Handling.To_Upper does on Latin-1
+ * (0x61 .. 0x7A, 0xE0 .. 0xF6 and 0xF8 .. 0xFE lose 0x20; 0xDF, 0xF7, 0xFF and everything else stay).  *occurrences is what the loop of
+ * find_zip.adb:64-84 counts: its ring of 1024 characters is all spaces when the entry starts, so this is the number of occurrences, overlapping
+ * ones included, of the string in (text_len - 1) spaces followed by the buffer's bytes -- a string that begins with spaces can match "in front of"
+ * the first byte.  *first is the 0-based offset of the LAST byte of the first occurrence, or n where there is none.  Nothing but the buffer's own
+ * bytes and those virtual spaces counts, and the buffer is never written: it is cut into pieces of 16 KiB, one wave each, read with 16-byte loads
+ * from its word boundary on, none of which touches a 16-byte word without a byte of the buffer in it; a lane upper-cases what it has to in
+ * registers and keeps the end positions whose last min (text_len, 8) bytes are the string's; a longer string is confirmed wave-wide, every lane
+ * comparing sixteen bytes of the string (staged once per workgroup in LDS) with the text in front of the position -- up to 1023 bytes into the
+ * piece before --, one vote per candidate; one 64-bit atomic add and one atomic minimum per piece that found any.  n = 0 gives 0 and 0; a null
+ * buffer with n > 0 is ZADA_E_INVALID, n of 1 TiB or more ZADA_E_TOO_LARGE.
+ *
+ * zada_findzip_device: `count` rows of an archive's directory (rows as for zada_unzip_device; out_off is ignored), in the order the caller wants them
+ * searched (Zip.Traverse's).  Group by group -- consecutive rows whose extracted bytes stay within "batch_mib" MiB of workspace of the context, or a
+ * single row -- the entries are extracted through zada_unzip_device's launches into one arena and searched there by ONE launch of the kernel above
+ * over a table of the group's pieces.  No entry byte crosses the host; the archive is never written; keys0 are the keys of the archive's password
+ * (NULL: none; an encrypted row is then ZADA_E_INVALID).  res [i]: rc, crc (the register, started from 0xFFFFFFFF) and out_len are the reader's
+ * (ZADA_OK, ZADA_E_DATA, ZADA_E_PASSWORD; the caller compares size and CRC-32 with the directory); for rc = ZADA_OK occurrences and first are as
+ * above, with n = out_len.  An entry that did not decode has occurrences = first = 0 and does not fail the call, which returns ZADA_OK unless an
+ * argument is refused -- zada_unzip_device's checks without the output ranges, each with the row's index in zada_last_error -- or the device fails.
+ * Both calls synchronise the context's stream before they return; zada_last_timing then holds their launches (find:k_fz_search; the reader's
+ * phases and findzip:k_fz_search, the times of equal names added up). */
+enum { ZADA_FZ_IGNORE_CASE = 1 };
+typedef struct { int32_t rc; uint32_t crc; uint64_t out_len, occurrences, first; } zada_findzip_result;
+int zada_find_device(zada_ctx *ctx, const void *d_buf, uint64_t n, const uint8_t *text, uint32_t text_len, uint32_t flags, uint64_t *occurrences,
+                     uint64_t *first);
+int zada_findzip_device(zada_ctx *ctx, const void *d_archive, uint64_t archive_len, int count, const zada_unzip_entry *ent, const uint32_t keys0[3],
+                        const uint8_t *text, uint32_t text_len, uint32_t flags, zada_findzip_result *res);
+
 /* ---- One stream over several contexts (GPUs) -------------------------------------------------------------------
  * The reference compresses an entry as ONE sequential stream (a 32 KiB window, a lazy-match state machine, a flush of the
  * LZ buffer every 65 536 atoms and the block chooser's state all run through it: lz77.adb:827-933,

@@ -238,6 +238,9 @@ def load_library():
     if hasattr(L, "zada_compare_device"):            # (likewise: Comp_Zip on device memory)
         L.zada_compare_device.argtypes = [vp, vp, vp, u64, u64p]
         L.zada_compzip_device.argtypes = [vp, vp, u64, vp, u64, i32, vp, vp, u32p, vp]
+    if hasattr(L, "zada_find_device"):               # (likewise: Find_Zip on device memory)
+        L.zada_find_device.argtypes = [vp, vp, u64, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, u64p, u64p]
+        L.zada_findzip_device.argtypes = [vp, vp, u64, i32, vp, u32p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, vp]
     L.zada_bz2_last_blocks.restype = ctypes.c_uint64
     L.zada_bz2_last_blocks.argtypes = [vp, vp, u64]
     L.zada_crc32_combine.restype = ctypes.c_uint32
@@ -268,6 +271,19 @@ def _password(password):
     if not pw:
         raise ZadaError("empty password (Password = \"\" means no encryption, zip-create.adb:221)")
     return pw
+
+
+FZ_IGNORE_CASE = 1         # ZADA_FZ_IGNORE_CASE
+FZ_MAX = 1024              # find_zip.adb's max: the longest search string
+
+
+def _search_text(text, check=True):
+    """A search string as the bytes Find_Zip sees: Character'Pos of every character, i.e. Latin-1, as passwords are.  check: a length outside
+    1 .. 1024 is a ValueError (Prepare_Search_String raises Constraint_Error there)."""
+    t = text.encode("latin-1") if isinstance(text, str) else bytes(text)
+    if check and not 1 <= len(t) <= FZ_MAX:
+        raise ValueError("a search string of %d bytes: find_zip takes 1 .. %d" % (len(t), FZ_MAX))
+    return t
 
 
 def _addr(buf):
@@ -1064,6 +1080,37 @@ class Encoder:
                                           res.ctypes.data if len(ra) else None)
         if rc != 0:
             self._err(rc, "zada_compzip_device")
+        return res
+
+    # ---- Find_Zip on device memory (include/zada.h "a string searched in every entry of an archive that lies in device memory") ----
+    def find_device(self, d_ptr, n, text, ignore_case=True):
+        """zada_find_device: the n bytes at the device address (any alignment) as one entry, text the search string (bytes, or str taken as Latin-1).
+        Returns (occurrences, first): what find_zip counts, and the offset of the last byte of the first occurrence, or n."""
+        text = _search_text(text, check=False)
+        occ, first = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        rc = self.lib.zada_find_device(self.ctx, d_ptr, n, text, len(text), FZ_IGNORE_CASE if ignore_case else 0, ctypes.byref(occ), ctypes.byref(first))
+        if rc != 0:
+            self._err(rc, "zada_find_device")
+        return occ.value, first.value
+
+    @staticmethod
+    def findzip_dtype():
+        """dtype of zada_findzip_result as a numpy structured type."""
+        import numpy as np
+        return np.dtype([("rc", "<i4"), ("crc", "<u4"), ("out_len", "<u8"), ("occurrences", "<u8"), ("first", "<u8")])
+
+    def findzip_device(self, d_archive_ptr, archive_len, entries, text, ignore_case=True, keys0=None):
+        """zada_findzip_device: `entries` is a numpy structured array of unzip_dtypes () [0] rows in the order they are to be searched, keys0 the keys of
+        the password or None.  Returns the structured array of results (findzip_dtype ()).  An argument the call refuses raises ZadaError."""
+        import numpy as np
+        text = _search_text(text, check=False)
+        ent = np.ascontiguousarray(entries, dtype=self.unzip_dtypes()[0])
+        res = np.zeros(len(ent), dtype=self.findzip_dtype())
+        k = (ctypes.c_uint32 * 3)(*keys0) if keys0 is not None else None
+        rc = self.lib.zada_findzip_device(self.ctx, d_archive_ptr, archive_len, len(ent), ent.ctypes.data if len(ent) else None, k, text, len(text),
+                                          FZ_IGNORE_CASE if ignore_case else 0, res.ctypes.data if len(ent) else None)
+        if rc != 0:
+            self._err(rc, "zada_findzip_device")
         return res
 
     def lz77_tokens(self, data, method=Method.Deflate_3):
@@ -1904,3 +1951,100 @@ class ReZip:
         if isinstance(r, tuple):
             return r[0].cpu().numpy().tobytes(), r[1]
         return r.cpu().numpy().tobytes()
+
+
+_L1_UPPER = bytes(c - 0x20 if 0x61 <= c <= 0x7A or 0xE0 <= c <= 0xF6 or 0xF8 <= c <= 0xFE else c for c in range(256))      # Ada.Characters.Handling.To_Upper
+_L1_LOWER = bytes(c + 0x20 if 0x41 <= c <= 0x5A or 0xC0 <= c <= 0xD6 or 0xD8 <= c <= 0xDE else c for c in range(256))      # ... To_Lower
+
+
+class FindZipResult:
+    """What Find_Zip reports (tools/find_zip.adb).  entries: per entry of the archive, in the order of the traversal, (name, occurrences, first,
+    error, key) -- occurrences what the loop of find_zip.adb:64-84 counts in the entry's decoded bytes, first the 0-based offset of the last byte of
+    the first occurrence (the entry's length where there is none), error the reader's exception for an entry that did not decode or did not meet its
+    size and CRC-32 (occurrences and first are then 0), key the name the tool goes by: the raw name's bytes with '\\' turned into '/'.
+    in_contents: [(key, occurrences)] with occurrences > 0; in_names: the keys that contain the string; damaged: how many entries carry an error --
+    the reference ends with the reader's exception at the first of them, this one goes on.  result [x] finds an entry by its key (bytes) or its
+    display name."""
+
+    def __init__(self):
+        self.entries, self.in_contents, self.in_names, self.damaged = [], [], [], 0
+
+    def __getitem__(self, name):
+        for e in self.entries:
+            if e[4 if isinstance(name, bytes) else 0] == name:
+                return e
+        raise KeyError(name)
+
+    def lines(self):
+        """The reference's output between "Searching string" and "Time elapsed", line by line: Put (occ, 5) and the name in lower case for every
+        entry whose contents hold the string, then every name that holds it."""
+        low = lambda key: key.translate(_L1_LOWER).decode("latin-1")
+        return (["%5d in [%s]'s contents" % (occ, low(key)) for key, occ in self.in_contents] +
+                [" Found in [%s]'s entry name" % low(key) for key in self.in_names])
+
+    def __repr__(self):
+        return "FindZipResult(in_contents=%d, in_names=%d, damaged=%d)" % (len(self.in_contents), len(self.in_names), self.damaged)
+
+
+class FindZip:
+    """Find_Zip (tools/find_zip.adb) on an archive that lies in device memory: every entry, in Zip.Traverse's order, is extracted on the device and
+    searched there for a string (zada_findzip_device); no entry byte crosses the host.  The names are searched on the host.  Every method the reader
+    decodes takes part (Store, Deflate, Deflate64, BZip2, LZMA); any other raises UnsupportedMethod in UnZip's words, an encrypted entry without a
+    password WrongPassword."""
+
+    def __init__(self, encoder):
+        self.enc = encoder
+
+    def find_device(self, info, text, ignore_case=True, password=None):
+        """info: ZipInfo.load_device of a tensor on the encoder's device; text: bytes, or a str taken as Latin-1 (1 .. 1024 bytes, else ValueError);
+        ignore_case: the reference's constant, True; password: the archive's.  -> FindZipResult"""
+        import numpy as np
+        import torch
+        text = _search_text(text)
+        t = info.device_data
+        if t is None:
+            raise ZadaError("FindZip.find_device: the ZipInfo was not made by ZipInfo.load_device")
+        if t.device.type != "cuda" or t.device.index != self.enc.device:
+            raise ZadaError("FindZip.find_device: the archive tensor lies on %s, not on the encoder's device" % t.device)
+        order = zip_load_order(info, "FindZip.find_device")
+        reader = UnZip(self.enc, bzip2=True, lzma=True)
+        for _, e in order:
+            ex = reader._unsupported(e)
+            if ex is None and e.encrypted and password is None:
+                ex = WrongPassword("entry %r is encrypted and no password was given" % e.name)
+            if ex is not None:
+                raise ex
+        n = len(order)
+        E = [e for _, e in order]
+        out = FindZipResult()
+        if n:
+            # the table, column by column, as in UnZip.extract_device (a stored entry gets room for what is stored)
+            col = lambda f, dt=np.uint64: np.fromiter((f(e) for e in E), dt, n)
+            tab = np.zeros(n, dtype=self.enc.unzip_dtypes()[0])
+            crypt, method = col(lambda e: e.encrypted, np.uint8), col(lambda e: e.method, np.uint16)
+            tab["in_off"], tab["n_in"], tab["method"] = col(lambda e: e.data_offset), col(lambda e: e.csize), method
+            tab["cap"] = np.where(method == 0, col(lambda e: max(e.csize - 12, 0) if e.encrypted else e.csize), col(lambda e: e.usize))
+            tab["flags"] = crypt | col(lambda e: e.flags & 2, np.uint8)
+            tab["check"] = col(lambda e: ((e.dos_time >> 8) if e.flags & 8 else (e.crc >> 24)) & 0xFF, np.uint8)
+            keys0 = self.enc.crypt_init_keys(password) if password is not None else None
+            torch.cuda.current_stream(t.device).synchronize()
+            r = self.enc.findzip_device(t.data_ptr(), t.numel(), tab, text, ignore_case, keys0)
+        for k, (key, e) in enumerate(order):
+            rc = int(r["rc"][k])
+            err = WrongPassword("entry %r: wrong password" % e.name) if rc == E_PASSWORD else reader._verdict(e, rc, int(r["out_len"][k]), int(r["crc"][k]))
+            occ, first = (0, 0) if err is not None else (int(r["occurrences"][k]), int(r["first"][k]))
+            out.damaged += err is not None
+            out.entries.append((e.name, occ, first, err, key))
+            if occ > 0:
+                out.in_contents.append((key, occ))
+        # Search_in_entry_name (find_zip.adb:150-159), on the host: Index (To_Upper (name), str) > 0
+        s = text.translate(_L1_UPPER) if ignore_case else text
+        out.in_names = [key for key, _ in order if (key.translate(_L1_UPPER) if ignore_case else key).find(s) >= 0]
+        return out
+
+    def find(self, archive_bytes, text, **kw):
+        """find_device for an archive in host bytes."""
+        import numpy as np
+        import torch
+        t = torch.from_numpy(np.frombuffer(bytes(archive_bytes), dtype=np.uint8).copy()).to(torch.device("cuda", self.enc.device))
+        return self.find_device(ZipInfo.load_device(t), text, **kw)

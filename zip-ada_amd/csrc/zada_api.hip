@@ -1068,6 +1068,7 @@ static void ctx_release(zada_ctx *z) {
   unzip_destroy(&z->c);
   zip_destroy(&z->c);
   rezip_destroy(&z->c);
+  find_destroy(&z->c);
   lzma_free(&z->c);
   free_workspace(&z->c);
   for (hipEvent_t e : z->c.ev_pool) hipEventDestroy(e);

@@ -274,6 +274,7 @@ struct Ctx {
   void *uz = nullptr;                                // archive reader state (zada_unzip.hip), made on first use
   void *zw = nullptr;                                // archive writer state (zada_zip.hip), made on first use
   void *rz = nullptr;                                // Comp_Zip state (zada_rezip.hip), made on first use
+  void *fz = nullptr;                                // Find_Zip state (zada_find.hip), made on first use
   int knob_unzip_piece = 14;                         // "unzip_piece" (test knob): log2 of the bytes of one piece of a stored entry (8 .. 14)
   void *lz_tab = nullptr; size_t cap_lz_tab = 0;     // LZMA (zada_lzma.hip): job table + results
   void *lz_save = nullptr; size_t cap_lz_save = 0;   // ... the coder's state between the launches of one stream
@@ -358,6 +359,7 @@ void unlzma_destroy(Ctx *c);                        // the LZMA reader (zada_unl
 void unzip_destroy(Ctx *c);                         // the archive reader (zada_unzip.hip)
 void zip_destroy(Ctx *c);                           // the archive writer (zada_zip.hip)
 void rezip_destroy(Ctx *c);                         // Comp_Zip (zada_rezip.hip)
+void find_destroy(Ctx *c);                          // Find_Zip (zada_find.hip)
 // ... its stored entries for the archive writer: entry k's len [k] > 0 bytes at device address src [k] copied to dst [k] and summed in one pass, in
 // pieces of 16 KiB (k_uz_store / k_uz_fold); crc [k] is in/out, the running register
 int unzip_store_entries(Ctx *c, uint32_t ns, const uint64_t *src, const uint64_t *dst, const uint64_t *len, uint32_t *crc);
