@@ -127,7 +127,8 @@ const char *zada_version(void);
  * does not), "lzma_segment" (one LZMA_3 stream coded in launches: log2 of the positions per segment of
  * the match producer, whose walks of segment k + 1 run beside the coder of segment k; 13 .. 30, 0 = by size: 2 ** 20 positions for streams from 2 MiB on, 2 ** 18 from 512 KiB on, none below,
  * -1 = all match sets before the coder starts), "lzma_waves" (one LZMA_3 stream alone: waves of its workgroup -- 0 or 4 = the wave that walks the stream's
- * chain and three helpers that take shares of its forks, 1 = that wave alone, as every entry of a batch has it).  None of them changes a byte.  One knob is a parameter of the reference instead: "lzma_dict" = LZMA.Encoding.Encode's
+ * chain and three helpers that take shares of its forks, 1 = that wave alone, as every entry of a batch has it), "trained_fork" (Trained_Compression:
+ * 1, the default = the trainer is coded and the stub decoded once per handle, 0 = every entry works through its whole stream).  None of them changes a byte.  One knob is a parameter of the reference instead: "lzma_dict" = LZMA.Encoding.Encode's
  * dictionary_size for LZMA_3 in bytes (0, the default: the entry's size, as Zip.Compress.LZMA_E passes it; lzma_enc.adb uses 32 KiB). */
 int zada_set_knob(zada_ctx *ctx, const char *name, int value);
 
@@ -759,6 +760,55 @@ int zada_test_llhc(zada_ctx *ctx, int max_bits, int n, uint32_t count, int waves
 int zada_test_radix_sort(zada_ctx *ctx, uint64_t n, int value_bytes, unsigned begin_bit, unsigned end_bit, int in_place, const uint32_t *keys, const void *vals,
                          uint32_t *keys_out, void *vals_out);
 int zada_test_scan(zada_ctx *ctx, uint64_t n, int in_place, const uint32_t *in, uint32_t *out, uint32_t *total);
+
+/* ---- Trained_Compression (trained/trained_compression.ads, .adb) for batches of messages in device memory ------
+ * Every message is coded as the tail of ONE LZMA stream -- Level_3, lc 3, lp 0, pb 2, dictionary_size 2 ** 19, a 5-byte header and no size field --
+ * whose head is training data both sides know (csrc/zada_trained.hip):
+ *   Encode_Trainer  the stub: LZMA.Encoding.Encode (trainer, end_marker => False).  The decoding side keeps it; it does not have the trainer.
+ *   Encode          LZMA.Encoding.Encode (trainer & data, end_marker => True) less its first `skip` bytes: the message.
+ *   Decode          LZMA.Decoding over stub [0 .. skip) & message with (has_size => False, marker_expected => True), less the first t_len bytes decoded.
+ * `skip` is the caller's, as in the reference: it must not exceed the bytes the two streams have in common (trtest_single.cmd takes the stub's
+ * length less 140).  With a larger one both sides still do what the reference does with those bytes, and the decoder most likely reports a
+ * data error for that entry.
+ * What the device adds: the head of the stream is the same for every message of a batch.  THE DECODING SIDE decodes stub [0 .. skip) once, when
+ * the handle is opened, up to the first symbol boundary from which fewer than 64 stub bytes remain; every entry's wave starts from that state
+ * (range, code, state, reps, the probability model) with the trainer's text so far copied into its window.  With a skip below 10 (no symbol
+ * boundary inside it) every entry decodes its whole stream.  THE ENCODING SIDE codes the trainer alone once, when the handle is opened, up to the
+ * first boundary of the coder's main loop at or beyond t_len - 4 369 (the matcher's look-ahead, keepSizeAfter: everything looked at so far lies
+ * inside the trainer and outside the reach of a stream's end), and every entry of a batch resumes from that state: it codes [fork_pos, t_len + n)
+ * and the marker.  The BT4 match producer still runs over trainer & data for every entry.  An entry whose stream is longer than one window fill
+ * (t_len + n > 2 ** 20), and every entry when t_len < 8 738 or t_len > 2 ** 20, codes its whole stream in the same launch: the same bytes.
+ * The knob "trained_fork" = 0 makes both sides work without their snapshots (the same bytes; for measurements, profiles/trained/NOTES.md).
+ * One divergence: the reference passes fail_on_bad_range_code => False here; the decoder keeps the product's rule (ULZ_R_RANGE_CORRUPTED, csrc/
+ * zada_unlzma_logic.h), so a message whose range code is corrupted is ZADA_E_DATA where the reference would deliver its bytes.  No CRC: the
+ * reference has none here.  A stub whose properties ask for a literal table of lc + lp > 3 is not Trained_Compression's: ZADA_E_INVALID.
+ * A handle belongs to the context it was opened on, and is closed before that context is destroyed.  Device pointers at any byte alignment;
+ * every argument is checked before anything touches the device; count = 0 and n = 0 (an empty message / empty data) are valid. */
+typedef struct zada_trained zada_trained;
+typedef struct { const void *d_data; uint64_t n; void *d_out; uint64_t cap; } zada_trained_entry;   /* encode: the data and room for its message; decode: the message (d_data, n) and room for the data */
+typedef struct {
+  uint64_t fork_pos, fork_out;           /* encoder: input positions coded in the snapshot and stream bytes written there (0, 0: no snapshot) */
+  uint64_t dec_fork_in, dec_fork_out;    /* decoder: stub bytes taken and trainer bytes written at the snapshot (0, 0: no snapshot) */
+  uint64_t forked, unforked;             /* entries of the handle's last call that started from the snapshot / that ran their whole stream */
+} zada_trained_info_t;
+/* Encode_Trainer.  Host pointers; one stream through zada_lzma's single-stream path.  *out_len is the stub's length also when it is longer than
+ * cap (ZADA_E_INVALID "output buffer too small"). */
+int zada_trained_stub(zada_ctx *ctx, const uint8_t *trainer, uint64_t t_len, uint8_t *out, uint64_t cap, uint64_t *out_len);
+/* The encoding side: keeps the trainer in device memory and the coder's state at the fork.  trainer: a device pointer when on_device is non-zero, a
+ * host pointer otherwise. */
+int zada_trained_open_encoder(zada_ctx *ctx, const void *trainer, uint64_t t_len, int on_device, uint64_t skip, zada_trained **h);
+/* The decoding side, from the stub alone.  ZADA_E_DATA: the first `skip` bytes of the stub do not decode (zada_last_error names the rule), decode
+ * to more than t_len bytes, or end on a marker.  skip <= stub_len. */
+int zada_trained_open_decoder(zada_ctx *ctx, const uint8_t *stub, uint64_t stub_len, uint64_t skip, uint64_t t_len, zada_trained **h);
+/* rc [i]: ZADA_OK, ZADA_E_REFERENCE (as zada_lzma_batch) or ZADA_E_INVALID "output buffer too small"; out_len [i] is the message's full length
+ * also then (0 for ZADA_E_REFERENCE); nothing is written at or beyond d_out + cap.  Returns the worst rc. */
+int zada_trained_encode_device(zada_ctx *ctx, zada_trained *h, int count, const zada_trained_entry *ent, uint64_t *out_len, int *rc);
+/* The stream ends on its marker only.  rc [i]: ZADA_OK or ZADA_E_DATA -- a stream that writes more than t_len + cap bytes, ends before its marker
+ * or refers further back than min (dictionary, bytes written), by the rules of enum UlzRule --, zada_last_error naming the rule and the first
+ * such entry.  out_len [i]: the data's length (0 unless ZADA_OK).  Returns the worst rc. */
+int zada_trained_decode_device(zada_ctx *ctx, zada_trained *h, int count, const zada_trained_entry *ent, uint64_t *out_len, int *rc);
+int zada_trained_info(const zada_trained *h, zada_trained_info_t *info);
+void zada_trained_close(zada_trained *h);
 
 #ifdef __cplusplus
 }

@@ -241,6 +241,15 @@ def load_library():
     if hasattr(L, "zada_find_device"):               # (likewise: Find_Zip on device memory)
         L.zada_find_device.argtypes = [vp, vp, u64, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, u64p, u64p]
         L.zada_findzip_device.argtypes = [vp, vp, u64, i32, vp, u32p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, vp]
+    if hasattr(L, "zada_trained_stub"):              # (likewise: Trained_Compression)
+        L.zada_trained_stub.argtypes = [vp, vp, u64, vp, u64, u64p]
+        L.zada_trained_open_encoder.argtypes = [vp, vp, u64, i32, u64, ctypes.POINTER(vp)]
+        L.zada_trained_open_decoder.argtypes = [vp, vp, u64, u64, u64, ctypes.POINTER(vp)]
+        L.zada_trained_encode_device.argtypes = [vp, vp, i32, vp, vp, vp]
+        L.zada_trained_decode_device.argtypes = [vp, vp, i32, vp, vp, vp]
+        L.zada_trained_info.argtypes = [vp, vp]
+        L.zada_trained_close.restype = None
+        L.zada_trained_close.argtypes = [vp]
     L.zada_bz2_last_blocks.restype = ctypes.c_uint64
     L.zada_bz2_last_blocks.argtypes = [vp, vp, u64]
     L.zada_crc32_combine.restype = ctypes.c_uint32
@@ -318,7 +327,8 @@ class Encoder:
 
     def set_knob(self, name, value):
         """Tuning / test knobs ("budget", "max_demand_rounds", "inner_budget", "shard_kib", "span_mib", "batch_mib", "bunzip_batch_mib", "inflate_par_chunk_kib", "inflate_par_repair_pct", "inflate_par_min_kib"); none changes a byte of output.
-        "lzma_dict" is the reference's dictionary_size parameter for LZMA_3 (0 = the entry's size, what Zip.Compress.LZMA_E passes)."""
+        "lzma_dict" is the reference's dictionary_size parameter for LZMA_3 (0 = the entry's size, what Zip.Compress.LZMA_E passes).
+        "trained_fork" = 0: TrainedCompression works through every entry's whole stream (the same bytes; for measurements)."""
         if self.lib.zada_set_knob(self.ctx, name.encode(), int(value)) != 0:
             raise ZadaError("unknown knob %r" % name)
 
@@ -2048,3 +2058,140 @@ class FindZip:
         import torch
         t = torch.from_numpy(np.frombuffer(bytes(archive_bytes), dtype=np.uint8).copy()).to(torch.device("cuda", self.enc.device))
         return self.find_device(ZipInfo.load_device(t), text, **kw)
+
+
+class TrainedCompression:
+    """Trained_Compression (trained/trained_compression.ads) for batches of messages: every message is the tail of one LZMA stream (Level_3, lc 3,
+    lp 0, pb 2, dictionary 2 ** 19) whose head is training data both sides know (include/zada.h).
+
+    TrainedCompression (encoder, trainer, skip=None, noise=b"") is the ENCODING side: `trainer` is bytes or a torch.uint8 tensor, `noise` is appended
+    to it (as trtest_single.cmd appends rnd_10.bin).  .stub is Encode_Trainer's output, the compressed trainer the decoding side keeps; .skip the
+    stream bytes every message leaves out; skip=None means max (0, len (stub) - 140), the calibration of trtest_single.cmd -- the caller answers
+    for a skip that is no longer than what the streams have in common.  .trainer_len counts the noise.
+    TrainedCompression.for_decoding (encoder, stub, skip, trainer_len) is the DECODING side: it has the stub, not the trainer."""
+    SKIP_MARGIN = 140          # trtest_single.cmd: skip = the stub's length less this
+    _ENTRY = [("d_data", "<u8"), ("n", "<u8"), ("d_out", "<u8"), ("cap", "<u8")]
+    _INFO = ("fork_pos", "fork_out", "dec_fork_in", "dec_fork_out", "forked", "unforked")
+
+    def __init__(self, encoder, trainer, skip=None, noise=b""):
+        self.enc, self.h, self.side = encoder, None, "encode"
+        t = bytes(trainer.cpu().numpy().tobytes()) if hasattr(trainer, "data_ptr") else bytes(trainer)
+        t += bytes(noise)
+        self.trainer_len = len(t)
+        L = encoder.lib
+        cap = len(t) + len(t) // 8 + 4096
+        out = ctypes.create_string_buffer(cap)
+        ol = ctypes.c_uint64()
+        rc = L.zada_trained_stub(encoder.ctx, t, len(t), out, cap, ctypes.byref(ol))
+        if rc != 0:
+            encoder._err(rc, "zada_trained_stub")
+        self.stub = out.raw[:ol.value]
+        self.skip = max(0, len(self.stub) - self.SKIP_MARGIN) if skip is None else int(skip)
+        h = ctypes.c_void_p()
+        rc = L.zada_trained_open_encoder(encoder.ctx, t, len(t), 0, self.skip, ctypes.byref(h))
+        if rc != 0:
+            encoder._err(rc, "zada_trained_open_encoder")
+        self.h = h
+
+    @classmethod
+    def for_decoding(cls, encoder, stub, skip, trainer_len):
+        self = cls.__new__(cls)
+        self.enc, self.h, self.side = encoder, None, "decode"
+        self.stub, self.skip, self.trainer_len = bytes(stub), int(skip), int(trainer_len)
+        h = ctypes.c_void_p()
+        rc = encoder.lib.zada_trained_open_decoder(encoder.ctx, self.stub, len(self.stub), self.skip, self.trainer_len, ctypes.byref(h))
+        if rc != 0:
+            encoder._err(rc, "zada_trained_open_decoder")
+        self.h = h
+        return self
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.enc.lib.zada_trained_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """fork_pos / fork_out (encoder: trainer positions coded once and stream bytes written there), dec_fork_in / dec_fork_out (decoder: stub bytes taken
+        and trainer bytes written once), forked / unforked: entries of the last call that started from the snapshot / that ran their whole stream."""
+        v = (ctypes.c_uint64 * 6)()
+        if self.enc.lib.zada_trained_info(self.h, v) != 0:
+            raise ZadaError("zada_trained_info failed")
+        return dict(zip(self._INFO, (int(x) for x in v)))
+
+    def _call(self, fn, rows):
+        """rows: (d_data, n, d_out, cap) per entry -> (the call's rc, out_len per entry, rc per entry)."""
+        import numpy as np
+        tab = np.array([tuple(int(x) for x in r) for r in rows], dtype=self._ENTRY) if rows else np.zeros(0, dtype=self._ENTRY)
+        n = len(tab)
+        ol, rcs = np.zeros(max(n, 1), np.uint64), np.full(max(n, 1), 99, np.int32)
+        rc = fn(self.enc.ctx, self.h, n, tab.ctypes.data if n else None, ol.ctypes.data, rcs.ctypes.data)
+        return rc, [int(x) for x in ol[:n]], [int(x) for x in rcs[:n]]
+
+    def encode_raw(self, rows):
+        """zada_trained_encode_device on device addresses: rows of (d_data, n, d_out, cap) -> (rc, out_len [], rc [])."""
+        return self._call(self.enc.lib.zada_trained_encode_device, rows)
+
+    def decode_raw(self, rows):
+        """zada_trained_decode_device on device addresses: rows of (d_msg, n_msg, d_out, cap) -> (rc, out_len [], rc [])."""
+        return self._call(self.enc.lib.zada_trained_decode_device, rows)
+
+    def _tensors(self, items, who):
+        import numpy as np
+        import torch
+        dev = torch.device("cuda", self.enc.device)
+        out = []
+        for t in items:
+            if not isinstance(t, torch.Tensor):
+                b = bytes(t)
+                t = torch.from_numpy(np.frombuffer(b, dtype=np.uint8).copy()).to(dev) if b else torch.empty(0, dtype=torch.uint8, device=dev)
+            if t.dtype != torch.uint8 or not t.is_contiguous() or (t.numel() and t.device != dev):
+                raise ZadaError("%s: contiguous torch.uint8 tensors on %s are needed" % (who, dev))
+            out.append(t)
+        return out, dev
+
+    def encode_device(self, datas):
+        """One message per data tensor (contiguous torch.uint8 on the encoder's device), in ONE call: the bytes Trained_Compression.Encode writes
+        for trainer & data with Skip_Compressed = skip.  Returns tensors on the device.  ReferenceDefect as Encoder.lzma_batch."""
+        import torch
+        datas, dev = self._tensors(datas, "TrainedCompression.encode_device")
+        caps = [t.numel() + t.numel() // 8 + self.SKIP_MARGIN + 256 for t in datas]         # (what is left of the stub behind skip, the data, the marker)
+        for attempt in range(2):
+            outs = [torch.empty(c, dtype=torch.uint8, device=dev) for c in caps]
+            torch.cuda.current_stream(dev).synchronize()
+            rc, ols, rcs = self.encode_raw([(t.data_ptr() if t.numel() else 0, t.numel(), o.data_ptr(), c) for t, o, c in zip(datas, outs, caps)])
+            if rc == 0:
+                return [o[:n] for o, n in zip(outs, ols)]
+            if attempt == 0 and all(r == 0 or (r == -1 and n > c) for r, n, c in zip(rcs, ols, caps)):
+                caps = [max(c, n) for c, n in zip(caps, ols)]                                  # (a skip far below the stub's length: the lengths are known now)
+                continue
+            self.enc._err(rc, "zada_trained_encode_device")
+
+    def encode(self, datas):
+        """encode_device for data in host bytes -> list of bytes."""
+        return [bytes(t.cpu().numpy().tobytes()) for t in self.encode_device(datas)]
+
+    def decode_device(self, messages, caps, errors="raise"):
+        """One data tensor per message (bytes or contiguous torch.uint8 tensors on the encoder's device), caps [i] bytes of room each, in ONE call:
+        what Trained_Compression.Decode writes for stub [0 .. skip) & message.  A message that is no valid stream, or holds more than caps [i]
+        bytes, raises DataError naming the first such entry; errors="return" puts a DataError in its place instead."""
+        import torch
+        msgs, dev = self._tensors(messages, "TrainedCompression.decode_device")
+        caps = [int(c) for c in caps]
+        if len(caps) != len(msgs):
+            raise ValueError("TrainedCompression.decode_device: %d caps for %d messages" % (len(caps), len(msgs)))
+        outs = [torch.empty(c, dtype=torch.uint8, device=dev) for c in caps]
+        torch.cuda.current_stream(dev).synchronize()
+        rc, ols, rcs = self.decode_raw([(t.data_ptr() if t.numel() else 0, t.numel(), o.data_ptr() if c else 0, c) for t, o, c in zip(msgs, outs, caps)])
+        if rc != 0 and (rc != E_DATA or errors != "return"):
+            self.enc._err(rc, "zada_trained_decode_device")
+        return [o[:n] if r == 0 else DataError("trained decode: entry %d is not a valid stream for this stub" % k) for k, (o, n, r) in enumerate(zip(outs, ols, rcs))]
+
+    def decode(self, messages, caps, errors="raise"):
+        """decode_device -> list of bytes."""
+        return [r if isinstance(r, Exception) else bytes(r.cpu().numpy().tobytes()) for r in self.decode_device(messages, caps, errors)]

@@ -1152,6 +1152,7 @@ int zada_set_knob(zada_ctx *z, const char *name, int value) {
   else if (!strcmp(name, "lzma_chunk")) { if (value < -1 || (value > 0 && value < 256)) return ZADA_E_INVALID; z->c.knob_lzma_chunk = value; }
   else if (!strcmp(name, "lzma_pool")) { if (value < 0) return ZADA_E_INVALID; z->c.knob_lzma_pool = value; }
   else if (!strcmp(name, "lzma_pool_fixed")) { if (value < 0 || value > 1) return ZADA_E_INVALID; z->c.knob_lzma_pool_fixed = value; }
+  else if (!strcmp(name, "trained_fork")) { if (value != 0 && value != 1) return ZADA_E_INVALID; z->c.knob_trained_fork = value; }
   else if (!strcmp(name, "lzma_waves")) { if (value != 0 && value != 1 && value != 4) return ZADA_E_INVALID; z->c.knob_lzma_waves = value; }
   else if (!strcmp(name, "lzma_lit_mib")) { if (value < 1) return ZADA_E_INVALID; z->c.knob_lzma_lit_mib = value; }
   else if (!strcmp(name, "lzma_segment")) { if (value < -1 || (value > 0 && (value < 13 || value > 30))) return ZADA_E_INVALID; z->c.knob_lzma_segment = value; }
@@ -1460,7 +1461,7 @@ static uint32_t lzma_segment_shift(const Ctx *c, uint64_t n) {
 // launches"), with feedback (pct_lo .. pct_hi by positions coded) and the abort test between them.
 static int lzma_run(Ctx *c, std::vector<LzmaJob> &jobs, const uint8_t *d_in, uint64_t arena_bytes, const uint32_t *d_tok, uint8_t *d_out, std::vector<uint64_t> &res,
                     const uint32_t *d_apos = nullptr, uint32_t T = 0, const uint32_t *d_ent_start = nullptr,
-                    uint64_t budget = 0, zada_feedback_fn fb = nullptr, void *user = nullptr, int pct_lo = 0, int pct_hi = 100) {
+                    uint64_t budget = 0, zada_feedback_fn fb = nullptr, void *user = nullptr, int pct_lo = 0, int pct_hi = 100, const LzFork *fork = nullptr) {
   const uint32_t E = (uint32_t)jobs.size();
   bool bt4 = false;
   for (LzmaJob &j : jobs) {
@@ -1515,7 +1516,15 @@ static int lzma_run(Ctx *c, std::vector<LzmaJob> &jobs, const uint8_t *d_in, uin
   res.resize(2 * (size_t)E);
   if (budget == 0) {
     fresh_lit();
-    if ((rc = lzma_launch(c, d_jobs, d_order, E, d_in, d_tok, d_out, sets, d_res, nullptr, 0, ~0ull, 1, lit_home, d_lit))) return rc;
+    uint8_t *d_save = nullptr;
+    if (fork) {                                                      // (Trained_Compression: a slot per job, the forked ones filled from the trainer's stopped stream)
+      const size_t save_bytes = (size_t)lzma_save_stride() * E;
+      if ((rc = lz_grow(c, &c->lz_save, &c->cap_lz_save, save_bytes))) return rc;
+      d_save = (uint8_t *)c->lz_save;
+      hipMemsetAsync(d_save, 0, save_bytes, c->stream);
+      if ((rc = lzma_fork_fill(c, d_jobs, E, fork->d_forked, fork->d_snap, fork->d_head, fork->head_len, d_save, d_out))) return rc;
+    }
+    if ((rc = lzma_launch(c, d_jobs, d_order, E, d_in, d_tok, d_out, sets, d_res, d_save, d_save ? 1ull << 62 : 0, ~0ull, 1, lit_home, d_lit))) return rc;
     hipMemcpyAsync(res.data(), d_res, 16 * (size_t)E, hipMemcpyDeviceToHost, c->stream);
     if (hip_check(c, hipStreamSynchronize(c->stream), "k_lzma_encode")) return ZADA_E_HIP;
   } else {
@@ -1887,6 +1896,61 @@ int lzma_device_one(Ctx *c, int method, const void *d_in, uint64_t n, void *d_ou
   return rc;
 }
 
+// One Level_3 stream with (3, 0, 2) as LZMA.Encoding.Encode writes it by itself -- no Zip prefix, dictionary_size and end_marker as given -- from host
+// memory into host memory, through the single-stream path above (Trained_Compression.Encode_Trainer, zada_trained.hip).  Of a stream longer than cap
+// only *out_len is given.
+int lzma_plain_stream(Ctx *c, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len, uint32_t dictionary_size, bool end_marker) {
+  if (n >= (2ull << 30) - 65536) { c->err = "LZMA: entries of 2 GiB and more are not taken"; return ZADA_E_TOO_LARGE; }
+  int rc;
+  if ((rc = ensure_rin(c, n + cap + 128))) return rc;
+  copy_in(c, c->ws.rin_own, in, n);
+  uint8_t *d_out = c->ws.rin_own + ((n + 63) & ~63ull);
+  c->lz_resume.clear();                                             // (an imported state is another stream's)
+  c->lz_last_lit_hbm = false;
+  std::vector<LzmaJob> jobs(1);
+  LzmaJob &J = jobs[0];
+  memset(&J, 0, sizeof J);
+  J.n = n; J.cap = cap; J.zip_prefix = end_marker ? 0 : 2;
+  lzma_job_method(J, ZADA_LZMA_3);
+  std::vector<uint64_t> res;
+  const int dict0 = c->knob_lzma_dict;
+  c->knob_lzma_dict = (int)dictionary_size;
+  c->tbegin(); c->tmark("lzma:begin");
+  rc = lzma_run(c, jobs, c->ws.rin_own, n, nullptr, d_out, res, nullptr, 0, nullptr, lzma_budget(c, 3));
+  c->knob_lzma_dict = dict0;
+  if ((rc = finish_call(c, rc))) return rc;
+  c->tmark("lzma:end"); c->tend();
+  if (lzma_refused(c, res, 0)) { *out_len = 0; return ZADA_E_REFERENCE; }
+  *out_len = res[0];
+  if (res[0] > cap) { c->err = "output buffer too small"; return ZADA_E_INVALID; }
+  return copy_out(c, out, d_out, res[0]) ? ZADA_E_HIP : ZADA_OK;
+}
+
+int lzma_fork_snapshot(Ctx *c, const uint8_t *d_in, uint64_t n, uint64_t pos_cap, uint32_t dictionary_size, uint8_t *d_out, uint64_t cap, uint8_t *d_snap, uint64_t *pos,
+                       uint64_t *olen) {
+  std::vector<LzmaJob> jobs(1);
+  LzmaJob &J = jobs[0];
+  memset(&J, 0, sizeof J);
+  J.n = n; J.cap = cap; J.zip_prefix = 1;
+  lzma_job_method(J, ZADA_LZMA_3);
+  J.sbs = lzma_string_buffer_size(3, dictionary_size); J.hash4_size = lzma_hash4_size(J.sbs);
+  int rc = lz_grow(c, &c->lz_tab, &c->cap_lz_tab, sizeof(LzmaJob) + 256);
+  if (rc) return rc;
+  Bt4Sets sets{nullptr, nullptr, nullptr, nullptr, nullptr};
+  if ((rc = bt4_produce(c, jobs, d_in, n, &sets))) return rc;
+  LzmaJob *d_jobs = (LzmaJob *)c->lz_tab;
+  uint64_t *d_res = (uint64_t *)((uint8_t *)c->lz_tab + ((sizeof(LzmaJob) + 63) & ~63ull));
+  uint64_t res[2] = {0, 0};
+  hipMemcpyAsync(d_jobs, jobs.data(), sizeof(LzmaJob), hipMemcpyHostToDevice, c->stream);
+  hipMemsetAsync(d_snap, 0, lzma_save_stride(), c->stream);
+  if ((rc = lzma_launch(c, d_jobs, nullptr, 1, d_in, nullptr, d_out, sets, d_res, d_snap, n, pos_cap, 1, 0, nullptr))) return rc;
+  hipMemcpyAsync(res, d_res, 16, hipMemcpyDeviceToHost, c->stream);
+  if (hip_check(c, hipStreamSynchronize(c->stream), "k_lzma_encode (the trainer)")) return ZADA_E_HIP;
+  if (!(res[1] >> 63) || (res[1] >> 62 & 1)) { c->err = "LZMA: the trainer's stream did not stop where it was told to"; return ZADA_E_INVALID; }
+  *pos = res[1] & ~(3ull << 62); *olen = res[0];
+  return 0;
+}
+
 // ---- BZip2 and LZMA batches as layout and launch (zada_internal.h, DevBatch) ----
 // BZip2: entries short enough for one block, on 64-byte slots of rin_own, the tables of k_batch_crc behind them
 int bzip2_batch_layout(Ctx *c, int method, uint32_t E, const uint64_t *n, const uint32_t *crc_in, DevBatch &D) {
@@ -1995,7 +2059,7 @@ int lzma_batch_launch(Ctx *c, int method, DevBatch &D) {
     hipMemcpyAsync(D.reg.data(), d_tab + 2 * E, 4ull * E, hipMemcpyDeviceToHost, st);
     if (hip_check(c, hipStreamSynchronize(st), "LZMA batch in")) return ZADA_E_HIP;
     c->tmark("lzma:tokens");
-    if ((rc = lzma_run(c, jobs, D.d_in, total, nullptr, D.d_out, res))) return rc;
+    if ((rc = lzma_run(c, jobs, D.d_in, total, nullptr, D.d_out, res, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, 100, D.fork))) return rc;
   } else {
     const uint32_t nseg = (uint32_t)(total >> 15);
     const uint32_t *t_seg = c->btab, *t_ent = c->btab + nseg;

@@ -293,6 +293,7 @@ struct Ctx {
   uint32_t bt4_pool_grown = 0;                       // the overflow pool of a stream's match sets was enlarged between two segments (since the context was made)
   int knob_lzma_pool_fixed = 0;                      // test knob "lzma_pool_fixed": 1 = the pool never grows between segments (the round-4 behaviour: run out, start again)
   uint32_t bt4_reruns = 0;                           // walks repeated with a larger overflow pool (since the context was made)
+  int knob_trained_fork = 1;                         // Trained_Compression (zada_trained.hip): 0 = every entry codes / decodes its whole stream (same bytes; for measurements)
   int knob_lzma_waves = 0;                           // LZMA_3, one stream: waves of its workgroup (0 = by the call: 4 for zada_lzma, 1 = the chain's wave alone)
   int knob_lzma_segment = 0;                         // LZMA_3, one stream: log2 of the positions per producer segment (0 = 20, -1 = no segments)
   int knob_lzma_pool = 0;                            // LZMA_3 test knob: blocks of the match sets' overflow pool to start with (0 = by size)
@@ -372,6 +373,18 @@ int inflate_run_jobs(Ctx *c, uint32_t E, const ReaderJob *jobs, ReaderRes *res, 
 int bunzip2_run_jobs(Ctx *c, uint32_t E, const ReaderJob *jobs, ReaderRes *res, bool *described);
 int unlzma_run_jobs(Ctx *c, uint32_t E, const ReaderJob *jobs, ReaderRes *res, bool *described);
 uint64_t unlzma_hbm_elems(const uint8_t *h9, uint64_t n_in);   // ReaderJob::lit_elems of an LZMA entry, from the first nine bytes of its payload
+// Trained_Compression's decoder (k_unlzma_trained, zada_unlzma.hip) for zada_trained.hip: E streams (5-byte header, no size field, ending on their
+// marker), one wave each, on the context's stream; nothing is waited for.  d_start: the snapshot every stream goes on from (its input is then what
+// follows the snapshot's input position, its output slot holds the snapshot's text), null: each stream starts at its own header.  d_stop: ONE stream
+// stops at the first symbol boundary from which fewer than 64 bytes remain before stop_in, and leaves its snapshot there (unlzma_snap_bytes () bytes).
+struct UlzTrainedJob { uint64_t in, out, n_in, cap; };             // device addresses; cap: room for the whole stream's text
+struct UlzResult;
+uint64_t unlzma_snap_bytes();
+// (the host's view of a snapshot: 0 if the stop did not happen; where it did, the input bytes taken and the bytes written)
+int unlzma_snap_info(const uint8_t *snap, uint64_t *in_pos, uint64_t *out_pos, uint64_t *lit_elems);
+int unlzma_trained_launch(Ctx *c, const UlzTrainedJob *d_jobs, const uint32_t *d_order, uint32_t E, UlzResult *d_res, const void *d_start, void *d_stop, uint64_t stop_in);
+// One Level_3 stream with (3, 0, 2) as LZMA.Encoding.Encode writes it by itself (zada_api.hip), host memory to host memory
+int lzma_plain_stream(Ctx *c, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len, uint32_t dictionary_size, bool end_marker);
 void crypt_update_keys(uint32_t keys[3], uint8_t by);
 uint8_t crypt_code(const uint32_t keys[3]);
 constexpr uint64_t CRYPT_WAVE_MAX = 256u << 10;     // a batch's entries of up to this many bytes: one wave each, in one launch
@@ -400,7 +413,7 @@ struct LzmaJob {
   uint64_t out_off, cap;            // where the stream goes (the bytes beyond cap are counted, not written)
   uint64_t verify;                  // Level_3: 1 = the coder checks every match of the sets it reads against the text (bt4_reads_behind_a_gap, zada_bt4.h)
   uint32_t sbs, hash4_size;         // String_buffer_size (lzma-encoding.adb:137-149), BT4's hash4 size (lz77.adb:1019-1032)
-  int32_t level, zip_prefix;        // 0 .. 3; 1: the four bytes of zip-compress-lzma_e.adb:155-158 go first
+  int32_t level, zip_prefix;        // 0 .. 3; bit 0: the four bytes of zip-compress-lzma_e.adb:155-158 go first, bit 1: no end marker (LZMA.Encoding.Encode's end_marker => False)
   int32_t lc, lp, pb;               // the method's literal context bits, literal position bits, position bits (zip-compress-lzma_e.adb:121-143)
   int32_t lit_home;                 // where the literal table lives (zada_lzma.hip LM_*): 0 (3, 0, 2), 1 LDS, 2 HBM; the same for every job of a launch
   uint64_t lit_off;                 // lit_home 2: the entry's table, in probabilities from the launch's literal buffer
@@ -419,6 +432,14 @@ int lzma_token_ranges(Ctx *c, uint32_t E, const uint32_t *d_apos, uint32_t T, co
 int lzma_launch(Ctx *c, const LzmaJob *d_jobs, const uint32_t *d_order, uint32_t count, const uint8_t *d_in, const uint32_t *d_tok, uint8_t *d_out, const Bt4Sets &sets, uint64_t *d_result,
                 uint8_t *d_save = nullptr, uint64_t budget = 0, uint64_t pos_cap = ~0ull, int waves = 1, int lit_home = 0, uint16_t *d_lit = nullptr);
 uint64_t lzma_save_stride();
+// Trained_Compression: the forked jobs of a batch go on from one stopped stream (zada_lzma.hip, k_lzma_fork_fill)
+struct LzFork { const uint8_t *d_snap, *d_head; uint64_t head_len; const uint8_t *d_forked; };   // d_forked [e] /= 0: job e of the launch is forked
+int lzma_fork_fill(Ctx *c, const LzmaJob *d_jobs, uint32_t count, const uint8_t *d_forked, const uint8_t *d_snap, const uint8_t *d_head, uint64_t head_len, uint8_t *d_save,
+                   uint8_t *d_out);
+// ... and that stream: n bytes at d_in (a multiple of 64) as ONE LZMA_3 job with the Zip prefix and the dictionary given, coded up to the first boundary of
+// the coder's main loop at or beyond pos_cap; the state goes to d_snap (lzma_save_stride () bytes), the stream so far to d_out (zada_api.hip)
+int lzma_fork_snapshot(Ctx *c, const uint8_t *d_in, uint64_t n, uint64_t pos_cap, uint32_t dictionary_size, uint8_t *d_out, uint64_t cap, uint8_t *d_snap, uint64_t *pos,
+                       uint64_t *olen);
 int lzma_save_info(const uint8_t *blob, uint64_t *pos, uint64_t *olen, uint64_t *n);
 int lzma_save_fits(const uint8_t *blob, const LzmaJob &J);
 int ensure_lz_workspace(Ctx *c, uint64_t nbuf);
@@ -476,6 +497,7 @@ struct DevBatch {
   std::vector<uint64_t> start, off, bytes, cap;    // per entry
   std::vector<uint32_t> len, reg;                  // (E + 1 values)
   std::vector<uint8_t> refused;                    // LZMA_3: ZADA_E_REFERENCE for this entry
+  const LzFork *fork = nullptr;                    // LZMA_3, Trained_Compression: entries that go on from a stopped stream
 };
 int bzip2_batch_layout(Ctx *c, int method, uint32_t E, const uint64_t *n, const uint32_t *crc_in, DevBatch &D);
 int bzip2_batch_launch(Ctx *c, int method, DevBatch &D, uint8_t *h_out, uint64_t h_cap);     // h_out: the streams also go to the host (pinned), null: they stay

@@ -1288,7 +1288,7 @@ template <bool HW, int LM> __global__ void __launch_bounds__(HW ? 64 * HELP_WAVE
     s_E.width = 0xFFFFFFFFu; s_E.low = 0; s_E.cache = 0; s_E.cache_size = 1;
     s_E.out = out_base + J.out_off; s_E.cap = J.cap; s_E.olen = 0;
     s_E.verify = J.level == 3 ? (uint32_t)J.verify : 0u; s_E.defect = 0;
-    if (J.zip_prefix) { put_byte(16); put_byte(2); put_byte(5); put_byte(0); }   // zip-compress-lzma_e.adb:155-158
+    if (J.zip_prefix & 1) { put_byte(16); put_byte(2); put_byte(5); put_byte(0); }   // zip-compress-lzma_e.adb:155-158
     put_byte(props<LM>(J));                                                         // Write_LZMA_header :1513-1536
     for (int i = 0; i < 4; i++) put_byte((J.sbs >> (8 * i)) & 255);
     if (J.level == 3) running = lz_bt4_begin((int)J.sbs, J.in_off, sets);
@@ -1336,8 +1336,10 @@ template <bool HW, int LM> __global__ void __launch_bounds__(HW ? 64 * HELP_WAVE
     helpers_release<HW>();
     return;
   }
-  encode_bit(P.match[s_E.ES.state][s_E.ES.pos_state], 1);                             // end marker :1549-1556
-  write_simple_match(0xFFFFFFFFu, 2);
+  if (!(J.zip_prefix & 2)) {                                                          // (bit 1: end_marker => False, Trained_Compression.Encode_Trainer)
+    encode_bit(P.match[s_E.ES.state][s_E.ES.pos_state], 1);                           // end marker :1549-1556
+    write_simple_match(0xFFFFFFFFu, 2);
+  }
   for (int i = 0; i < 5; i++) shift_low();                                          // Flush_range_encoder
 #ifdef ZADA_LZ_PROF
   if (blockIdx.x == 0 && threadIdx.x == 0) printf("LZPROF total %llu literal %llu emit_dl %llu (decisions %llu: strict + expanded %llu, cuts %llu) estimate %llu bt_get %llu bt_skip %llu\n", clock64() - prof_k0, g_lzprof[1], g_lzprof[2], g_lzprof[0], g_lzprof[7], g_lzprof[6], g_lzprof[3], g_lzprof[4], g_lzprof[5]);
@@ -1348,7 +1350,43 @@ template <bool HW, int LM> __global__ void __launch_bounds__(HW ? 64 * HELP_WAVE
   helpers_release<HW>();
 }
 
+// Trained_Compression (zada_trained.hip): every forked job of a batch goes on from ONE stopped stream, the trainer's.  The job's slot
+// receives that stream's state -- the model, the coder, the two look-ahead match sets, the reps and the parse fields of BT4 depend on the text the
+// coder has looked at only, and that text is the same in every job -- with the window's bookkeeping of THIS job: one fill holds the whole stream
+// (n <= String_buffer_size), so writePos = in_pos = n, nothing was moved, nothing is pending.  The stream bytes written so far go to the job's
+// output slot.  A job that is not forked keeps its zeroed slot: phase 0.  Plain streaming: 16-byte copies (both sides are multiples of 64), a byte tail.
+__global__ void __launch_bounds__(64) k_lzma_fork_fill(const LzmaJob *__restrict__ jobs, const uint8_t *__restrict__ forked, const uint8_t *__restrict__ snap,
+                                                       uint8_t *save_base, uint8_t *out_base, const uint8_t *__restrict__ head, uint64_t head_len) {
+  const uint32_t job = blockIdx.x;
+  if (!forked[job]) return;
+  const LzmaJob J = jobs[job];
+  uint8_t *slot = save_base + job * LZ_SAVE_STRIDE;
+  static_assert(LZ_SAVE_STRIDE % 16 == 0, "16-byte copies");
+  for (uint32_t i = threadIdx.x; i < LZ_SAVE_STRIDE / 16; i += 64) ((uint4 *)slot)[i] = ((const uint4 *)snap)[i];
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    LzSave *S = (LzSave *)slot;
+    S->E.n = J.n;
+    S->B.writePos = (int)J.n; S->B.in_pos = J.n; S->B.readLimit = (int)J.n - S->B.keepSizeAfter;
+    S->B.base = J.in_off;
+  }
+  uint8_t *out = out_base + J.out_off;
+  const uint64_t w = head_len < J.cap ? head_len : J.cap;
+  for (uint64_t i = threadIdx.x; i < w / 16; i += 64) ((uint4 *)out)[i] = ((const uint4 *)head)[i];
+  for (uint64_t i = (w & ~15ull) + threadIdx.x; i < w; i += 64) out[i] = head[i];
+}
+
 }  // namespace
+
+// snap: one slot of lzma_save_stride () bytes, a stream that stopped (lzma_launch with d_save) with everything it has looked at well inside the
+// text all forked jobs share; head: the head_len stream bytes it had written; both at multiples of 16, as the jobs' output slots are.  d_forked [e] /= 0:
+// job e goes on from it.  d_save: count zeroed slots.  Nothing is waited for.
+int lzma_fork_fill(Ctx *c, const LzmaJob *d_jobs, uint32_t count, const uint8_t *d_forked, const uint8_t *d_snap, const uint8_t *d_head, uint64_t head_len, uint8_t *d_save,
+                   uint8_t *d_out) {
+  if (count == 0) return 0;
+  hipLaunchKernelGGL(k_lzma_fork_fill, dim3(count), dim3(64), 0, c->stream, d_jobs, d_forked, d_snap, d_save, d_out, d_head, head_len);
+  return hip_check(c, hipGetLastError(), "k_lzma_fork_fill") ? ZADA_E_HIP : 0;
+}
 
 // String_buffer_size of a level (:137-149) and the BT4 hash size (lz77.adb:1019-1032)
 uint32_t lzma_string_buffer_size(int level, uint64_t dictionary_size) {

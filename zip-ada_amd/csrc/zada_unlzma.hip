@@ -177,6 +177,77 @@ __global__ void __launch_bounds__(ULZ_WAVE) k_unlzma(const UlzJob *__restrict__ 
   }
 }
 
+// ---- Trained_Compression: the same wave, started from a snapshot or stopped into one ----
+// A snapshot is the decoder between two symbols: ulz_decode_f's UlzFork, the stream's properties and the probability model (the literal table in the
+// LDS only: lc + lp <= 3).  The window is not part of it: the text written so far lies in the output slot, where the caller puts a copy of it for
+// every stream that starts from the snapshot.
+struct UlzSnap { UlzFork f; UlzProps P; uint32_t valid, pad; uint16_t probs[ULZ_NPROBS + 2]; uint16_t lit[ULZ_LIT_LDS_MAX]; };
+static_assert(sizeof(UlzSnap) % 4 == 0 && (ULZ_NPROBS + 2) % 2 == 0, "word copies");
+__device__ __forceinline__ uint64_t ulz_uni64(uint64_t v) { return (uint64_t)ULZ_UNI((uint32_t)v) | (uint64_t)ULZ_UNI((uint32_t)(v >> 32)) << 32; }
+
+template <bool STOP>
+__global__ void __launch_bounds__(ULZ_WAVE) k_unlzma_trained(const UlzTrainedJob *__restrict__ jobs, const uint32_t *__restrict__ order, uint32_t count, uint32_t *counter,
+                                                             UlzResult *results, const UlzSnap *start, UlzSnap *snap, uint64_t stop_in) {
+  const uint32_t lane = threadIdx.x;
+  for (;;) {
+    __syncthreads();
+    if (lane == 0) s_ulz_next = atomicAdd(counter, 1u);
+    __syncthreads();
+    const uint32_t slot = ULZ_UNI(s_ulz_next);
+    if (slot >= count) break;
+    const uint32_t e = order[slot];
+    const UlzTrainedJob J = jobs[e];
+    UlzWaveIO<ULM_LDS> io;
+    io.open((ulz_gcu8 *)J.in, J.n_in, (ulz_gu8 *)J.out, nullptr);
+    UlzResult R;
+    UlzProps P{};
+    UlzFork F{};
+    uint32_t rule = ULZ_OK;
+    if (start) {
+      P = UlzProps{ULZ_UNI(start->P.lc), ULZ_UNI(start->P.lp), ULZ_UNI(start->P.pb), ULZ_UNI(start->P.dict)};
+      F = UlzFork{ULZ_UNI(start->f.range), ULZ_UNI(start->f.code), ULZ_UNI(start->f.corrupted), ULZ_UNI(start->f.state), ULZ_UNI(start->f.rep0), ULZ_UNI(start->f.rep1),
+                  ULZ_UNI(start->f.rep2), ULZ_UNI(start->f.rep3), ULZ_UNI(start->f.prev), 0u, 0ull, ulz_uni64(start->f.out_pos)};
+      const uint32_t *l32 = (const uint32_t *)start->lit;
+      const uint32_t words = (uint32_t)(ulz_lit_elems(P) / 2);                  // (<= ULZ_LIT_LDS_MAX / 2: unlzma_trained_launch's caller saw to it)
+      for (uint32_t i = lane; i < ULZ_NPROBS; i += ULZ_WAVE) s_ulz_probs[i] = start->probs[i];
+      for (uint32_t i = lane; i < words && i < ULZ_LIT_LDS_MAX / 2; i += ULZ_WAVE) ((uint32_t *)s_ulz_lit)[i] = l32[i];
+      __syncthreads();
+      io.qpos = F.out_pos; io.fence_pos = F.out_pos;                            // (the text before: written by the launch before this one)
+    } else {
+      uint8_t h5[5];
+#pragma unroll
+      for (uint32_t k = 0; k < 5; k++) h5[k] = (uint8_t)io.staged(k);           // (zeros beyond n_in)
+      rule = ulz_props5(h5, J.n_in, P);
+      if (!rule && ulz_lit_elems(P) > (uint64_t)ULZ_LIT_LDS_MAX) rule = ULZ_R_PROPERTIES;
+      if (!rule) {
+        for (uint32_t i = lane; i < ULZ_NPROBS; i += ULZ_WAVE) s_ulz_probs[i] = (uint16_t)ULZ_PROB_INIT;
+        const uint32_t words = (uint32_t)(ulz_lit_elems(P) / 2);
+        uint32_t *l32 = (uint32_t *)s_ulz_lit;
+        for (uint32_t i = lane; i < words; i += ULZ_WAVE) l32[i] = ULZ_PROB_INIT * 0x10001u;
+        __syncthreads();
+        io.ip = 5;
+      }
+    }
+    if (rule) ulz_fail(R, rule, J.n_in < 5 ? J.n_in : 0, 0);
+    else {
+      const UlzStop stp{stop_in, ~0ull};
+      ulz_decode_f<true>(io, P, J.cap, 1u, R, start ? &F : nullptr, STOP ? &stp : nullptr, &F);
+      if (R.rc == 0) io.flush();
+      if constexpr (STOP) {
+        if (R.rc == 0 && R.end == ULZ_END_FORK) {
+          __syncthreads();
+          uint32_t *l32 = (uint32_t *)snap->lit;
+          for (uint32_t i = lane; i < ULZ_NPROBS; i += ULZ_WAVE) snap->probs[i] = s_ulz_probs[i];
+          for (uint32_t i = lane; i < ULZ_LIT_LDS_MAX / 2; i += ULZ_WAVE) l32[i] = ((const uint32_t *)s_ulz_lit)[i];
+          if (lane == 0) { snap->f = F; snap->P = P; snap->valid = 1u; snap->pad = 0u; }
+        }
+      }
+    }
+    R.crc = 0;
+    if (lane == 0) results[e] = R;
+  }
+}
+
 // ---- host side ----
 struct UlzBuf { uint8_t *p = nullptr; uint64_t cap = 0; };
 struct UlzState {
@@ -325,6 +396,28 @@ int unlzma_run_jobs(Ctx *c, uint32_t E, const ReaderJob *rj, ReaderRes *rr, bool
     else rr[k] = ReaderRes{ZADA_OK, res[k].crc, res[k].out_len, res[k].in_used};
   }
   return 0;
+}
+
+// k_unlzma_trained for zada_trained.hip (zada_internal.h)
+uint64_t unlzma_snap_bytes() { return sizeof(UlzSnap); }
+int unlzma_snap_info(const uint8_t *snap, uint64_t *in_pos, uint64_t *out_pos, uint64_t *lit_elems) {
+  const UlzSnap *S = (const UlzSnap *)snap;
+  if (S->valid != 1u) return 0;
+  *in_pos = S->f.in_pos; *out_pos = S->f.out_pos; *lit_elems = ulz_lit_elems(S->P);
+  return 1;
+}
+int unlzma_trained_launch(Ctx *c, const UlzTrainedJob *d_jobs, const uint32_t *d_order, uint32_t E, UlzResult *d_res, const void *d_start, void *d_stop, uint64_t stop_in) {
+  if (E == 0) return 0;
+  if (d_stop && (E != 1 || d_start)) { c->err = "unlzma: one stream from its header stops into a snapshot"; return ZADA_E_INVALID; }
+  UlzState *S = ulz_state(c);
+  if (!S) { c->err = "unlzma: no memory for the tables"; return ZADA_E_NOMEM; }
+  hipStream_t st = c->stream;
+  hipMemsetAsync(S->d_counter, 0, 4, st);
+  const uint32_t waves = (uint32_t)S->cus * 10u;
+  const uint32_t grid = E < waves ? E : waves;
+  if (d_stop) hipLaunchKernelGGL(k_unlzma_trained<true>, dim3(grid), dim3(ULZ_WAVE), 0, st, d_jobs, d_order, E, S->d_counter, d_res, (const UlzSnap *)nullptr, (UlzSnap *)d_stop, stop_in);
+  else hipLaunchKernelGGL(k_unlzma_trained<false>, dim3(grid), dim3(ULZ_WAVE), 0, st, d_jobs, d_order, E, S->d_counter, d_res, (const UlzSnap *)d_start, (UlzSnap *)nullptr, 0ull);
+  return hip_check(c, hipGetLastError(), "k_unlzma_trained") ? ZADA_E_HIP : 0;
 }
 
 }  // namespace zada

@@ -54,7 +54,7 @@ ULZ_HD const char *ulz_rule_name(uint32_t r) {
     default: return "?";
   }
 }
-enum { ULZ_END_NONE = 0, ULZ_END_MARKER = 1, ULZ_END_NO_MARKER = 2 };
+enum { ULZ_END_NONE = 0, ULZ_END_MARKER = 1, ULZ_END_NO_MARKER = 2, ULZ_END_FORK = 3 };   // _FORK: stopped between two symbols (ulz_decode_f)
 
 // the probabilities that are no literal's: 1846 of them
 constexpr uint32_t ULZ_IS_MATCH = 0;                          // [12][16]
@@ -158,22 +158,52 @@ ULZ_HD uint32_t ulz_props(const uint8_t *h9, uint64_t n_in, UlzProps &P) {
 }
 ULZ_HD uint64_t ulz_lit_elems(const UlzProps &P) { return (uint64_t)0x300 << (P.lc + P.lp); }
 
+// The decoder between two symbols (Trained_Compression): everything Decode_Contents carries from one turn of its loop to the next, but
+// the probability model and the window, which stay where the IO keeps them.  in_pos: input bytes taken, out_pos: bytes written.
+struct UlzFork { uint32_t range, code, corrupted, state, rep0, rep1, rep2, rep3, prev, pad; uint64_t in_pos, out_pos; };
+// where a decoder that may stop does so: at the first symbol boundary from which fewer than ULZ_FORK_MARGIN input bytes remain before in_limit, or
+// the first one behind `symbols` symbols (a test's way to every boundary).  One symbol takes fewer than 64 bytes: at most 22 adaptive bits, each
+// narrowing the range by less than 2 ** 7 (a probability stays within 31 .. 2017 of 2048), and 26 direct bits -- under 180 bits.
+constexpr uint64_t ULZ_FORK_MARGIN = 64;
+struct UlzStop { uint64_t in_limit, symbols; };
+
 // Decode_Contents behind the nine header bytes (io stands at byte 9, the model is initialised).  res.crc is the caller's.
-template <class IO> ULZ_HD void ulz_decode(IO &io, const UlzProps &P, uint64_t cap, uint32_t eos, UlzResult &res) {
+// FORK (Trained_Compression): start, when given, is a state to go on from in place of the initial one (io and the model are the caller's to set); with
+// stop the decoder ends at the boundary UlzStop names, leaves its state in *fork and reports ULZ_END_FORK.  Without FORK none of this is compiled.
+template <bool FORK, class IO> ULZ_HD void ulz_decode_f(IO &io, const UlzProps &P, uint64_t cap, uint32_t eos, UlzResult &res, const UlzFork *start, const UlzStop *stop,
+                                                       UlzFork *fork) {
   const uint32_t lc = P.lc, lpm = (1u << P.lp) - 1u, pbm = (1u << P.pb) - 1u, dict = P.dict;
   UlzRc rc{0xFFFFFFFFu, 0u, 0u};
   uint32_t state = 0, rep0 = 0, rep1 = 0, rep2 = 0, rep3 = 0, prev = 0;
-  uint64_t pos = 0;
+  uint64_t pos = 0, nsym = 0;
   res.rc = 0; res.rule = 0; res.out_len = 0; res.in_used = 0; res.in_pos = 0; res.out_pos = 0; res.end = ULZ_END_NONE;
 #define ULZ_FAIL(r) do { ulz_fail(res, (r), io.ip, pos); return; } while (0)
 #define ULZ_OVER() do { if (io.over) ULZ_FAIL(ULZ_R_INPUT_END); } while (0)
-  // Init
-  if (io.byte() != 0) rc.corrupted = 1;
-  for (int i = 0; i < 4; i++) rc.code = (rc.code << 8) | io.byte();
-  ULZ_OVER();
-  if (rc.code == rc.range) rc.corrupted = 1;
+  bool resumed = false;
+  if constexpr (FORK) {
+    if (start) {
+      rc.range = start->range; rc.code = start->code; rc.corrupted = start->corrupted;
+      state = start->state; rep0 = start->rep0; rep1 = start->rep1; rep2 = start->rep2; rep3 = start->rep3; prev = start->prev; pos = start->out_pos;
+      resumed = true;
+    }
+  }
+  if (!resumed) {
+    // Init
+    if (io.byte() != 0) rc.corrupted = 1;
+    for (int i = 0; i < 4; i++) rc.code = (rc.code << 8) | io.byte();
+    ULZ_OVER();
+    if (rc.code == rc.range) rc.corrupted = 1;
+  }
   uint32_t end = ULZ_END_NONE;
   for (;;) {
+    if constexpr (FORK) {
+      if (stop && (io.ip + ULZ_FORK_MARGIN > stop->in_limit || nsym >= stop->symbols)) {
+        *fork = UlzFork{rc.range, rc.code, rc.corrupted, state, rep0, rep1, rep2, rep3, prev, 0u, io.ip, pos};
+        res.out_len = pos; res.in_used = io.ip; res.in_pos = io.ip; res.out_pos = pos; res.end = ULZ_END_FORK;
+        return;
+      }
+      nsym++;
+    }
     if (!eos && pos == cap && rc.code == 0) { end = ULZ_END_NO_MARKER; break; }
     const uint32_t ps = (uint32_t)pos & pbm;
     if (ulz_bit<false>(io, rc, ULZ_IS_MATCH + state * 16 + ps) == 0) {
@@ -254,6 +284,20 @@ template <class IO> ULZ_HD void ulz_decode(IO &io, const UlzProps &P, uint64_t c
 #undef ULZ_FAIL
 #undef ULZ_OVER
   res.out_len = pos; res.in_used = io.ip; res.in_pos = io.ip; res.out_pos = pos; res.end = end;
+}
+template <class IO> ULZ_HD void ulz_decode(IO &io, const UlzProps &P, uint64_t cap, uint32_t eos, UlzResult &res) {
+  ulz_decode_f<false>(io, P, cap, eos, res, nullptr, nullptr, nullptr);
+}
+
+// The five header bytes of a stream as LZMA.Encoding.Encode writes it with no size field (Trained_Compression: has_size => False).  Returns a UlzRule.
+ULZ_HD uint32_t ulz_props5(const uint8_t *h5, uint64_t n_in, UlzProps &P) {
+  if (n_in < 5) return ULZ_R_INPUT_END;
+  uint32_t d = h5[0];
+  if (d >= 225) return ULZ_R_PROPERTIES;
+  P.lc = d % 9; d /= 9; P.lp = d % 5; P.pb = d / 5;
+  P.dict = (uint32_t)h5[1] | (uint32_t)h5[2] << 8 | (uint32_t)h5[3] << 16 | (uint32_t)h5[4] << 24;
+  if (P.dict < ULZ_MIN_DICT) P.dict = ULZ_MIN_DICT;
+  return ULZ_OK;
 }
 
 // ---- the surroundings of the CPU model, and the whole decoder with one lane ----
