@@ -28,6 +28,11 @@ extern "C" {
 
 /* Compression_Method'Pos (zip_lib/zip-compress.ads:59-122); Deflation_Method = 6 .. 11 (:132). */
 enum {
+  ZADA_SHRINK_1 = 1,        /* Shrink: LZW with partial clearing, codes of 9 .. 13 bits (zip-compress-shrink_e.adb; Zip format 1) */
+  ZADA_REDUCE_1 = 2,        /* Reduce, factor 1 .. 4: an LZSS matcher over a 4 096-byte ring (look-ahead 31 / 63 / 255 / 191) in front of a per-stream */
+  ZADA_REDUCE_2 = 3,        /* follower-set coder (zip-compress-reduce.adb, lz77.adb:249-429; Zip formats 2 .. 5) */
+  ZADA_REDUCE_3 = 4,
+  ZADA_REDUCE_4 = 5,
   ZADA_DEFLATE_FIXED = 6,   /* single fixed block, LZ77 level IZ_4      (zip-compress-deflate.adb:1574) */
   ZADA_DEFLATE_0 = 7,       /* no LZ77, Taillaule + Huffman only        (:1575) */
   ZADA_DEFLATE_1 = 8,       /* IZ_6  (8,16,128,128),   1 scan level     (:1576, lz77.adb:542) */
@@ -128,7 +133,8 @@ const char *zada_version(void);
  * the match producer, whose walks of segment k + 1 run beside the coder of segment k; 13 .. 30, 0 = by size: 2 ** 20 positions for streams from 2 MiB on, 2 ** 18 from 512 KiB on, none below,
  * -1 = all match sets before the coder starts), "lzma_waves" (one LZMA_3 stream alone: waves of its workgroup -- 0 or 4 = the wave that walks the stream's
  * chain and three helpers that take shares of its forks, 1 = that wave alone, as every entry of a batch has it), "trained_fork" (Trained_Compression:
- * 1, the default = the trainer is coded and the stub decoded once per handle, 0 = every entry works through its whole stream).  None of them changes a byte.  One knob is a parameter of the reference instead: "lzma_dict" = LZMA.Encoding.Encode's
+ * 1, the default = the trainer is coded and the stub decoded once per handle, 0 = every entry works through its whole stream), "reduce_group_mib" (MiB of HBM the work arrays of one launch
+ * group of zada_reduce_batch may take, 328 KiB and the raw bytes per entry; default 4096: it bounds a group as "lzma_lit_mib" does).  None of them changes a byte.  One knob is a parameter of the reference instead: "lzma_dict" = LZMA.Encoding.Encode's
  * dictionary_size for LZMA_3 in bytes (0, the default: the entry's size, as Zip.Compress.LZMA_E passes it; lzma_enc.adb uses 32 KiB). */
 int zada_set_knob(zada_ctx *ctx, const char *name, int value);
 
@@ -163,9 +169,9 @@ int zada_deflate_batch(zada_ctx *ctx, int method, int count,
                        uint8_t *const *out, const uint64_t *cap,
                        uint64_t *out_len, uint32_t *crc, int *rc);
 
-/* Zip.Compress.Compress_Data for one unencrypted Deflate, BZip2 or LZMA method (zip-compress.adb:142-241):
- * CRC Init/Final around zada_deflate, Store fallback when compression_ok = False.
- * zip_type: 8 (deflate), 12 (bzip2), 14 (lzma) or 0 (store).  crc_out is the final CRC-32.  Preselection: zada_compress_data_hint. */
+/* Zip.Compress.Compress_Data for one unencrypted Shrink, Reduce, Deflate, BZip2 or LZMA method (zip-compress.adb:142-241):
+ * CRC Init/Final around the method's encoder, Store fallback when compression_ok = False.
+ * zip_type: 1 (shrink), 2 .. 5 (reduce, by factor), 8 (deflate), 12 (bzip2), 14 (lzma) or 0 (store).  crc_out is the final CRC-32.  Preselection: zada_compress_data_hint. */
 int zada_compress_data(zada_ctx *ctx, int method, const uint8_t *in, uint64_t n,
                        uint8_t *out, uint64_t cap, uint64_t *out_len,
                        uint32_t *crc_out, uint16_t *zip_type);
@@ -178,6 +184,35 @@ int zada_preselect(int method, int content_hint, int input_size_known, uint64_t 
 /* zada_compress_data with Preselection: the method is zada_preselect (method, content_hint, 1, n); *method_used (may be NULL) = that method. */
 int zada_compress_data_hint(zada_ctx *ctx, int method, int content_hint, const uint8_t *in, uint64_t n, uint8_t *out,
                             uint64_t cap, uint64_t *out_len, uint32_t *crc_out, uint16_t *zip_type, int *method_used);
+
+/* ---- Shrink_1 and Reduce_1 .. _4: Zip.Compress.Shrink_E (zip-compress-shrink_e.adb) and Zip.Compress.Reduce (zip-compress-reduce.adb) --------
+ * The two oldest methods of Zip.Compress, through the same Compress_Data as every other (zip-compress.adb:181-195).  Both are chains -- an LZW code
+ * is looked up under the code the bytes before led to; the matcher's tree is what the bytes before left --, so ENTRIES are what runs in parallel, one
+ * wave per entry (csrc/zada_shrink.hip, csrc/zada_reduce.hip), and ONE STREAM ALONE RUNS AT ONE WAVE'S PACE, as one Inflate or LZMA
+ * stream does: use the batch calls.  Behind Reduce's matcher the rest is parallel inside an entry: pair counts, one wave per row for the follower
+ * sets, a scan of the bit counts, one emit kernel.  Per entry Reduce takes 328 KiB of HBM (256 KiB of pair counts, 64 KiB of follower positions,
+ * 8 KiB of followers, Slen) and 2 n + 16 raw bytes; a batch runs in launch groups bounded by the knob "reduce_group_mib".
+ * Arguments and pointer contract are those of zada_deflate_device / zada_lzma_batch: in / d_in is never written and, like out / d_out, may lie at any
+ * byte alignment; a cap of exactly the stream's length is enough and nothing is written at or beyond out + cap; crc_inout is the running register,
+ * started anywhere, and may be NULL; the batch calls give an rc [i] per entry and return the last negative one, or 0.  THERE IS NO FEEDBACK
+ * CALLBACK: the calls are one launch sequence each.  ZADA_INEFFICIENT is Write_Block's rule (zip-compress.adb:468-490): the stream is not shorter
+ * than the input -- n = 0 included, where Shrink writes nothing and Reduce the 192 bytes of 256 empty follower sets --; *out_len is then its length
+ * and nothing is delivered.  A stream shorter than the input that does not fit cap is ZADA_E_INVALID ("output buffer too small").  An entry of 1 GiB -
+ * 64 KiB or more is ZADA_E_TOO_LARGE.  method is ZADA_REDUCE_1 .. ZADA_REDUCE_4.  Output bytes are those of the CPU models (tests/legacy/), whose
+ * stated forms restate the reference's encoders; parity with an Ada build is unpinned, as everywhere.
+ * Still refused, by name: zada_zip_device, zada_zip_device_ex and zada_rezip_device take neither method, and the readers decode neither format. */
+int zada_shrink(zada_ctx *ctx, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout);
+int zada_shrink_device(zada_ctx *ctx, const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout);
+int zada_shrink_batch(zada_ctx *ctx, int count, const uint8_t *const *in, const uint64_t *n, uint8_t *const *out, const uint64_t *cap,
+                      uint64_t *out_len, uint32_t *crc, int *rc);
+int zada_reduce(zada_ctx *ctx, int method, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout);
+int zada_reduce_device(zada_ctx *ctx, int method, const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout);
+int zada_reduce_batch(zada_ctx *ctx, int method, int count, const uint8_t *const *in, const uint64_t *n, uint8_t *const *out, const uint64_t *cap,
+                      uint64_t *out_len, uint32_t *crc, int *rc);
+/* Test hook: what the last zada_reduce* launch group on the context left on the device for its entry `entry` -- what = 0: the raw bytes (the
+ * matcher's tokens with the escape 144, before the follower-set coder), 1: Slen (256 bytes), 2: the followers (256 x 32 bytes, row x counting up to
+ * Slen [x]).  Up to cap bytes are copied; returns how many there are (0: no such entry). */
+uint64_t zada_reduce_last_record(zada_ctx *ctx, int what, uint32_t entry, uint8_t *dst, uint64_t cap);
 
 /* ---- Password-protected entries: Zip.CRC_Crypto (zip-crc_crypto.adb:78-137) ---------------------------------------
  * The traditional Zip cipher.  Update_keys (:90-99) per plaintext byte is three first-order recurrences -- a prefix CRC of the
@@ -460,7 +495,8 @@ int zada_zip_device_ex(zada_ctx *ctx, int method, int count, const zada_zip_entr
  * flag and 0xFFF5, bit 1 set again when the winner ends on a marker); name, name_len the bytes of the new headers (HOST memory).
  * approaches: a bit per approach in the reference's order: 0 original (always taken as set), 1 Preselection_2, 2 Preselection_1, 3 Shrink_1, 4 Reduce_4,
  *   5 Deflate_3, 6 Deflate_R, 7 BZip2_3, 8 BZip2_2, 9 BZip2_1, 10 LZMA_3, 11 LZMA_2.  ZADA_RZ_DEFAULT is every approach built here.  Bits 3 and 4 are
- *   ZADA_E_INVALID by name: Shrink_1 and Reduce_4 have no encoder here -- a divergence from `rezip -int`, which tries them on entries of at most
+ *   ZADA_E_INVALID by name: the device writer this call runs on does not take Shrink_1 and Reduce_4 (zada_shrink_batch / zada_reduce_batch encode them from
+ *   host buffers) -- a divergence from `rezip -int`, which tries them on entries of at most
  *   6 000 and 9 000 bytes and may choose their stream there.
  * formats: a bit per zip type the result may hold: 0 Store, 1 Deflate, 2 Deflate64, 3 BZip2, 4 LZMA (ZADA_RZ_ALL_FORMATS, _DEFLATE_OR_STORE,
  *   _FAST_DECOMPRESSION as rezip_lib.ads:46-54).  A single-method approach is considered when its format is in the set, the Preselections only with

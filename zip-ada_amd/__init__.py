@@ -22,8 +22,10 @@ LIB_PATH = os.environ.get("ZADA_LIB", os.path.join(_HERE, "libzada_hip.so"))   #
 
 
 class Method:
-    """Compression_Method'Pos, zip-compress.ads:59-122.  Shrink and Reduce are not implemented; the Preselection methods pick
-    one of the others per entry (preselect)."""
+    """Compression_Method'Pos, zip-compress.ads:59-122.  Every method has an encoder (Encoder.shrink / reduce / deflate / bzip2 / lzma and their batch
+    calls, compress_data, ZipCreate); the Preselection methods pick one of the others per entry (preselect) and never Shrink or Reduce.  Still
+    refused for Shrink_1 and Reduce_1 .. _4, by name: the device writers (zip_device, zip_device_ex), ReZip's approaches, and reading such entries
+    (UnZip: UnsupportedMethod)."""
     Store = 0
     Shrink_1 = 1
     Reduce_1, Reduce_2, Reduce_3, Reduce_4 = 2, 3, 4, 5
@@ -59,7 +61,9 @@ class ContentType:
 
 
 def _zip_type(method):
-    """The Zip format code of a single method (zip.ads:496-503): BZip2 12, LZMA 14, Deflate 8, Store 0."""
+    """The Zip format code of a single method (zip.ads:496-503): Shrink 1, Reduce_1 .. _4 2 .. 5, BZip2 12, LZMA 14, Deflate 8, Store 0."""
+    if Method.Shrink_1 <= method <= Method.Reduce_4:
+        return int(method)
     return 0 if method == Method.Store else 12 if Method.BZip2_1 <= method <= Method.BZip2_3 else 14 if Method.LZMA_0 <= method <= Method.LZMA_for_AU else 8
 
 
@@ -185,6 +189,14 @@ def load_library():
     L.zada_lzma_export_state.argtypes = [vp, vp, u64, u64p, vp, u64, u64p, u64p]
     L.zada_lzma_import_state.argtypes = [vp, vp, u64]
     L.zada_lzma_batch.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.zada_shrink.argtypes = [vp, vp, u64, vp, u64, u64p, u32p]
+    L.zada_shrink_device.argtypes = [vp, vp, u64, vp, u64, u64p, u32p]
+    L.zada_shrink_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.zada_reduce.argtypes = [vp, i32, vp, u64, vp, u64, u64p, u32p]
+    L.zada_reduce_device.argtypes = [vp, i32, vp, u64, vp, u64, u64p, u32p]
+    L.zada_reduce_batch.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.zada_reduce_last_record.restype = ctypes.c_uint64
+    L.zada_reduce_last_record.argtypes = [vp, i32, ctypes.c_uint32, vp, u64]
     L.zada_lzma_match_sets.argtypes = [vp, vp, u64, vp, vp, vp, i32]
     if hasattr(L, "zada_preselect"):                 # (an older library under ZADA_LIB, for an A/B of what both have, lacks these)
         L.zada_lzma_lit_table_bytes.restype = ctypes.c_uint64
@@ -460,6 +472,95 @@ class Encoder:
             self._err(worst, "zada_lzma_batch")
         mv = memoryview(arena)
         return [(int(rcs[i]), bytes(mv[int(offs[i]):int(offs[i]) + int(ols[i])]) if rcs[i] >= 0 and ols[i] <= caps[i] else None, int(crcs[i])) for i in range(cnt)]
+
+    # ---- Shrink_1 and Reduce_1 .. _4 (include/zada.h "Shrink_1 and Reduce_1 .. _4"): one wave per entry, so the batch calls are what fills the device ----
+    def _legacy_one(self, data, method, crc, cap):
+        n = len(data)
+        cap = int(n if cap is None else cap)
+        out = ctypes.create_string_buffer(max(cap, 1))
+        ol = ctypes.c_uint64(0)
+        c = ctypes.c_uint32(crc)
+        if method == Method.Shrink_1:
+            rc, who = self.lib.zada_shrink(self.ctx, _addr(data) if n else None, n, ctypes.addressof(out), cap, ctypes.byref(ol), ctypes.byref(c)), "zada_shrink"
+        else:
+            rc, who = self.lib.zada_reduce(self.ctx, method, _addr(data) if n else None, n, ctypes.addressof(out), cap, ctypes.byref(ol), ctypes.byref(c)), "zada_reduce"
+        if rc < 0:
+            self._err(rc, who)
+        return rc, (out.raw[:ol.value] if rc == 0 else None), ol.value, c.value
+
+    def shrink(self, data, crc=0xFFFFFFFF, cap=None):
+        """Zip.Compress.Shrink_E (Shrink_1).  Returns (rc, stream or None, stream length, running CRC register); rc 1 = the stream is not shorter than
+        the input and is not delivered.  cap defaults to len (data), which always suffices."""
+        return self._legacy_one(data, Method.Shrink_1, crc, cap)
+
+    def reduce(self, data, method=Method.Reduce_4, crc=0xFFFFFFFF, cap=None):
+        """Zip.Compress.Reduce (method 2 .. 5 = Reduce_1 .. _4).  Returns as shrink ()."""
+        return self._legacy_one(data, method, crc, cap)
+
+    def _legacy_batch(self, datas, method, crc):
+        import numpy as np
+        cnt = len(datas)
+        if cnt == 0:
+            return []
+        lens = np.fromiter((len(d) for d in datas), dtype=np.uint64, count=cnt)
+        caps = lens.copy()
+        offs = np.concatenate(([0], np.cumsum(caps)[:-1])).astype(np.uint64)
+        arena = np.empty(int(caps.sum()) + 1, dtype=np.uint8)
+        outp = (arena.ctypes.data + offs).astype(np.uint64)
+        keep = [d if len(d) else b"\0" for d in datas]
+        ins = np.fromiter((_addr(d) for d in keep), dtype=np.uint64, count=cnt)
+        ols = np.zeros(cnt, dtype=np.uint64)
+        crcs = np.full(cnt, crc, dtype=np.uint32)
+        rcs = np.zeros(cnt, dtype=np.int32)
+        if method == Method.Shrink_1:
+            worst, who = self.lib.zada_shrink_batch(self.ctx, cnt, ins.ctypes.data, lens.ctypes.data, outp.ctypes.data, caps.ctypes.data, ols.ctypes.data,
+                                                    crcs.ctypes.data, rcs.ctypes.data), "zada_shrink_batch"
+        else:
+            worst, who = self.lib.zada_reduce_batch(self.ctx, method, cnt, ins.ctypes.data, lens.ctypes.data, outp.ctypes.data, caps.ctypes.data, ols.ctypes.data,
+                                                    crcs.ctypes.data, rcs.ctypes.data), "zada_reduce_batch"
+        if worst < 0:
+            self._err(worst, who)
+        mv = memoryview(arena)
+        return [(int(rcs[i]), bytes(mv[int(offs[i]):int(offs[i]) + int(ols[i])]) if rcs[i] == 0 else None, int(crcs[i])) for i in range(cnt)]
+
+    def shrink_batch(self, datas, crc=0xFFFFFFFF):
+        """Independent Shrink_1 streams (one per Zip entry) in one call, one wave per entry.  Returns a list of (rc, stream or None, running CRC
+        register); rc 1: the stream is not shorter than the entry (Store it)."""
+        return self._legacy_batch(datas, Method.Shrink_1, crc)
+
+    def reduce_batch(self, datas, method=Method.Reduce_4, crc=0xFFFFFFFF):
+        """Independent Reduce streams (method 2 .. 5) in one call, in launch groups bounded by the knob "reduce_group_mib".  Returns as shrink_batch ()."""
+        return self._legacy_batch(datas, method, crc)
+
+    def shrink_device(self, d_in, n, d_out, cap, crc=0xFFFFFFFF):
+        """Shrink_1 stream of n bytes at device address d_in into d_out (cap bytes).  Returns (rc, length, running CRC register)."""
+        ol = ctypes.c_uint64(0)
+        c = ctypes.c_uint32(crc)
+        rc = self.lib.zada_shrink_device(self.ctx, d_in, n, d_out, cap, ctypes.byref(ol), ctypes.byref(c))
+        if rc < 0:
+            self._err(rc, "zada_shrink_device")
+        return rc, ol.value, c.value
+
+    def reduce_device(self, d_in, n, d_out, cap, method=Method.Reduce_4, crc=0xFFFFFFFF):
+        """Reduce stream (method 2 .. 5) of n bytes at device address d_in into d_out (cap bytes).  Returns (rc, length, running CRC register)."""
+        ol = ctypes.c_uint64(0)
+        c = ctypes.c_uint32(crc)
+        rc = self.lib.zada_reduce_device(self.ctx, method, d_in, n, d_out, cap, ctypes.byref(ol), ctypes.byref(c))
+        if rc < 0:
+            self._err(rc, "zada_reduce_device")
+        return rc, ol.value, c.value
+
+    def reduce_last_record(self, entry=0):
+        """Test hook (zada_reduce_last_record): what the last Reduce launch group left for its entry `entry`: (raw bytes, Slen [256] u8,
+        followers [256, 32] u8)."""
+        import numpy as np
+        k = self.lib.zada_reduce_last_record(self.ctx, 0, entry, None, 0)
+        raw = ctypes.create_string_buffer(max(int(k), 1))
+        slen, foll = np.zeros(256, np.uint8), np.zeros((256, 32), np.uint8)
+        self.lib.zada_reduce_last_record(self.ctx, 0, entry, ctypes.addressof(raw), k)
+        if self.lib.zada_reduce_last_record(self.ctx, 1, entry, slen.ctypes.data, 256) != 256 or self.lib.zada_reduce_last_record(self.ctx, 2, entry, foll.ctypes.data, 8192) != 8192:
+            raise ZadaError("zada_reduce_last_record: no such entry")
+        return raw.raw[:k], slen, foll
 
     def lzma_match_sets(self, data, stride=50):
         """Test hook: the match sets of LZMA_3's BT4 matcher at every position of `data`, as the producer kernels leave them for the coder
@@ -1270,6 +1371,10 @@ class ZipCreate:
             return self.enc.bzip2_batch(datas, method)
         if Method.LZMA_0 <= method <= Method.LZMA_for_AU:
             return self.enc.lzma_batch(datas, method)
+        if method == Method.Shrink_1:
+            return self.enc.shrink_batch(datas)
+        if Method.Reduce_1 <= method <= Method.Reduce_4:
+            return self.enc.reduce_batch(datas, method)
         return self.enc.deflate_batch(datas, method)
 
     def add_streams(self, names, datas, file_time=None, unicode_name=True, password=None, _headers=None):
@@ -1885,8 +1990,8 @@ class CompZip:
 class ReZip:
     """ReZip (tools/rezip_lib.adb, `rezip -int`) on an archive that lies in device memory: every entry is extracted and compressed on the device with
     each considered approach, and the new archive keeps per entry the smallest stream, the source's own where nothing beats it (zada_rezip_device).
-    Divergences from the reference: Shrink_1 and Reduce_4, which it tries on entries of at most 6 000 and 9 000 bytes, are not built (their approaches
-    are refused by name); an LZMA_3 entry the coder refuses loses that approach instead of getting a stream that does not decode; more than 65 534
+    Divergences from the reference: Shrink_1 and Reduce_4, which it tries on entries of at most 6 000 and 9 000 bytes, are not among the approaches here (they
+    are refused by name: the device writer under ReZip does not take them, though Encoder.shrink_batch / reduce_batch encode them); an LZMA_3 entry the coder refuses loses that approach instead of getting a stream that does not decode; more than 65 534
     kept entries are refused; the headers carry the directory's CRC-32; with lower=True two names that differ only in case are refused as duplicates,
     where the reference writes both."""
     _FORMATS = {"all": RZ_ALL_FORMATS, "deflate_or_store": RZ_DEFLATE_OR_STORE, "fast_decompression": RZ_FAST_DECOMPRESSION}

@@ -15,6 +15,7 @@
 #include "../../include/zada.h"
 #include "zada_internal.h"
 #include "zada_bt4.h"
+#include "zada_legacy.h"
 
 struct zada_ctx { zada::Ctx c; };
 
@@ -1069,6 +1070,7 @@ static void ctx_release(zada_ctx *z) {
   zip_destroy(&z->c);
   rezip_destroy(&z->c);
   find_destroy(&z->c);
+  legacy_destroy(&z->c);
   lzma_free(&z->c);
   free_workspace(&z->c);
   for (hipEvent_t e : z->c.ev_pool) hipEventDestroy(e);
@@ -1155,6 +1157,7 @@ int zada_set_knob(zada_ctx *z, const char *name, int value) {
   else if (!strcmp(name, "trained_fork")) { if (value != 0 && value != 1) return ZADA_E_INVALID; z->c.knob_trained_fork = value; }
   else if (!strcmp(name, "lzma_waves")) { if (value != 0 && value != 1 && value != 4) return ZADA_E_INVALID; z->c.knob_lzma_waves = value; }
   else if (!strcmp(name, "lzma_lit_mib")) { if (value < 1) return ZADA_E_INVALID; z->c.knob_lzma_lit_mib = value; }
+  else if (!strcmp(name, "reduce_group_mib")) { if (value < 1) return ZADA_E_INVALID; z->c.knob_reduce_group_mib = value; }
   else if (!strcmp(name, "lzma_segment")) { if (value < -1 || (value > 0 && (value < 13 || value > 30))) return ZADA_E_INVALID; z->c.knob_lzma_segment = value; }
   else return ZADA_E_INVALID;
   return ZADA_OK;
@@ -1821,6 +1824,173 @@ int zada_lzma_batch(zada_ctx *z, int method, int count, const uint8_t *const *in
   flush_group();
   return worst;
 }
+// --------------------------------------------------------------------------------------------
+// Shrink_1 and Reduce_1 .. _4: Zip.Compress.Shrink_E and Zip.Compress.Reduce (zip-compress.adb:181-195).  One wave per entry for the serial
+// stage (zada_shrink.hip, zada_reduce.hip), so the batch is what fills the device; one stream alone runs at one wave's pace.
+// A launch group: the entries on 64-byte slots of rin_own, their output slots behind them (a stream that does not beat its input is not
+// delivered, so a slot holds the entry's size), k_batch_crc's tables behind those.
+// --------------------------------------------------------------------------------------------
+static bool is_legacy_method(int method) { return method >= ZADA_SHRINK_1 && method <= ZADA_REDUCE_4; }
+constexpr uint64_t LEGACY_ENTRY_MAX = (1ull << 30) - 65536;
+// entries idx [0 .. E) of the caller's arrays through one launch group.  device: E = 1, and in [0] / out [0] are device addresses.
+static int legacy_group(Ctx *c, int method, const int *idx, uint32_t E, const uint8_t *const *in, const uint64_t *n, uint8_t *const *out, bool device,
+                        const uint64_t *cap, uint64_t *out_len, uint32_t *crc, int *rc_out) {
+  hipStream_t st = c->stream;
+  std::vector<LegacyJob> jobs(E);
+  std::vector<uint32_t> tab(3 * (size_t)E);
+  uint64_t total = 0, ototal = 0;
+  for (uint32_t e = 0; e < E; e++) {
+    const uint64_t ln = n[idx[e]];
+    jobs[e].in_off = (uint32_t)total; jobs[e].n = (uint32_t)ln; jobs[e].out_off = (uint32_t)ototal; jobs[e].cap = (uint32_t)legacy_slot(ln);
+    tab[e] = (uint32_t)total; tab[E + e] = (uint32_t)ln; tab[2 * (size_t)E + e] = crc ? crc[idx[e]] : 0xFFFFFFFFu;
+    total += legacy_slot(ln); ototal += legacy_slot(ln);
+  }
+  if (total + ototal >= (1ull << 32)) return ZADA_E_TOO_LARGE;
+  int rc = ensure_rin(c, total + ototal + 16ull * (E + 1) + 64);
+  if (!rc && !device) rc = grow_pinned((void **)&c->bstage, &c->cap_bstage, total + 64);
+  if (rc) return rc;
+  uint8_t *d_in = c->ws.rin_own, *d_out = d_in + total;
+  uint32_t *d_tab = (uint32_t *)(d_out + ototal);
+  if (device) { if (n[idx[0]]) hipMemcpyAsync(d_in, in[idx[0]], n[idx[0]], hipMemcpyDeviceToDevice, st); }
+  else {
+    parallel_entries(E, total, [&](uint32_t e) { if (jobs[e].n) memcpy(c->bstage + jobs[e].in_off, in[idx[e]], jobs[e].n); });
+    hipMemcpyAsync(d_in, c->bstage, total, hipMemcpyHostToDevice, st);
+  }
+  c->tbegin(); c->tmark("legacy:begin");
+  hipMemcpyAsync(d_tab, tab.data(), 12ull * E, hipMemcpyHostToDevice, st);
+  hipLaunchKernelGGL(k_batch_crc, dim3(E), dim3(64), 0, st, E, d_in, d_tab, d_tab + E, d_tab + 2 * E);
+  hipMemcpyAsync(tab.data() + 2 * (size_t)E, d_tab + 2 * E, 4ull * E, hipMemcpyDeviceToHost, st);
+  c->tmark("k_batch_crc");
+  std::vector<uint64_t> bytes(E);
+  rc = method == ZADA_SHRINK_1 ? shrink_encode_group(c, E, d_in, jobs.data(), d_out, bytes.data())
+                               : reduce_encode_group(c, method - ZADA_REDUCE_1 + 1, E, d_in, jobs.data(), d_out, ototal, bytes.data());
+  if (rc) { c->tend(); return rc; }
+  // the verdicts, and the streams that are delivered: in one copy of the arena's used part for a large group, one by one otherwise
+  bool bad = false;
+  uint64_t used = 0;
+  uint32_t deliver = 0;
+  for (uint32_t e = 0; e < E; e++) {
+    const int i = idx[e];
+    out_len[i] = bytes[e];
+    if (crc) crc[i] = tab[2 * (size_t)E + e];
+    rc_out[i] = bytes[e] >= n[i] ? ZADA_INEFFICIENT : ZADA_OK;                      // Write_Block, zip-compress.adb:468-490
+    if (rc_out[i] == ZADA_OK && bytes[e] > cap[i]) { rc_out[i] = ZADA_E_INVALID; bad = true; }
+    if (rc_out[i] == ZADA_OK) { deliver++; used = jobs[e].out_off + bytes[e]; }
+  }
+  if (bad) c->err = ERR_OUTPUT_TOO_SMALL;
+  if (device) {
+    if (rc_out[idx[0]] == ZADA_OK) hipMemcpyAsync(out[idx[0]], d_out, bytes[0], hipMemcpyDeviceToDevice, st);
+  } else if (deliver > 8) {
+    if ((rc = grow_pinned((void **)&c->bstage, &c->cap_bstage, used + 64))) { c->tend(); return rc; }
+    hipMemcpyAsync(c->bstage, d_out, used, hipMemcpyDeviceToHost, st);
+    if (hip_check(c, hipStreamSynchronize(st), "legacy batch out")) { c->tend(); return ZADA_E_HIP; }
+    parallel_entries(E, used, [&](uint32_t e) { if (rc_out[idx[e]] == ZADA_OK) memcpy(out[idx[e]], c->bstage + jobs[e].out_off, bytes[e]); });
+  } else {
+    for (uint32_t e = 0; e < E; e++)
+      if (rc_out[idx[e]] == ZADA_OK) hipMemcpyAsync(out[idx[e]], d_out + jobs[e].out_off, bytes[e], hipMemcpyDeviceToHost, st);
+  }
+  c->tmark("legacy:out");
+  const int sync = hip_check(c, hipStreamSynchronize(st), "legacy out");
+  c->tend();
+  if (sync) return ZADA_E_HIP;
+  return 0;
+}
+static int legacy_check_one(zada_ctx *z, int method, uint64_t n, bool null_in, const char *who) {
+  const int rc = prepare(z);
+  if (rc) return rc;
+  if (!is_legacy_method(method)) { z->c.err = std::string(who) + ": not a Shrink or Reduce method"; return ZADA_E_INVALID; }
+  if (n && null_in) { z->c.err = std::string(who) + ": null input"; return ZADA_E_INVALID; }
+  return n >= LEGACY_ENTRY_MAX ? ZADA_E_TOO_LARGE : 0;
+}
+static int legacy_host_one(zada_ctx *z, int method, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout, const char *who) {
+  int rc = legacy_check_one(z, method, n, !in, who);
+  if (rc) return rc;
+  Ctx *c = &z->c;
+  if (!out && cap) { c->err = std::string(who) + ": null output"; return ZADA_E_INVALID; }
+  const int idx = 0;
+  uint64_t ol = 0;
+  int rc1 = 0;
+  if ((rc = finish_call(c, legacy_group(c, method, &idx, 1, &in, &n, &out, false, &cap, &ol, crc_inout, &rc1))) < 0) return rc;
+  if (out_len) *out_len = ol;
+  return rc1;
+}
+}  // extern "C"
+namespace zada {
+// one stream from device memory into device memory (zada_shrink_device / zada_reduce_device; the encrypted Compress_Data)
+int legacy_device_one(zada_ctx *z, int method, const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout, const char *who) {
+  int rc = legacy_check_one(z, method, n, !d_in, who);
+  if (rc) return rc;
+  Ctx *c = &z->c;
+  if (!d_out && cap) { c->err = std::string(who) + ": null output"; return ZADA_E_INVALID; }
+  const int idx = 0;
+  uint64_t ol = 0;
+  int rc1 = 0;
+  const uint8_t *src = (const uint8_t *)d_in;
+  uint8_t *dst = (uint8_t *)d_out;
+  if ((rc = finish_call(c, legacy_group(c, method, &idx, 1, &src, &n, &dst, true, &cap, &ol, crc_inout, &rc1))) < 0) return rc;
+  if (out_len) *out_len = ol;
+  return rc1;
+}
+}  // namespace zada
+extern "C" {
+
+// ---- Shrink_1 and Reduce_1 .. _4 (include/zada.h) ----
+int zada_shrink(zada_ctx *z, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout) {
+  return legacy_host_one(z, ZADA_SHRINK_1, in, n, out, cap, out_len, crc_inout, "zada_shrink");
+}
+int zada_reduce(zada_ctx *z, int method, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout) {
+  if (z && (method < ZADA_REDUCE_1 || method > ZADA_REDUCE_4)) { z->c.err = "zada_reduce: not a Reduce method"; return ZADA_E_INVALID; }
+  return legacy_host_one(z, method, in, n, out, cap, out_len, crc_inout, "zada_reduce");
+}
+int zada_shrink_device(zada_ctx *z, const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout) {
+  return legacy_device_one(z, ZADA_SHRINK_1, d_in, n, d_out, cap, out_len, crc_inout, "zada_shrink_device");
+}
+int zada_reduce_device(zada_ctx *z, int method, const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout) {
+  if (z && (method < ZADA_REDUCE_1 || method > ZADA_REDUCE_4)) { z->c.err = "zada_reduce_device: not a Reduce method"; return ZADA_E_INVALID; }
+  return legacy_device_one(z, method, d_in, n, d_out, cap, out_len, crc_inout, "zada_reduce_device");
+}
+static int legacy_batch(zada_ctx *z, int method, int count, const uint8_t *const *in, const uint64_t *n, uint8_t *const *out, const uint64_t *cap, uint64_t *out_len,
+                        uint32_t *crc, int *rc) {
+  if (!z || count < 0 || !is_legacy_method(method)) return ZADA_E_INVALID;
+  int prc = prepare(z);
+  if (prc) return prc;
+  Ctx *c = &z->c;
+  if (count && (!in || !n || !out || !cap || !out_len || !rc)) { c->err = "legacy batch: null argument"; return ZADA_E_INVALID; }
+  int worst = 0;
+  std::vector<int> group;
+  uint64_t gbytes = 0, gwork = 0;
+  const bool reduce = method != ZADA_SHRINK_1;
+  const uint64_t work_cap = (uint64_t)c->knob_reduce_group_mib << 20;               // (Reduce's work arrays of a group: "reduce_group_mib")
+  auto flush_group = [&]() {
+    if (group.empty()) return;
+    int r = finish_call(c, legacy_group(c, method, group.data(), (uint32_t)group.size(), in, n, out, false, cap, out_len, crc, rc));
+    if (r < 0) { for (int i : group) rc[i] = r; worst = r; }
+    else { for (int i : group) if (rc[i] < 0) worst = rc[i]; }
+    group.clear(); gbytes = 0; gwork = 0;
+  };
+  for (int i = 0; i < count; i++) {
+    if (n[i] >= LEGACY_ENTRY_MAX) { rc[i] = ZADA_E_TOO_LARGE; worst = rc[i]; continue; }
+    if ((n[i] && !in[i]) || (cap[i] && !out[i])) { rc[i] = ZADA_E_INVALID; worst = rc[i]; c->err = "legacy batch: null buffer"; continue; }
+    const uint64_t slot = 2 * legacy_slot(n[i]), work = reduce ? reduce_footprint(n[i]) : 0;
+    if (!group.empty() && (gbytes + slot > (1ull << 30) || gwork + work > work_cap)) flush_group();
+    group.push_back(i); gbytes += slot; gwork += work;
+  }
+  flush_group();
+  return worst;
+}
+int zada_shrink_batch(zada_ctx *z, int count, const uint8_t *const *in, const uint64_t *n, uint8_t *const *out, const uint64_t *cap, uint64_t *out_len,
+                      uint32_t *crc, int *rc) {
+  return legacy_batch(z, ZADA_SHRINK_1, count, in, n, out, cap, out_len, crc, rc);
+}
+int zada_reduce_batch(zada_ctx *z, int method, int count, const uint8_t *const *in, const uint64_t *n, uint8_t *const *out, const uint64_t *cap, uint64_t *out_len,
+                      uint32_t *crc, int *rc) {
+  if (method < ZADA_REDUCE_1 || method > ZADA_REDUCE_4) return ZADA_E_INVALID;
+  return legacy_batch(z, method, count, in, n, out, cap, out_len, crc, rc);
+}
+uint64_t zada_reduce_last_record(zada_ctx *z, int what, uint32_t entry, uint8_t *dst, uint64_t cap) {
+  if (!z || what < 0 || what > 2 || hipSetDevice(z->c.device) != hipSuccess) return 0;
+  return reduce_last_record(&z->c, what, entry, dst, cap);
+}
 // raw CRC-32 register (started from 0) of n bytes in device memory: the piece a rank contributes to a stream's CRC
 // (zada_crc32_combine chains the pieces)
 int zada_crc32_device(zada_ctx *z, const void *d_in, uint64_t n, uint32_t *raw) {
@@ -2254,11 +2424,13 @@ int zada_compress_data(zada_ctx *z, int method, const uint8_t *in, uint64_t n, u
   uint32_t crc = 0xFFFFFFFFu;                                   // Init, zip-compress.adb:144
   const bool bz = method >= ZADA_BZIP2_1 && method <= ZADA_BZIP2_3;                  // :204-209 (bzip2_code = 12, zip.ads:502)
   const bool lz = is_lzma_method(method);                                            // :211-216 (lzma_code = 14, zip.ads:503)
+  const bool lg = is_legacy_method(method);                                          // :181-195 (shrink_code = 1, reduce_code = 2 .. 5, zip.ads)
   int rc = bz ? zada_bzip2(z, method, in, n, out, cap, out_len, &crc, nullptr, nullptr)
          : lz ? zada_lzma(z, method, in, n, out, cap, out_len, &crc, nullptr, nullptr)
+         : lg ? (method == ZADA_SHRINK_1 ? zada_shrink(z, in, n, out, cap, out_len, &crc) : zada_reduce(z, method, in, n, out, cap, out_len, &crc))
               : zada_deflate(z, method, in, n, out, cap, out_len, &crc, nullptr, nullptr);
   if (rc < 0 || rc == ZADA_ABORTED) return rc;
-  *zip_type = bz ? 12 : lz ? 14 : 8;
+  *zip_type = bz ? 12 : lz ? 14 : lg ? (uint16_t)method : 8;
   crc = ~crc;                                                   // Final :218
   if (rc == ZADA_INEFFICIENT) {                                 // :224-237 Store_data; the CRC of the same bytes is unchanged
     if (cap < n) { z->c.err = "output buffer too small"; return ZADA_E_INVALID; }
@@ -2420,8 +2592,8 @@ int zada_compress_data_pw(zada_ctx *z, int method, int content_hint, const uint8
   if (!password || pw_len == 0) { c->err = "zada_compress_data_pw: empty password (the unencrypted call is zada_compress_data)"; return ZADA_E_INVALID; }
   const int m = zada_preselect(method, content_hint, 1, n);
   if (m < 0) { c->err = "zada_compress_data_pw: method or content hint out of range"; return ZADA_E_INVALID; }
-  const bool bz = m >= ZADA_BZIP2_1 && m <= ZADA_BZIP2_3, lz = is_lzma_method(m), df = method_level(m) >= 0;
-  if (m != 0 && !bz && !lz && !df) { c->err = "unsupported method"; return ZADA_E_INVALID; }
+  const bool bz = m >= ZADA_BZIP2_1 && m <= ZADA_BZIP2_3, lz = is_lzma_method(m), df = method_level(m) >= 0, lg = is_legacy_method(m);
+  if (m != 0 && !bz && !lz && !df && !lg) { c->err = "unsupported method"; return ZADA_E_INVALID; }
   if (cap < 12) { c->err = "output buffer too small"; return ZADA_E_INVALID; }
   if (method_used) *method_used = m;
   uint32_t keys[3];
@@ -2446,10 +2618,11 @@ int zada_compress_data_pw(zada_ctx *z, int method, int content_hint, const uint8
   rc = m == 0 ? ZADA_INEFFICIENT                                  // Store: Store_data (do_write => True) :178-179, the bytes the fallback writes
      : bz ? zada_bzip2_device(z, m, d_in, n, d_out, dcap, &ol, &crc2)
      : lz ? zada_lzma_device(z, m, d_in, n, d_out, dcap, &ol, &crc2)
+     : lg ? legacy_device_one(z, m, d_in, n, d_out, dcap, &ol, &crc2, "zada_compress_data_pw")
           : zada_deflate_device(z, m, d_in, n, d_out, dcap, &ol, &crc2);
   if (rc < 0 || rc == ZADA_ABORTED) return rc;
   if (m != 0 && ~crc2 != crc) { c->err = "zada_compress_data_pw: the encoder's CRC-32 differs from the pre-scan's"; return ZADA_E_HIP; }
-  *zip_type = m == 0 ? 0 : bz ? 12 : lz ? 14 : 8;
+  *zip_type = m == 0 ? 0 : bz ? 12 : lz ? 14 : lg ? (uint16_t)m : 8;
   uint8_t *d_payload = d_out;
   if (rc == ZADA_INEFFICIENT) { d_payload = d_in; ol = n; *zip_type = 0; }     // :224-237
   if (cap - 12 < ol) { c->err = "output buffer too small"; return ZADA_E_INVALID; }

@@ -275,6 +275,8 @@ struct Ctx {
   void *zw = nullptr;                                // archive writer state (zada_zip.hip), made on first use
   void *rz = nullptr;                                // Comp_Zip state (zada_rezip.hip), made on first use
   void *fz = nullptr;                                // Find_Zip state (zada_find.hip), made on first use
+  void *lg = nullptr;                                // Shrink / Reduce state (zada_shrink.hip, zada_reduce.hip), made on first use
+  int knob_reduce_group_mib = 4096;                  // "reduce_group_mib": MiB of HBM the work arrays of one launch group of zada_reduce_batch may take (328 KiB + raw bytes per entry)
   int knob_unzip_piece = 14;                         // "unzip_piece" (test knob): log2 of the bytes of one piece of a stored entry (8 .. 14)
   void *lz_tab = nullptr; size_t cap_lz_tab = 0;     // LZMA (zada_lzma.hip): job table + results
   void *lz_save = nullptr; size_t cap_lz_save = 0;   // ... the coder's state between the launches of one stream

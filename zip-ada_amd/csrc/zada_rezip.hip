@@ -458,7 +458,7 @@ int zada_rezip_device(zada_ctx *z, const void *d_src, uint64_t src_len, int coun
   if (!archive_len || (count && (!ent || !res)) || (comment_len && !comment)) { c->err = "zada_rezip_device: null argument"; return ZADA_E_INVALID; }
   if (!d_archive || (src_len && !d_src)) { c->err = "zada_rezip_device: null archive"; return ZADA_E_INVALID; }
   if (approaches & RZ_UNBUILT) {
-    c->err = std::string("zada_rezip_device: approach ") + ((approaches >> RZ_SHRINK) & 1u ? "shrink (Shrink_1)" : "reduce_4 (Reduce_4)") + " has no encoder here";
+    c->err = std::string("zada_rezip_device: approach ") + ((approaches >> RZ_SHRINK) & 1u ? "shrink (Shrink_1)" : "reduce_4 (Reduce_4)") + " is not taken by the device writer";
     return ZADA_E_INVALID;
   }
   if (approaches >> RZ_NA || formats >> 5 || comment_len > 65535u) { c->err = "zada_rezip_device: approaches, formats or comment length out of range"; return ZADA_E_INVALID; }

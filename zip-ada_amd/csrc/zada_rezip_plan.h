@@ -76,7 +76,7 @@ inline uint64_t cz_piece_count(uint64_t n) { return (n + CZ_PIECE - 1) >> CZ_PIE
 
 // ---- ReZip (tools/rezip_lib.adb) ----
 // The approaches in the reference's order (rezip_lib.adb:79-91); the rank is the bit in the mask.  Method 0: not a single method here (original,
-// the two Preselections, and Shrink_1 / Reduce_4, which have no encoder).
+// the two Preselections, and Shrink_1 / Reduce_4, which the device writer does not take).
 constexpr int RZ_NA = 12, RZ_ORIGINAL = 0, RZ_PRESEL_2 = 1, RZ_PRESEL_1 = 2, RZ_SHRINK = 3, RZ_REDUCE_4 = 4, RZ_LZMA_3 = 10;
 constexpr int RZ_METHOD[RZ_NA] = {0, ZADA_PRESELECTION_2, ZADA_PRESELECTION_1, 0, 0, ZADA_DEFLATE_3, ZADA_DEFLATE_R, ZADA_BZIP2_3, ZADA_BZIP2_2, ZADA_BZIP2_1, ZADA_LZMA_3, ZADA_LZMA_2};
 constexpr uint32_t RZ_BUILT = 0x0FE7, RZ_UNBUILT = (1u << RZ_SHRINK) | (1u << RZ_REDUCE_4);
