@@ -100,7 +100,7 @@ enum {
                              * bytes that no window fill took up, :1000-1017, 1397-1406: lzPos lags behind readPos) and the reference's own stream does not
                              * decode to the input.  Cannot happen with the dictionary Zip.Compress.LZMA_E asks for unless the entry is beyond 256 MiB and its
                              * last window fill brings 163 .. 4 368 bytes; the shim Stores such an entry or takes another method.  Nothing was written. */
-  ZADA_E_DATA = -7          /* zada_inflate*, zada_bunzip2* and zada_unlzma* only: the compressed data is not a valid stream (Zip.Archive_corrupted); zada_last_error names the rule and the bit (zada_unlzma*: the input byte) */
+  ZADA_E_DATA = -7          /* zada_inflate*, zada_bunzip2*, zada_unlzma* and zada_unlegacy* only: the compressed data is not a valid stream (Zip.Archive_corrupted); zada_last_error names the rule and the bit (zada_unlzma*, zada_unlegacy*: the input byte) */
 };
 
 typedef struct zada_ctx zada_ctx;
@@ -125,7 +125,7 @@ const char *zada_version(void);
  * needs more gets the full 1152 and the parse starts again), "inner_budget" (ZADA_INNER_BUDGET), "shard_kib" (ZADA_SHARD_KIB: KiB of
  * a stream the match finder takes at a time, multiple of 64), "span_mib" (MiB of a stream one pass takes; longer streams go span after
  * span, default 2048), "link_run" (segments of 32 KiB one workgroup of the link stage takes one after the other, making their cross links itself:
- * a power of two from 1 to 64, 0 = by size; anything else is ZADA_E_INVALID), "batch_mib" (MiB one batch of small entries may take), "unzip_piece" (test knob: log2 of the bytes of one piece of a stored entry in zada_unzip_device, 8 .. 14, default 14),"bunzip_batch_mib" (MiB of HBM one group of zada_bunzip2_batch may take: streams, outputs, slots, tt arrays; 16 .. 262144, default 8192), "bz_batch_mib" / "bz_span_mib" / "bz_batch_melems" (BZip2
+ * a power of two from 1 to 64, 0 = by size; anything else is ZADA_E_INVALID), "batch_mib" (MiB one batch of small entries may take), "unzip_piece" (test knob: log2 of the bytes of one piece of a stored entry in zada_unzip_device, 8 .. 14, default 14), "unzip_legacy" (1 = zada_unzip_device, zada_compzip_device and zada_findzip_device also know methods 1 .. 6, Shrink / Reduce / Implode; default 0; zada_rezip_device does not look at it),"bunzip_batch_mib" (MiB of HBM one group of zada_bunzip2_batch may take: streams, outputs, slots, tt arrays; 16 .. 262144, default 8192), "bz_batch_mib" / "bz_span_mib" / "bz_batch_melems" (BZip2
  * batching; "bz_lists", "bz_list_rows", "bz_text_order", "bz_pipeline", "bz_pipe_prio", "bz_small_wg", "bz_split", "bz_tail_pct": scheduling of the BZip2 stages), "lzma_chunk" (positions of an LZMA stream one launch codes between two feedback calls; 0 = by level, -1 = one launch
  * per stream), "lzma_pool" (test knob: blocks of the LZMA_3 match sets' overflow pool to start with, 0 = by size; a pool that is too small is
  * counted and the match producer's walk runs again; for a stream whose producer works in segments the pool grows between the segments), "lzma_pool_fixed" (test knob: 1 = it
@@ -383,13 +383,51 @@ int zada_unlzma_batch(zada_ctx *ctx, int count, const uint8_t *const *in, const 
  * copied; returns how many there are. */
 uint64_t zada_unlzma_last_records(zada_ctx *ctx, uint64_t *dst, uint64_t cap_items);
 
+/* ---- The reader: UnZip.Decompress.Unshrink, Unreduce and Explode (unzip-decompress.adb:590-1418; Zip formats 1, 2 .. 5 and 6) --
+ * One Shrink, Reduce or Implode payload back into bytes: what the encoders zada_shrink* / zada_reduce* write, and what PKZIP 0.9 .. 1.1 wrote.  All
+ * three formats are chains -- an LZW code is read through the table the codes before it built, a Reduce byte through the follower set of the byte
+ * before it, an Implode symbol from the bit behind the symbol before it --, so ENTRIES are what runs in parallel: one wave per entry
+ * (csrc/zada_unlegacy.hip), use zada_unlegacy_batch for many of them, where ONE STREAM ALONE RUNS AT ONE WAVE'S PACE.  The tables
+ * are in LDS; one kernel per format.
+ *   method    : 1 Shrink, 2 .. 5 Reduce with factor 1 .. 4, 6 Implode; anything else is ZADA_E_INVALID.
+ *   flags     : Implode only, the entry's general-purpose flags: bit 1 (value 2) = 8 KiB dictionary, bit 2 (value 4) = three trees.  Other bits
+ *               and other methods: ignored.
+ *   cap       : the uncompressed size the directory promises.  THE STREAM ENDS WHEN cap BYTES ARE OUT: none of the formats has an end code.
+ *   crc_inout, out_len as for zada_inflate; in_used counts through the byte that held the last bit consumed; trailing bytes are not an error.
+ * A stream is valid when the reference's decoder accepts it, with two departures: a code, a table byte or an extra field that needs a byte beyond
+ * n_in is ULG_R_INPUT_END (the reference reads on in whatever its buffer holds and leaves it to the CRC), and a string or a copy that would pass
+ * cap is ULG_R_OUTPUT_FULL (the reference's unsigned count wraps).  The other rules of enum UlgRule (csrc/zada_unlegacy_logic.h), each
+ * ZADA_E_DATA: ULG_R_SHRINK_FIRST (the first code is no literal), ULG_R_SHRINK_CODE_SIZE (256, 1 with 13 bits already), ULG_R_SHRINK_SPECIAL
+ * (256, x with x not 1 or 2), ULG_R_SHRINK_STACK (a string of more than 8193 stack bytes: this also ends the cycles a damaged stream can make),
+ * ULG_R_IMPLODE_RUNS (the runs of a tree's lengths pass or miss the tree's size), ULG_R_IMPLODE_TREE (a tree incomplete or over-subscribed).
+ * A Shrink code whose node is free is an orphan and is read as the reference reads it (Last_Incode with Last_Outcode on the stack), a full table
+ * adds nothing, Reduce's follower sets take Slen up to 63, and a copy of Reduce or Implode whose source lies in front of the entry's first byte
+ * reads 0 there.  Shrink with cap = 0 reads nothing; Reduce and Implode read their tables first.  zada_last_error names the rule and the input
+ * byte; nothing is delivered for such an entry (*out_len = *in_used = 0, the CRC register stays).  Nothing is read beyond n_in, nothing written
+ * beyond cap.  Argument checks come before anything touches the device; a stream or a cap of 1 TiB or more is ZADA_E_TOO_LARGE. */
+int zada_unlegacy(zada_ctx *ctx, int method, int flags, const uint8_t *in, uint64_t n_in, uint8_t *out, uint64_t cap,
+                  uint64_t *out_len, uint64_t *in_used, uint32_t *crc_inout);
+/* the same with the payload and the output in device memory, at any alignment */
+int zada_unlegacy_device(zada_ctx *ctx, int method, int flags, const void *d_in, uint64_t n_in, void *d_out, uint64_t cap,
+                         uint64_t *out_len, uint64_t *in_used, uint32_t *crc_inout);
+/* `count` independent payloads (one per Zip entry), method [i] and flags [i] per entry (flags may be NULL: all 0); one batch may mix methods.  The
+ * entries are staged in groups of up to "batch_mib" MiB of streams and outputs; a group takes one launch per format present, whose waves take the
+ * entries longest first.  rc [i] is ZADA_OK or ZADA_E_DATA per entry, crc [i] in/out; the call returns the worst rc.  `out` may be NULL: the
+ * decoded bytes then stay on the device (UnZip's test_only). */
+int zada_unlegacy_batch(zada_ctx *ctx, int count, const uint8_t *const *in, const uint64_t *n_in, uint8_t *const *out, const uint64_t *cap,
+                        const uint16_t *method, const uint8_t *flags, uint64_t *out_len, uint64_t *in_used, uint32_t *crc, int *rc);
+/* What the last zada_unlegacy* call on the context found, as 64-bit values, four per entry: the UlgRule broken (0: none), the input byte and the
+ * output position where the decoder stood, 0.  Up to cap_items values are copied; returns how many there are. */
+uint64_t zada_unlegacy_last_records(zada_ctx *ctx, uint64_t *dst, uint64_t cap_items);
+
 /* ---- The reader: an archive that lies in device memory, extracted into device memory -----------------------------------
  * `count` entries of one archive in ONE call, every method the reader decodes: what UnZip.Extract does entry after entry (unzip.adb), with no entry
  * byte crossing the host.  ent [i] is the entry's row of the directory:
  *   in_off, n_in  : its data, archive bytes [in_off, in_off + n_in), the 12-byte encryption header included
  *   out_off, cap  : its output, bytes [out_off, out_off + cap) of d_out; cap = the uncompressed size the directory promises
- *   method        : 0 Store, 8 Deflate, 9 Deflate64, 12 BZip2, 14 LZMA
- *   flags         : bit 0: encrypted (CRC_Crypto), bit 1: the LZMA stream ends on the marker (eos)
+ *   method        : 0 Store, 8 Deflate, 9 Deflate64, 12 BZip2, 14 LZMA; with the knob "unzip_legacy" = 1 also 1 Shrink, 2 .. 5 Reduce, 6 Implode
+ *   flags         : bit 0: encrypted (CRC_Crypto), bit 1: the LZMA stream ends on the marker (eos); in a method-6 row bits 1 and 2 are the entry's
+ *                   general-purpose bits 1 and 2 (8 KiB dictionary, three trees)
  *   check         : encrypted: the byte the decoded encryption header must end in (crc >> 24, or the time stamp's high byte with flag bit 3)
  * d_archive (archive_len bytes) and d_out (out_bytes bytes) are device addresses at any byte alignment, in_off and out_off any values.  The archive is
  * never written: encrypted data are decoded out of place, from keys0 -- the keys of the password (zada_crypt_init_keys), the same for every entry --
@@ -400,7 +438,10 @@ uint64_t zada_unlzma_last_records(zada_ctx *ctx, uint64_t *dst, uint64_t cap_ite
  * counts archive bytes (with the 12 header bytes of an encrypted entry; Store: n_in).  ZADA_OK and ZADA_E_DATA are what the method's decoder above gives
  * for the same bytes, by the same rules: Deflate, Deflate64, BZip2 and LZMA entries run through the same launches as zada_inflate_batch,
  * zada_bunzip2_batch and zada_unlzma_batch (whose bounds on work arrays hold: the work-array half of "bunzip_batch_mib", "lzma_lit_mib"), their jobs
- * pointing into the archive -- or the decoded copy -- and into d_out.  An encrypted entry shorter than 12 bytes is ZADA_E_DATA; so is a stored entry
+ * pointing into the archive -- or the decoded copy -- and into d_out.  With "unzip_legacy" = 1 (default 0: behaviour and every text as without the
+ * knob) Shrink, Reduce and Implode entries run the same way through the launches of zada_unlegacy_batch, and the text for an unknown method lists
+ * all eleven; zada_compzip_device and zada_findzip_device, which run on this call's launches, honour the knob too.  zada_rezip_device does NOT and
+ * keeps refusing such sources: a kept source stream of method 6 would have to carry its flag bits into the new headers -- a follow-up.  An encrypted entry shorter than 12 bytes is ZADA_E_DATA; so is a stored entry
  * with more bytes (less the header) than cap, otherwise its out_len is that length.  A failed entry delivers nothing (out_len = in_used = 0, the
  * register unchanged).  Stored entries are copied and summed in one pass, parallel INSIDE an entry: pieces of 16 KiB (test knob "unzip_piece": log2 of
  * the piece, 8 .. 14; it changes no byte), one wave per piece, then one wave per entry folds the pieces' registers.

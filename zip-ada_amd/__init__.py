@@ -24,8 +24,9 @@ LIB_PATH = os.environ.get("ZADA_LIB", os.path.join(_HERE, "libzada_hip.so"))   #
 class Method:
     """Compression_Method'Pos, zip-compress.ads:59-122.  Every method has an encoder (Encoder.shrink / reduce / deflate / bzip2 / lzma and their batch
     calls, compress_data, ZipCreate); the Preselection methods pick one of the others per entry (preselect) and never Shrink or Reduce.  Still
-    refused for Shrink_1 and Reduce_1 .. _4, by name: the device writers (zip_device, zip_device_ex), ReZip's approaches, and reading such entries
-    (UnZip: UnsupportedMethod)."""
+    refused for Shrink_1 and Reduce_1 .. _4, by name: the device writers (zip_device, zip_device_ex) and ReZip's approaches and sources.  Reading such
+    entries -- and Implode entries, which have no encoder here -- is opt-in: Encoder.unlegacy*, UnZip / CompZip / FindZip (encoder, legacy=True);
+    without the keyword they stay UnsupportedMethod."""
     Store = 0
     Shrink_1 = 1
     Reduce_1, Reduce_2, Reduce_3, Reduce_4 = 2, 3, 4, 5
@@ -233,6 +234,12 @@ def load_library():
         L.zada_unlzma_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.zada_unlzma_last_records.restype = u64
         L.zada_unlzma_last_records.argtypes = [vp, vp, u64]
+    if hasattr(L, "zada_unlegacy"):                  # (likewise: the Shrink / Reduce / Implode reader)
+        L.zada_unlegacy.argtypes = [vp, i32, i32, vp, u64, vp, u64, u64p, u64p, u32p]
+        L.zada_unlegacy_device.argtypes = [vp, i32, i32, vp, u64, vp, u64, u64p, u64p, u32p]
+        L.zada_unlegacy_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.zada_unlegacy_last_records.restype = u64
+        L.zada_unlegacy_last_records.argtypes = [vp, vp, u64]
     if hasattr(L, "zada_unzip_device"):              # (likewise: the archive reader on device memory)
         L.zada_unzip_device.argtypes = [vp, vp, u64, vp, u64, i32, vp, u32p, vp]
     if hasattr(L, "zada_zip_device"):                # (likewise: the archive writer on device memory)
@@ -339,6 +346,7 @@ class Encoder:
 
     def set_knob(self, name, value):
         """Tuning / test knobs ("budget", "max_demand_rounds", "inner_budget", "shard_kib", "span_mib", "batch_mib", "bunzip_batch_mib", "inflate_par_chunk_kib", "inflate_par_repair_pct", "inflate_par_min_kib"); none changes a byte of output.
+        "unzip_legacy" = 1: unzip_device, compzip_device and findzip_device know methods 1 .. 6 (UnZip / CompZip / FindZip set it around their calls).
         "lzma_dict" is the reference's dictionary_size parameter for LZMA_3 (0 = the entry's size, what Zip.Compress.LZMA_E passes).
         "trained_fork" = 0: TrainedCompression works through every entry's whole stream (the same bytes; for measurements)."""
         if self.lib.zada_set_knob(self.ctx, name.encode(), int(value)) != 0:
@@ -1044,6 +1052,76 @@ class Encoder:
             self._err(rc, "zada_unlzma_device")
         return ol.value, iu.value, c.value
 
+    # ---- the reader: Unshrink, Unreduce, Explode (unzip-decompress.adb:590-1418; include/zada.h "Unshrink, Unreduce and Explode") ----
+    def unlegacy(self, payload, cap, method, flags=0, crc=0xFFFFFFFF):
+        """One Shrink (method 1), Reduce (2 .. 5) or Implode (6) payload.  cap: the uncompressed size the directory promises -- the stream ends when cap
+        bytes are out, none of the formats has an end code.  flags: the entry's general-purpose flags (Implode: bit 1 = 8 KiB dictionary, bit 2 = three
+        trees).  Returns (bytes, input bytes used, running CRC register).  Raises DataError."""
+        n, cap = len(payload), int(cap)
+        out = ctypes.create_string_buffer(max(cap, 1))
+        ol, iu, c = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(crc)
+        rc = self.lib.zada_unlegacy(self.ctx, int(method), int(flags), _addr(payload) if n else None, n, ctypes.addressof(out), cap, ctypes.byref(ol), ctypes.byref(iu),
+                                    ctypes.byref(c))
+        if rc != 0:
+            self._err(rc, "zada_unlegacy")
+        return out.raw[:ol.value], iu.value, c.value
+
+    def unlegacy_batch(self, streams, caps, methods, flags=None, crc=0xFFFFFFFF, deliver=True):
+        """Independent Shrink / Reduce / Implode payloads (one per Zip entry), one wave per entry, in groups bounded by "batch_mib"; one batch may mix
+        methods (one launch per format present).  caps [i], methods [i] per entry (methods: one for all, or one per entry); flags: None, one value
+        for all, or one per entry.  Returns a list of (rc, bytes or None, bytes written, input bytes used, running CRC register); rc is 0 or E_DATA.
+        deliver = False: the bytes stay on the device (UnZip's test_only)."""
+        import numpy as np
+        cnt = len(streams)
+        if cnt == 0:
+            return []
+        lens = np.fromiter((len(d) for d in streams), dtype=np.uint64, count=cnt)
+        caps = np.ascontiguousarray(np.array(caps, dtype=np.uint64))
+        if len(caps) != cnt:
+            raise ZadaError("unlegacy_batch: one cap per stream")
+        meth = np.full(cnt, int(methods), dtype=np.uint16) if isinstance(methods, int) else np.ascontiguousarray(np.array([int(m) for m in methods], dtype=np.uint16))
+        flg = (np.full(cnt, 0 if flags is None else int(flags) & 0xFF, dtype=np.uint8) if flags is None or isinstance(flags, int)
+               else np.ascontiguousarray(np.array([int(f) & 0xFF for f in flags], dtype=np.uint8)))
+        if len(meth) != cnt or len(flg) != cnt:
+            raise ZadaError("unlegacy_batch: one method and one flags value per stream")
+        total = sum(int(x) for x in caps)                  # (Python integers: the sizes may come from a directory that lies)
+        if total >= 1 << 40:
+            raise ZadaError("unlegacy_batch: %d bytes of output are promised -- more than this machine holds" % total)
+        keep = [d if len(d) else b"\0" for d in streams]
+        ins = np.fromiter((_addr(d) for d in keep), dtype=np.uint64, count=cnt)
+        offs = np.concatenate(([0], np.cumsum(caps)[:-1])).astype(np.uint64)
+        try:
+            arena = np.empty(total + 1 if deliver else 1, dtype=np.uint8)
+        except (MemoryError, ValueError):
+            raise ZadaError("unlegacy_batch: %d bytes of output are promised -- more than this machine holds" % total)
+        outp = (arena.ctypes.data + offs).astype(np.uint64)
+        ols, ius = np.zeros(cnt, dtype=np.uint64), np.zeros(cnt, dtype=np.uint64)
+        crcs = np.full(cnt, crc, dtype=np.uint32)
+        rcs = np.zeros(cnt, dtype=np.int32)
+        worst = self.lib.zada_unlegacy_batch(self.ctx, cnt, ins.ctypes.data, lens.ctypes.data, outp.ctypes.data if deliver else None, caps.ctypes.data,
+                                             meth.ctypes.data, flg.ctypes.data, ols.ctypes.data, ius.ctypes.data, crcs.ctypes.data, rcs.ctypes.data)
+        if worst < 0 and worst != E_DATA:
+            self._err(worst, "zada_unlegacy_batch")
+        mv = memoryview(arena)
+        return [(int(rcs[i]), bytes(mv[int(offs[i]):int(offs[i]) + int(ols[i])]) if deliver and rcs[i] == 0 else None, int(ols[i]), int(ius[i]), int(crcs[i]))
+                for i in range(cnt)]
+
+    def unlegacy_last_records(self):
+        """The last unlegacy* call: per entry (rule broken or 0, input byte, output position, 0) as a numpy array of 64-bit values."""
+        import numpy as np
+        n = self.lib.zada_unlegacy_last_records(self.ctx, None, 0)
+        a = np.zeros(max(int(n), 1), dtype=np.uint64)
+        self.lib.zada_unlegacy_last_records(self.ctx, a.ctypes.data, int(n))
+        return a[:int(n)].reshape(-1, 4)
+
+    def unlegacy_device(self, d_in_ptr, n_in, d_out_ptr, cap, method, flags=0, crc=0xFFFFFFFF):
+        """Device-resident variant (HBM addresses of any alignment).  Returns (bytes written, input bytes used, running CRC register); raises DataError."""
+        ol, iu, c = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(crc)
+        rc = self.lib.zada_unlegacy_device(self.ctx, int(method), int(flags), d_in_ptr, n_in, d_out_ptr, cap, ctypes.byref(ol), ctypes.byref(iu), ctypes.byref(c))
+        if rc != 0:
+            self._err(rc, "zada_unlegacy_device")
+        return ol.value, iu.value, c.value
+
     # ---- the archive reader on device memory (include/zada.h "an archive that lies in device memory") ----
     @staticmethod
     def unzip_dtypes():
@@ -1416,12 +1494,13 @@ class ZipCreate:
         for name, payload, crc, usize, zt in plain:
             self.add_compressed(name, payload, crc, usize, zt, file_time, unicode_name)
 
-    def add_compressed(self, name, payload, crc, usize, zt, file_time=None, unicode_name=True, password=None):
+    def add_compressed(self, name, payload, crc, usize, zt, file_time=None, unicode_name=True, password=None, flag_bits=0):
         """Entry whose payload was compressed elsewhere (another rank / GPU): the bytes written
         are those Add_Stream would have written for the same payload.  With a password the payload is what Compress_Data left for it -- the
-        encryption header and the encoded stream -- and the entry carries Encryption_Flag_Bit (zip-create.adb:221-223)."""
+        encryption header and the encoded stream -- and the entry carries Encryption_Flag_Bit (zip-create.adb:221-223).  flag_bits: an Implode
+        payload's (zt = 6) general-purpose bits 1 and 2 -- 8 KiB dictionary, three trees --, which say how it was written; ignored otherwise."""
         nm = name.replace("\\", "/").encode("utf-8")
-        e = dict(name=nm, flag=(0x0800 if unicode_name else 0) | (0x0002 if zt == 14 else 0) | (0x0001 if password else 0),   # LZMA_EOS_Flag_Bit, zip-create.adb:266-278
+        e = dict(name=nm, flag=(0x0800 if unicode_name else 0) | (0x0002 if zt == 14 else 0) | (0x0001 if password else 0) | (flag_bits & 6 if zt == 6 else 0),   # LZMA_EOS_Flag_Bit, zip-create.adb:266-278
                  zip_type=zt, time=self.DEFAULT_TIME if file_time is None else file_time,
                  crc=crc, csize=len(payload), usize=usize, offset=len(self.buf) + self._bias)
         self._check_size(usize)
@@ -1686,15 +1765,19 @@ class UnZip:
     extract_device does the same for an archive that lies in device memory (ZipInfo.load_device), into device memory, in ONE zada_unzip_device call.
     UnZip (encoder, parallel_inflate=KiB) -- experimental -- sends Deflate entries whose compressed size is at least that many KiB through
     Encoder.inflate_par, one stream on many waves: extract calls it entry by entry (last_parallel lists their records), extract_device sets the knob
-    "inflate_par_min_kib" around its call (Encoder.inflate_par_last then holds the sums).  Results, exceptions and texts are the default's."""
+    "inflate_par_min_kib" around its call (Encoder.inflate_par_last then holds the sums).  Results, exceptions and texts are the default's.
+    UnZip (encoder, legacy=True) also decodes Shrink (1), Reduce (2 .. 5) and Implode (6) entries: all of a call through ONE unlegacy_batch (one wave
+    per entry; an Implode entry's general-purpose bits 1 and 2 say how it was written); extract_device sets the knob "unzip_legacy" around its call.
+    Without legacy=True they are UnsupportedMethod, in the words of before."""
 
     _NAMES = {1: "Shrink", 2: "Reduce_1", 3: "Reduce_2", 4: "Reduce_3", 5: "Reduce_4", 6: "Implode", 12: "BZip2", 14: "LZMA", 98: "PPMd", 99: "AES"}
-    _STREAMS = {8: "Deflate", 9: "Deflate64", 12: "BZip2", 14: "LZMA"}
+    _STREAMS = {1: "Shrink", 2: "Reduce", 3: "Reduce", 4: "Reduce", 5: "Reduce", 6: "Implode", 8: "Deflate", 9: "Deflate64", 12: "BZip2", 14: "LZMA"}
 
-    def __init__(self, encoder, bzip2=False, lzma=False, parallel_inflate=None):
+    def __init__(self, encoder, bzip2=False, lzma=False, parallel_inflate=None, legacy=False):
         self.enc = encoder
         self.bzip2 = bool(bzip2)
         self.lzma = bool(lzma)
+        self.legacy = bool(legacy)
         if parallel_inflate is not None and int(parallel_inflate) < 1:
             raise ZadaError("UnZip: parallel_inflate is a size in KiB, at least 1, or None")
         self.parallel_inflate = None if parallel_inflate is None else int(parallel_inflate)
@@ -1702,7 +1785,7 @@ class UnZip:
 
     def _unsupported(self, e):
         """The UnsupportedMethod of an entry this reader's gates exclude, or None."""
-        if e.method in (0, 8, 9) or (self.bzip2 and e.method == 12) or (self.lzma and e.method == 14):
+        if e.method in (0, 8, 9) or (self.bzip2 and e.method == 12) or (self.lzma and e.method == 14) or (self.legacy and 1 <= e.method <= 6):
             return None
         if self.lzma:
             return UnsupportedMethod("entry %r: method %d (%s) is not decoded by this reader: Store, Deflate, Deflate64%s and LZMA only%s"
@@ -1793,6 +1876,10 @@ class UnZip:
         todo = [k for k in range(len(ents)) if k not in res and ents[k].method == 14]
         if todo:
             settle(todo, self.enc.unlzma_batch([payload[k] for k in todo], [ents[k].usize for k in todo], [bool(ents[k].flags & 2) for k in todo], deliver=not test_only))
+        todo = [k for k in range(len(ents)) if k not in res and 1 <= ents[k].method <= 6]
+        if todo:
+            settle(todo, self.enc.unlegacy_batch([payload[k] for k in todo], [ents[k].usize for k in todo], [ents[k].method for k in todo],
+                                                 [ents[k].flags & 6 for k in todo], deliver=not test_only))
         for k, e in enumerate(ents):
             if k in res:
                 continue
@@ -1840,7 +1927,7 @@ class UnZip:
             slots = (tab["cap"] + np.uint64(255)) & ~np.uint64(255)
             tab["out_off"] = np.cumsum(slots) - slots
             total = int(slots.sum())
-            tab["flags"] = crypt | col(lambda e: e.flags & 2, np.uint8)
+            tab["flags"] = crypt | col(lambda e: e.flags & (6 if e.method == 6 else 2), np.uint8)
             # the header's last byte (zip-compress.adb:153-161; bit 3: the time stamp)
             tab["check"] = col(lambda e: ((e.dos_time >> 8) if e.flags & 8 else (e.crc >> 24)) & 0xFF, np.uint8)
             out = None if test_only else torch.empty(max(total, 1), dtype=torch.uint8, device=t.device)
@@ -1848,11 +1935,15 @@ class UnZip:
             torch.cuda.current_stream(t.device).synchronize()
             if self.parallel_inflate is not None:
                 self.enc.set_knob("inflate_par_min_kib", self.parallel_inflate)
+            if self.legacy:
+                self.enc.set_knob("unzip_legacy", 1)
             try:
                 _, r = self.enc.unzip_device(t.data_ptr(), t.numel(), None if out is None else out.data_ptr(), 0 if out is None else total, tab, keys0)
             finally:
                 if self.parallel_inflate is not None:
                     self.enc.set_knob("inflate_par_min_kib", 0)
+                if self.legacy:
+                    self.enc.set_knob("unzip_legacy", 0)
             good = (r["rc"] == 0) & (r["out_len"] == usize) & ((r["crc"] ^ np.uint32(0xFFFFFFFF)) == col(lambda e: e.crc, np.uint32))
             if out is not None:                                # every good entry's view in one split: cuts in front of and behind each
                 cuts = np.stack((tab["out_off"], tab["out_off"] + np.where(good, usize, 0).astype(np.uint64)), axis=1).reshape(-1)
@@ -1911,11 +2002,12 @@ def zip_load_order(info, who="Zip.Load"):
 class CompZip:
     """Comp_Zip_Prc (tools/comp_zip_prc.adb) on two archives that lie in device memory: every entry of archive 1, in Zip.Traverse's order, is looked up
     by name in archive 2 (case-sensitive, '\\' = '/'), both are extracted on the device and compared there (zada_compzip_device); no entry byte
-    crosses the host.  Every method the reader decodes takes part (Store, Deflate, Deflate64, BZip2, LZMA); any other raises UnsupportedMethod in
-    UnZip's words, an encrypted entry without a password WrongPassword."""
+    crosses the host.  Every method the reader decodes takes part (Store, Deflate, Deflate64, BZip2, LZMA; with legacy=True also Shrink, Reduce and
+    Implode); any other raises UnsupportedMethod in UnZip's words, an encrypted entry without a password WrongPassword."""
 
-    def __init__(self, encoder):
+    def __init__(self, encoder, legacy=False):
         self.enc = encoder
+        self.legacy = bool(legacy)
 
     def compare_device(self, info1, info2, password=None):
         """info1, info2: ZipInfo.load_device of two tensors on the encoder's device; password: of both archives.  -> CompZipResult"""
@@ -1929,7 +2021,7 @@ class CompZip:
                 raise ZadaError("CompZip.compare_device: an archive tensor lies on %s, not on the encoder's device" % t.device)
         order1 = zip_load_order(info1, "CompZip.compare_device (archive 1)")
         dir2 = dict(zip_load_order(info2, "CompZip.compare_device (archive 2)"))
-        reader = UnZip(self.enc, bzip2=True, lzma=True)
+        reader = UnZip(self.enc, bzip2=True, lzma=True, legacy=self.legacy)
         pairs = [(key, e, dir2.get(key)) for key, e in order1]
         for _, e1, e2 in pairs:
             for e in (e1, e2) if e2 is not None else (e1,):        # (the C call looks at every row of archive 1, the missing pairs' too)
@@ -1949,7 +2041,7 @@ class CompZip:
             tab["in_off"], tab["n_in"], tab["method"] = col(lambda e: e.data_offset), col(lambda e: e.csize), method
             # (a stored entry gets room for what is stored, as there)
             tab["cap"] = np.where(method == 0, col(lambda e: max(e.csize - 12, 0) if e.encrypted else e.csize), col(lambda e: e.usize))
-            tab["flags"] = crypt | col(lambda e: e.flags & 2, np.uint8) | np.fromiter((CZ_ABSENT if e is None else 0 for e in ents), np.uint8, n)
+            tab["flags"] = crypt | col(lambda e: e.flags & (6 if e.method == 6 else 2), np.uint8) | np.fromiter((CZ_ABSENT if e is None else 0 for e in ents), np.uint8, n)
             tab["check"] = col(lambda e: ((e.dos_time >> 8) if e.flags & 8 else (e.crc >> 24)) & 0xFF, np.uint8)
             return tab
         out = CompZipResult()
@@ -1957,7 +2049,13 @@ class CompZip:
         if n:
             keys0 = self.enc.crypt_init_keys(password) if password is not None else None
             torch.cuda.current_stream(t1.device).synchronize()
-            r = self.enc.compzip_device(t1.data_ptr(), t1.numel(), t2.data_ptr(), t2.numel(), table([p[1] for p in pairs]), table([p[2] for p in pairs]), keys0)
+            if self.legacy:
+                self.enc.set_knob("unzip_legacy", 1)
+            try:
+                r = self.enc.compzip_device(t1.data_ptr(), t1.numel(), t2.data_ptr(), t2.numel(), table([p[1] for p in pairs]), table([p[2] for p in pairs]), keys0)
+            finally:
+                if self.legacy:
+                    self.enc.set_knob("unzip_legacy", 0)
         for k, (key, e1, e2) in enumerate(pairs):
             out.total_1 += 1
             v, pos, cmpd, err = int(r["verdict"][k]), int(r["position"][k]), int(r["compared"][k]), None
@@ -2104,11 +2202,12 @@ class FindZipResult:
 class FindZip:
     """Find_Zip (tools/find_zip.adb) on an archive that lies in device memory: every entry, in Zip.Traverse's order, is extracted on the device and
     searched there for a string (zada_findzip_device); no entry byte crosses the host.  The names are searched on the host.  Every method the reader
-    decodes takes part (Store, Deflate, Deflate64, BZip2, LZMA); any other raises UnsupportedMethod in UnZip's words, an encrypted entry without a
-    password WrongPassword."""
+    decodes takes part (Store, Deflate, Deflate64, BZip2, LZMA; with legacy=True also Shrink, Reduce and Implode); any other raises UnsupportedMethod
+    in UnZip's words, an encrypted entry without a password WrongPassword."""
 
-    def __init__(self, encoder):
+    def __init__(self, encoder, legacy=False):
         self.enc = encoder
+        self.legacy = bool(legacy)
 
     def find_device(self, info, text, ignore_case=True, password=None):
         """info: ZipInfo.load_device of a tensor on the encoder's device; text: bytes, or a str taken as Latin-1 (1 .. 1024 bytes, else ValueError);
@@ -2122,7 +2221,7 @@ class FindZip:
         if t.device.type != "cuda" or t.device.index != self.enc.device:
             raise ZadaError("FindZip.find_device: the archive tensor lies on %s, not on the encoder's device" % t.device)
         order = zip_load_order(info, "FindZip.find_device")
-        reader = UnZip(self.enc, bzip2=True, lzma=True)
+        reader = UnZip(self.enc, bzip2=True, lzma=True, legacy=self.legacy)
         for _, e in order:
             ex = reader._unsupported(e)
             if ex is None and e.encrypted and password is None:
@@ -2139,11 +2238,17 @@ class FindZip:
             crypt, method = col(lambda e: e.encrypted, np.uint8), col(lambda e: e.method, np.uint16)
             tab["in_off"], tab["n_in"], tab["method"] = col(lambda e: e.data_offset), col(lambda e: e.csize), method
             tab["cap"] = np.where(method == 0, col(lambda e: max(e.csize - 12, 0) if e.encrypted else e.csize), col(lambda e: e.usize))
-            tab["flags"] = crypt | col(lambda e: e.flags & 2, np.uint8)
+            tab["flags"] = crypt | col(lambda e: e.flags & (6 if e.method == 6 else 2), np.uint8)
             tab["check"] = col(lambda e: ((e.dos_time >> 8) if e.flags & 8 else (e.crc >> 24)) & 0xFF, np.uint8)
             keys0 = self.enc.crypt_init_keys(password) if password is not None else None
             torch.cuda.current_stream(t.device).synchronize()
-            r = self.enc.findzip_device(t.data_ptr(), t.numel(), tab, text, ignore_case, keys0)
+            if self.legacy:
+                self.enc.set_knob("unzip_legacy", 1)
+            try:
+                r = self.enc.findzip_device(t.data_ptr(), t.numel(), tab, text, ignore_case, keys0)
+            finally:
+                if self.legacy:
+                    self.enc.set_knob("unzip_legacy", 0)
         for k, (key, e) in enumerate(order):
             rc = int(r["rc"][k])
             err = WrongPassword("entry %r: wrong password" % e.name) if rc == E_PASSWORD else reader._verdict(e, rc, int(r["out_len"][k]), int(r["crc"][k]))

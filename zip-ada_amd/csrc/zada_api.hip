@@ -1066,6 +1066,7 @@ static void ctx_release(zada_ctx *z) {
   inflate_par_destroy(&z->c);
   bunzip2_destroy(&z->c);
   unlzma_destroy(&z->c);
+  unlegacy_destroy(&z->c);
   unzip_destroy(&z->c);
   zip_destroy(&z->c);
   rezip_destroy(&z->c);
@@ -1136,6 +1137,7 @@ int zada_set_knob(zada_ctx *z, const char *name, int value) {
   else if (!strcmp(name, "bz_split")) { if (value < 0 || value > 1) return ZADA_E_INVALID; z->c.knob_bz_split = value; }
   else if (!strcmp(name, "bz_small_wg")) { if (value < 0 || value > 1) return ZADA_E_INVALID; z->c.knob_bz_small_wg = value; }
   else if (!strcmp(name, "bz_lists")) { if (value < -1) return ZADA_E_INVALID; z->c.knob_bz_lists = value; }
+  else if (!strcmp(name, "unzip_legacy")) { if (value < 0 || value > 1) return ZADA_E_INVALID; z->c.knob_unzip_legacy = value; }
   else if (!strcmp(name, "batch_mib")) { if (value < 1 || value > 1024) return ZADA_E_INVALID; z->c.knob_batch_mib = value; }
   else if (!strcmp(name, "inflate_par_chunk_kib")) { if (value < 4 || value > 65536) return ZADA_E_INVALID; z->c.knob_infp_chunk_kib = value; }
   else if (!strcmp(name, "inflate_par_repair_pct")) { if (value < 0 || value > 100) return ZADA_E_INVALID; z->c.knob_infp_repair_pct = value; }

@@ -252,10 +252,10 @@ int zada_findzip_device(zada_ctx *z, const void *d_archive, uint64_t archive_len
   int rc = fz_text(c, "zada_findzip_device", text, text_len, flags, N);
   if (rc) return rc;
   int bad = -1, why = 0;
-  rc = fz_check(ent, count, archive_len, keys0 != nullptr, &bad, &why);
+  rc = fz_check(ent, count, archive_len, keys0 != nullptr, &bad, &why, c->knob_unzip_legacy);
   if (rc) {
     char buf[200];
-    snprintf(buf, sizeof buf, "zada_findzip_device: entry %d: %s", bad, uz_why_text(why));
+    snprintf(buf, sizeof buf, "zada_findzip_device: entry %d: %s", bad, uz_why_text(why, c->knob_unzip_legacy));
     c->err = buf;
     return rc;
   }
@@ -273,7 +273,7 @@ int zada_findzip_device(zada_ctx *z, const void *d_archive, uint64_t archive_len
     c->timing.clear();
   };
   std::vector<zada_unzip_entry> rows(ent, ent + count);
-  for (zada_unzip_entry &e : rows) e.flags &= 3u;
+  for (zada_unzip_entry &e : rows) e.flags &= e.method == 6 ? 7u : 3u;   // (an Implode row keeps its general-purpose bit 2)
   std::vector<int> ends;
   fz_groups(rows.data(), count, (uint64_t)c->knob_batch_mib << 20, ends);
   std::vector<zada_unzip_result> ur;

@@ -167,13 +167,13 @@ FZ_HD void fz_lane_text(const Load &ld, uint64_t e, uint32_t L, uint64_t base, u
 // Groups of consecutive rows of zada_findzip_device: the extracted bytes (uz_slot of every cap) within `limit`, or a single row
 inline void fz_groups(const zada_unzip_entry *ent, int count, uint64_t limit, std::vector<int> &ends) { uz_groups(ent, count, limit, ends); }
 // the argument checks of zada_findzip_device: uz_check's without the output ranges, row by row
-inline int fz_check(const zada_unzip_entry *ent, int count, uint64_t archive_len, int have_keys, int *bad, int *why) {
+inline int fz_check(const zada_unzip_entry *ent, int count, uint64_t archive_len, int have_keys, int *bad, int *why, int legacy = 0) {
   *bad = -1; *why = UZ_W_NONE;
   for (int i = 0; i < count; i++) {
     zada_unzip_entry e = ent[i];
     e.flags &= 3u;
     int k = -1, w = 0;
-    const int rc = uz_check(&e, 1, archive_len, 0, 0, have_keys, &k, &w);
+    const int rc = uz_check(&e, 1, archive_len, 0, 0, have_keys, &k, &w, legacy);
     if (rc) { *bad = i; *why = w; return rc; }
   }
   return ZADA_OK;

@@ -271,12 +271,14 @@ struct Ctx {
   int knob_infp_min_kib = 0;                         // "inflate_par_min_kib": zada_unzip_device sends Deflate entries of at least this many KiB of stream through the parallel path (0 = off)
   void *bzd = nullptr;                               // BZip2 reader state (zada_bunzip2.hip), made on first use
   void *ulz = nullptr;                               // LZMA reader state (zada_unlzma.hip), made on first use
+  void *ulg = nullptr;                               // Shrink / Reduce / Implode reader state (zada_unlegacy.hip), made on first use
   void *uz = nullptr;                                // archive reader state (zada_unzip.hip), made on first use
   void *zw = nullptr;                                // archive writer state (zada_zip.hip), made on first use
   void *rz = nullptr;                                // Comp_Zip state (zada_rezip.hip), made on first use
   void *fz = nullptr;                                // Find_Zip state (zada_find.hip), made on first use
   void *lg = nullptr;                                // Shrink / Reduce state (zada_shrink.hip, zada_reduce.hip), made on first use
   int knob_reduce_group_mib = 4096;                  // "reduce_group_mib": MiB of HBM the work arrays of one launch group of zada_reduce_batch may take (328 KiB + raw bytes per entry)
+  int knob_unzip_legacy = 0;                         // "unzip_legacy": 1 = zada_unzip_device, zada_compzip_device and zada_findzip_device know methods 1 .. 6 (Shrink, Reduce, Implode: zada_unlegacy.hip)
   int knob_unzip_piece = 14;                         // "unzip_piece" (test knob): log2 of the bytes of one piece of a stored entry (8 .. 14)
   void *lz_tab = nullptr; size_t cap_lz_tab = 0;     // LZMA (zada_lzma.hip): job table + results
   void *lz_save = nullptr; size_t cap_lz_save = 0;   // ... the coder's state between the launches of one stream
@@ -359,6 +361,7 @@ int inflate_par_try(Ctx *c, int format, const void *d_in, uint64_t n_in, void *d
 void inflate_par_record(Ctx *c, ::zada_inflate_par_info *get, const ::zada_inflate_par_info *set);   // the record zada_inflate_par_last gives: read and / or replaced
 void bunzip2_destroy(Ctx *c);                       // the BZip2 reader (zada_bunzip2.hip)
 void unlzma_destroy(Ctx *c);                        // the LZMA reader (zada_unlzma.hip)
+void unlegacy_destroy(Ctx *c);                      // the Shrink / Reduce / Implode reader (zada_unlegacy.hip)
 void unzip_destroy(Ctx *c);                         // the archive reader (zada_unzip.hip)
 void zip_destroy(Ctx *c);                           // the archive writer (zada_zip.hip)
 void rezip_destroy(Ctx *c);                         // Comp_Zip (zada_rezip.hip)
@@ -375,6 +378,8 @@ int inflate_run_jobs(Ctx *c, uint32_t E, const ReaderJob *jobs, ReaderRes *res, 
 int bunzip2_run_jobs(Ctx *c, uint32_t E, const ReaderJob *jobs, ReaderRes *res, bool *described);
 int unlzma_run_jobs(Ctx *c, uint32_t E, const ReaderJob *jobs, ReaderRes *res, bool *described);
 uint64_t unlzma_hbm_elems(const uint8_t *h9, uint64_t n_in);   // ReaderJob::lit_elems of an LZMA entry, from the first nine bytes of its payload
+// (ulg_run, zada_unlegacy.hip: format is the method 1 .. 6, eos holds the general-purpose bits 1 and 2 of an Implode entry)
+int unlegacy_run_jobs(Ctx *c, uint32_t E, const ReaderJob *jobs, ReaderRes *res, bool *described);
 // Trained_Compression's decoder (k_unlzma_trained, zada_unlzma.hip) for zada_trained.hip: E streams (5-byte header, no size field, ending on their
 // marker), one wave each, on the context's stream; nothing is waited for.  d_start: the snapshot every stream goes on from (its input is then what
 // follows the snapshot's input position, its output slot holds the snapshot's text), null: each stream starts at its own header.  d_stop: ONE stream

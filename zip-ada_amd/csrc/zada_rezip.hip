@@ -214,10 +214,10 @@ int zada_compzip_device(zada_ctx *z, const void *d_archive_a, uint64_t len_a, co
   if (count && (!a || !b || !res)) { c->err = "zada_compzip_device: null argument"; return ZADA_E_INVALID; }
   if ((len_a && !d_archive_a) || (len_b && !d_archive_b)) { c->err = "zada_compzip_device: null archive"; return ZADA_E_INVALID; }
   int bad = -1, side = 0, why = 0;
-  int rc = cz_check(a, b, count, len_a, len_b, keys0 != nullptr, &bad, &side, &why);
+  int rc = cz_check(a, b, count, len_a, len_b, keys0 != nullptr, &bad, &side, &why, c->knob_unzip_legacy);
   if (rc) {
     char buf[200];
-    snprintf(buf, sizeof buf, "zada_compzip_device: pair %d, archive %d: %s", bad, side, uz_why_text(why));
+    snprintf(buf, sizeof buf, "zada_compzip_device: pair %d, archive %d: %s", bad, side, uz_why_text(why, c->knob_unzip_legacy));
     c->err = buf;
     return rc;
   }
@@ -254,7 +254,7 @@ int zada_compzip_device(zada_ctx *z, const void *d_archive_a, uint64_t len_a, co
       if (cz_absent(b[i])) { R.verdict = ZADA_CZ_MISSING; continue; }
       zada_unzip_entry x = a[i], y = b[i];
       x.out_off = y.out_off = bytes;
-      x.flags &= 3u; y.flags &= 3u;
+      x.flags &= x.method == 6 ? 7u : 3u; y.flags &= y.method == 6 ? 7u : 3u;   // (an Implode row keeps its general-purpose bit 2)
       bytes += cz_slot(a[i], b[i]);
       ea.push_back(x); eb.push_back(y); idx.push_back(i);
     }

@@ -38,7 +38,8 @@ inline bool cz_absent(const zada_unzip_entry &e) { return (e.flags & ZADA_CZ_ABS
 
 // The argument checks of zada_compzip_device: uz_check's on every row of archive 1, then on every present row of archive 2 (no output ranges: the
 // outputs are workspace).  *side: 1 or 2.  Returns ZADA_OK, ZADA_E_INVALID or ZADA_E_TOO_LARGE.
-inline int cz_check(const zada_unzip_entry *a, const zada_unzip_entry *b, int count, uint64_t len_a, uint64_t len_b, int have_keys, int *bad, int *side, int *why) {
+inline int cz_check(const zada_unzip_entry *a, const zada_unzip_entry *b, int count, uint64_t len_a, uint64_t len_b, int have_keys, int *bad, int *side, int *why,
+                    int legacy = 0) {
   *bad = -1; *side = 0; *why = UZ_W_NONE;
   for (int s = 1; s <= 2; s++)
     for (int i = 0; i < count; i++) {
@@ -46,7 +47,7 @@ inline int cz_check(const zada_unzip_entry *a, const zada_unzip_entry *b, int co
       zada_unzip_entry e = s == 1 ? a[i] : b[i];
       e.flags &= 3u;
       int k = -1, w = 0;
-      const int rc = uz_check(&e, 1, s == 1 ? len_a : len_b, 0, 0, have_keys, &k, &w);
+      const int rc = uz_check(&e, 1, s == 1 ? len_a : len_b, 0, 0, have_keys, &k, &w, legacy);
       if (rc) { *bad = i; *side = s; *why = w; return rc; }
     }
   return ZADA_OK;

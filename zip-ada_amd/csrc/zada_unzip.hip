@@ -438,21 +438,22 @@ static int uz_group(Ctx *c, UzState *S, const uint8_t *archive, const zada_unzip
     }
     inflate_par_record(c, nullptr, &sum);
   }
-  for (int pass = 0; pass < 3; pass++) {
+  for (int pass = 0; pass < 4; pass++) {
     rj.clear(); rr.clear(); rk.clear();
     for (uint32_t k = 0; k < n; k++) {
       const zada_unzip_entry &e = ent[idx[k]];
       const bool lz = e.method == 14;
       if (done[k]) continue;
-      if (!(pass == 0 ? (e.method == 8 || e.method == 9) : pass == 1 ? e.method == 12 : lz)) continue;
+      if (!(pass == 0 ? (e.method == 8 || e.method == 9) : pass == 1 ? e.method == 12 : pass == 2 ? lz : uz_method_legacy(e.method))) continue;
       ReaderJob J{src[k], out[k], uz_payload(e), e.cap, (int32_t)e.method, (e.flags & 2u) ? 1u : 0u, 0, idx[k], 0};
+      if (e.method == 6) J.eos = e.flags & 6u;             // (an Implode row: the entry's general-purpose bits 1 and 2)
       if (lz) J.lit_elems = unlzma_hbm_elems(h16.data() + (size_t)gslot[k] * 16, J.n_in);
       rj.push_back(J); rr.push_back(ReaderRes{0, res[idx[k]].crc, 0, 0}); rk.push_back(k);
     }
     const uint32_t E = (uint32_t)rj.size();
     if (!E) continue;
     const int rc = pass == 0 ? inflate_run_jobs(c, E, rj.data(), rr.data(), described) : pass == 1 ? bunzip2_run_jobs(c, E, rj.data(), rr.data(), described)
-                                                                                                     : unlzma_run_jobs(c, E, rj.data(), rr.data(), described);
+                 : pass == 2 ? unlzma_run_jobs(c, E, rj.data(), rr.data(), described) : unlegacy_run_jobs(c, E, rj.data(), rr.data(), described);
     if (rc) return rc;
     for (uint32_t j = 0; j < E; j++) {
       const uint32_t k = rk[j];
@@ -496,10 +497,10 @@ int zada_unzip_device(zada_ctx *z, const void *d_archive, uint64_t archive_len, 
   if (count && (!ent || !res)) { c->err = "zada_unzip_device: null argument"; return ZADA_E_INVALID; }
   if (archive_len && !d_archive) { c->err = "zada_unzip_device: null archive"; return ZADA_E_INVALID; }
   int bad = -1, why = 0;
-  int rc = uz_check(ent, count, archive_len, out_bytes, d_out != nullptr, keys0 != nullptr, &bad, &why);
+  int rc = uz_check(ent, count, archive_len, out_bytes, d_out != nullptr, keys0 != nullptr, &bad, &why, c->knob_unzip_legacy);
   if (rc) {
     char buf[200];
-    snprintf(buf, sizeof buf, "zada_unzip_device: entry %d: %s", bad, uz_why_text(why));
+    snprintf(buf, sizeof buf, "zada_unzip_device: entry %d: %s", bad, uz_why_text(why, c->knob_unzip_legacy));
     c->err = buf;
     return rc;
   }

@@ -14,9 +14,11 @@ constexpr uint64_t UZ_OUT_ALIGN = 256;                 // test-only form: every 
 
 // what uz_check found wrong with entry *bad
 enum UzWhy { UZ_W_NONE = 0, UZ_W_METHOD, UZ_W_TOO_LARGE, UZ_W_IN_RANGE, UZ_W_OUT_RANGE, UZ_W_NO_KEYS, UZ_W_OVERLAP };
-inline const char *uz_why_text(int why) {
+// legacy: the knob "unzip_legacy" is set, so that methods 1 .. 6 (Shrink, Reduce_1 .. _4, Implode) are known too
+inline const char *uz_why_text(int why, int legacy = 0) {
   switch (why) {
-    case UZ_W_METHOD: return "unknown method (0 Store, 8 Deflate, 9 Deflate64, 12 BZip2, 14 LZMA)";
+    case UZ_W_METHOD: return legacy ? "unknown method (0 Store, 1 Shrink, 2 .. 5 Reduce, 6 Implode, 8 Deflate, 9 Deflate64, 12 BZip2, 14 LZMA)"
+                                    : "unknown method (0 Store, 8 Deflate, 9 Deflate64, 12 BZip2, 14 LZMA)";
     case UZ_W_TOO_LARGE: return "a stream or an output of 1 TiB or more";
     case UZ_W_IN_RANGE: return "its data lie beyond the archive";
     case UZ_W_OUT_RANGE: return "its output range lies beyond the output buffer";
@@ -25,20 +27,22 @@ inline const char *uz_why_text(int why) {
     default: return "";
   }
 }
-inline bool uz_method_known(uint16_t m) { return m == 0 || m == 8 || m == 9 || m == 12 || m == 14; }
+inline bool uz_method_legacy(uint16_t m) { return m >= 1 && m <= 6; }
+inline bool uz_method_known(uint16_t m, int legacy = 0) { return m == 0 || m == 8 || m == 9 || m == 12 || m == 14 || (legacy && uz_method_legacy(m)); }
 inline bool uz_encrypted(const zada_unzip_entry &e) { return (e.flags & 1u) != 0; }
 // bytes of the entry's data behind the encryption header (an encrypted entry shorter than its header: 0, and ZADA_E_DATA)
 inline uint64_t uz_payload(const zada_unzip_entry &e) { return uz_encrypted(e) ? (e.n_in < 12 ? 0 : e.n_in - 12) : e.n_in; }
 
 // The argument checks, entry after entry in the order of the table: method, 1 TiB, input range, output range (have_out), keys; then the overlap of the
 // output ranges with cap > 0 (have_out), found by sorting them by their start: the entry whose range begins before the end of an earlier one is *bad.
-// Returns ZADA_OK, ZADA_E_INVALID or ZADA_E_TOO_LARGE.
-inline int uz_check(const zada_unzip_entry *ent, int count, uint64_t archive_len, uint64_t out_bytes, int have_out, int have_keys, int *bad, int *why) {
+// Returns ZADA_OK, ZADA_E_INVALID or ZADA_E_TOO_LARGE.  legacy: methods 1 .. 6 are known (the knob "unzip_legacy").
+inline int uz_check(const zada_unzip_entry *ent, int count, uint64_t archive_len, uint64_t out_bytes, int have_out, int have_keys, int *bad, int *why,
+                    int legacy = 0) {
   *bad = -1; *why = UZ_W_NONE;
   for (int i = 0; i < count; i++) {
     const zada_unzip_entry &e = ent[i];
     int w = UZ_W_NONE;
-    if (!uz_method_known(e.method)) w = UZ_W_METHOD;
+    if (!uz_method_known(e.method, legacy)) w = UZ_W_METHOD;
     else if (e.n_in >= UZ_MAX_BYTES || e.cap >= UZ_MAX_BYTES) w = UZ_W_TOO_LARGE;
     else if (e.in_off > archive_len || e.n_in > archive_len - e.in_off) w = UZ_W_IN_RANGE;
     else if (have_out && (e.out_off > out_bytes || e.cap > out_bytes - e.out_off)) w = UZ_W_OUT_RANGE;
