@@ -125,7 +125,7 @@ const char *zada_version(void);
  * needs more gets the full 1152 and the parse starts again), "inner_budget" (ZADA_INNER_BUDGET), "shard_kib" (ZADA_SHARD_KIB: KiB of
  * a stream the match finder takes at a time, multiple of 64), "span_mib" (MiB of a stream one pass takes; longer streams go span after
  * span, default 2048), "link_run" (segments of 32 KiB one workgroup of the link stage takes one after the other, making their cross links itself:
- * a power of two from 1 to 64, 0 = by size; anything else is ZADA_E_INVALID), "batch_mib" (MiB one batch of small entries may take), "unzip_piece" (test knob: log2 of the bytes of one piece of a stored entry in zada_unzip_device, 8 .. 14, default 14), "unzip_legacy" (1 = zada_unzip_device, zada_compzip_device and zada_findzip_device also know methods 1 .. 6, Shrink / Reduce / Implode; default 0; zada_rezip_device does not look at it),"bunzip_batch_mib" (MiB of HBM one group of zada_bunzip2_batch may take: streams, outputs, slots, tt arrays; 16 .. 262144, default 8192), "bz_batch_mib" / "bz_span_mib" / "bz_batch_melems" (BZip2
+ * a power of two from 1 to 64, 0 = by size; anything else is ZADA_E_INVALID), "batch_mib" (MiB one batch of small entries may take), "unzip_piece" (test knob: log2 of the bytes of one piece of a stored entry in zada_unzip_device, 8 .. 14, default 14), "unzip_legacy" (1 = zada_unzip_device, zada_compzip_device, zada_findzip_device and, for its source entries, zada_rezip_device also know methods 1 .. 6, Shrink / Reduce / Implode; default 0), "zip_legacy" (1 = zada_zip_device_ex takes Shrink_1 and Reduce_1 .. _4, zada_rezip_device the approaches shrink and reduce_4; default 0: every call answers as without the knob),"bunzip_batch_mib" (MiB of HBM one group of zada_bunzip2_batch may take: streams, outputs, slots, tt arrays; 16 .. 262144, default 8192), "bz_batch_mib" / "bz_span_mib" / "bz_batch_melems" (BZip2
  * batching; "bz_lists", "bz_list_rows", "bz_text_order", "bz_pipeline", "bz_pipe_prio", "bz_small_wg", "bz_split", "bz_tail_pct": scheduling of the BZip2 stages), "lzma_chunk" (positions of an LZMA stream one launch codes between two feedback calls; 0 = by level, -1 = one launch
  * per stream), "lzma_pool" (test knob: blocks of the LZMA_3 match sets' overflow pool to start with, 0 = by size; a pool that is too small is
  * counted and the match producer's walk runs again; for a stream whose producer works in segments the pool grows between the segments), "lzma_pool_fixed" (test knob: 1 = it
@@ -200,7 +200,8 @@ int zada_compress_data_hint(zada_ctx *ctx, int method, int content_hint, const u
  * and nothing is delivered.  A stream shorter than the input that does not fit cap is ZADA_E_INVALID ("output buffer too small").  An entry of 1 GiB -
  * 64 KiB or more is ZADA_E_TOO_LARGE.  method is ZADA_REDUCE_1 .. ZADA_REDUCE_4.  Output bytes are those of the CPU models (tests/legacy/), whose
  * stated forms restate the reference's encoders; parity with an Ada build is unpinned, as everywhere.
- * Still refused, by name: zada_zip_device, zada_zip_device_ex and zada_rezip_device take neither method, and the readers decode neither format. */
+ * In the device tools these methods are opt-in: with the knob "zip_legacy" = 1 zada_zip_device_ex writes them and zada_rezip_device tries Shrink_1
+ * and Reduce_4; without it both refuse them by name.  zada_zip_device refuses them whatever the knob says.  (Reading: zada_unlegacy*, "unzip_legacy".) */
 int zada_shrink(zada_ctx *ctx, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout);
 int zada_shrink_device(zada_ctx *ctx, const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout);
 int zada_shrink_batch(zada_ctx *ctx, int count, const uint8_t *const *in, const uint64_t *n, uint8_t *const *out, const uint64_t *cap,
@@ -498,12 +499,18 @@ typedef struct { int32_t rc; uint16_t zip_type; uint16_t pad; uint32_t crc; uint
 uint64_t zada_zip_bound(int count, const zada_zip_entry *ent, uint64_t archive_base);
 int zada_zip_device(zada_ctx *ctx, int method, int count, const zada_zip_entry *ent, void *d_archive, uint64_t cap, uint64_t archive_base,
                     uint64_t *archive_len, zada_zip_result *res);
-/* The writer with every method Zip.Create takes but Shrink and Reduce, and with a password.  zada_zip_device_ex is zada_zip_device -- the same
+/* The writer with every method Zip.Create takes -- Shrink and Reduce only with the knob "zip_legacy" -- and with a password.  zada_zip_device_ex is zada_zip_device -- the same
  * entries, results, checks and texts (under its own name), the same bytes for Store and the Deflate methods without a password -- and besides:
  *   method   : also BZip2_1 .. _3 (zip type 12), LZMA_0 .. LZMA_for_AU (zip type 14, the headers carry LZMA_EOS_Flag_Bit 0x0002) and
  *              Preselection_1 / _2: per entry zada_preselect (method, zada_guess_type_from_name (name), 1, n), the name being the bytes of the table
  *              (copied: they are not NUL-terminated there); res [i].zip_type tells the outcome.  Shrink_1, Reduce_1 .. 4 and anything out of range
- *              stay ZADA_E_INVALID with a text that names them.
+ *              stay ZADA_E_INVALID with a text that names them.  With the knob "zip_legacy" = 1 Shrink_1 (zip type 1) and Reduce_1 .. _4 (zip types
+ *              2 .. 5) are taken, for all entries, with or without a password; Preselection never chooses them.  Their groups follow
+ *              zada_shrink_batch / zada_reduce_batch: an entry takes twice its size rounded up to 64 bytes, the slots of a group stay within
+ *              "batch_mib" (at most 1 GiB), Reduce's work arrays within "reduce_group_mib"; the entries are gathered from their addresses and run
+ *              ONE launch sequence of that batch call.  One wave works on one entry (2.5 MB/s for Shrink_1, 0.18 MB/s for Reduce_4): a batch of
+ *              small entries fills the device, an entry of several megabytes is accepted and slow.  An entry of 1 GiB - 64 KiB or more is
+ *              ZADA_E_TOO_LARGE with its index, and nothing is written.
  *   crypt    : NULL, or the password of every entry (HOST memory; one byte per Character'Pos as for zada_crypt_init_keys) and random11 = count x 11
  *              bytes, the eleven random bytes of every entry's encryption header in the order of the table -- the library draws no random numbers, as
  *              with zada_compress_data_pw.  The headers carry Encryption_Flag_Bit 0x0001, the payload is the 12-byte encryption header (made on the
@@ -535,13 +542,18 @@ int zada_zip_device_ex(zada_ctx *ctx, int method, int count, const zada_zip_entr
  * source's zip type (0, 8, 9, 12, 14); flags, version, time the LOCAL header's bit flag, version needed and DOS time (kept in the new headers: the
  * flag and 0xFFF5, bit 1 set again when the winner ends on a marker); name, name_len the bytes of the new headers (HOST memory).
  * approaches: a bit per approach in the reference's order: 0 original (always taken as set), 1 Preselection_2, 2 Preselection_1, 3 Shrink_1, 4 Reduce_4,
- *   5 Deflate_3, 6 Deflate_R, 7 BZip2_3, 8 BZip2_2, 9 BZip2_1, 10 LZMA_3, 11 LZMA_2.  ZADA_RZ_DEFAULT is every approach built here.  Bits 3 and 4 are
- *   ZADA_E_INVALID by name: the device writer this call runs on does not take Shrink_1 and Reduce_4 (zada_shrink_batch / zada_reduce_batch encode them from
- *   host buffers) -- a divergence from `rezip -int`, which tries them on entries of at most
- *   6 000 and 9 000 bytes and may choose their stream there.
+ *   5 Deflate_3, 6 Deflate_R, 7 BZip2_3, 8 BZip2_2, 9 BZip2_1, 10 LZMA_3, 11 LZMA_2.  ZADA_RZ_DEFAULT is every approach but bits 3 and 4.  Those two are
+ *   ZADA_E_INVALID by name unless the knob "zip_legacy" is 1.  With it they are tried as `rezip -int` tries them: Shrink_1 on entries of at most
+ *   6 000 bytes, Reduce_4 on entries of at most 9 000 (rezip_lib.adb:819-832); a larger entry's size row says not tried.
  * formats: a bit per zip type the result may hold: 0 Store, 1 Deflate, 2 Deflate64, 3 BZip2, 4 LZMA (ZADA_RZ_ALL_FORMATS, _DEFLATE_OR_STORE,
  *   _FAST_DECOMPRESSION as rezip_lib.ads:46-54).  A single-method approach is considered when its format is in the set, the Preselections only with
  *   all formats; an original whose format is not in the set is forced out, even at a larger size (rezip_lib.adb:876-886).
+ *   The mask has five bits and cannot name Shrink, Reduce or Implode.  Such a format -- of the approaches shrink and reduce_4, of a source entry of
+ *   method 1 .. 6 -- counts as in the set exactly when the set is ZADA_RZ_ALL_FORMATS; that agrees with all three named sets of the reference.
+ *   Source entries of methods 1 .. 6 are taken with the knob "unzip_legacy" = 1 (the two knobs are independent); the text for an unknown source
+ *   method is then the reader's longer one.
+ *   Divergence, on purpose: the reference's mask 0xFFF5 drops general-purpose bit 1 of a kept Implode stream (its 8 KiB dictionary), so that its
+ *   own output no longer decodes.  Here a kept original of method 6 keeps bits 1 and 2 of its source; every other case follows the reference.
  * The choice is the considered approach with the smallest (size, rank); a stream not shorter than its input counts as Store of usize bytes
  * (Compress_Data's fallback).  Every distinct method of a group of entries (groups bounded by "batch_mib"; an entry above 4 MiB alone) runs ONE
  * zada_zip_device_ex launch sequence over exactly the entries that need it, in ascending method order, into a holding buffer of the context: at

@@ -23,10 +23,11 @@ LIB_PATH = os.environ.get("ZADA_LIB", os.path.join(_HERE, "libzada_hip.so"))   #
 
 class Method:
     """Compression_Method'Pos, zip-compress.ads:59-122.  Every method has an encoder (Encoder.shrink / reduce / deflate / bzip2 / lzma and their batch
-    calls, compress_data, ZipCreate); the Preselection methods pick one of the others per entry (preselect) and never Shrink or Reduce.  Still
-    refused for Shrink_1 and Reduce_1 .. _4, by name: the device writers (zip_device, zip_device_ex) and ReZip's approaches and sources.  Reading such
-    entries -- and Implode entries, which have no encoder here -- is opt-in: Encoder.unlegacy*, UnZip / CompZip / FindZip (encoder, legacy=True);
-    without the keyword they stay UnsupportedMethod."""
+    calls, compress_data, ZipCreate); the Preselection methods pick one of the others per entry (preselect) and never Shrink or Reduce.  Shrink_1
+    and Reduce_1 .. _4 in the device tools are opt-in: Encoder.zip_device_ex / ZipCreate.write_device_ex (..., legacy=True) write them, ReZip (encoder,
+    legacy=True) tries shrink and reduce_4 and reads such sources; without the keyword they are refused by name.  zip_device (Store and Deflate only)
+    refuses them always.  Reading such entries -- and Implode entries, which have no encoder here -- is opt-in as well: Encoder.unlegacy*,
+    UnZip / CompZip / FindZip (encoder, legacy=True); without the keyword they stay UnsupportedMethod."""
     Store = 0
     Shrink_1 = 1
     Reduce_1, Reduce_2, Reduce_3, Reduce_4 = 2, 3, 4, 5
@@ -125,7 +126,8 @@ class UserAbort(Exception):
 
 
 RZ_APPROACHES = ("original", "presel_2", "presel_1", "shrink", "reduce_4", "deflate_3", "deflate_r", "bzip2_3", "bzip2_2", "bzip2_1", "lzma_3", "lzma_2")
-RZ_DEFAULT = 0x0FE7                                  # zada.h ZADA_RZ_DEFAULT: every approach built here (not shrink, not reduce_4)
+RZ_DEFAULT = 0x0FE7                                  # zada.h ZADA_RZ_DEFAULT: every approach but shrink and reduce_4
+RZ_LEGACY = 0x0018                                   # shrink and reduce_4: taken with the knob "zip_legacy" (ReZip (encoder, legacy=True))
 RZ_ALL_FORMATS, RZ_DEFLATE_OR_STORE, RZ_FAST_DECOMPRESSION = 0x1F, 0x03, 0x17       # bits: Store, Deflate, Deflate64, BZip2, LZMA (rezip_lib.ads:46-54)
 RZ_NOT_TRIED = 0xFFFFFFFFFFFFFFFF
 
@@ -347,6 +349,7 @@ class Encoder:
     def set_knob(self, name, value):
         """Tuning / test knobs ("budget", "max_demand_rounds", "inner_budget", "shard_kib", "span_mib", "batch_mib", "bunzip_batch_mib", "inflate_par_chunk_kib", "inflate_par_repair_pct", "inflate_par_min_kib"); none changes a byte of output.
         "unzip_legacy" = 1: unzip_device, compzip_device and findzip_device know methods 1 .. 6 (UnZip / CompZip / FindZip set it around their calls).
+        "zip_legacy" = 1: zip_device_ex takes Shrink_1 and Reduce_1 .. _4, rezip_device the approaches shrink and reduce_4 (legacy=True sets it around the calls).
         "lzma_dict" is the reference's dictionary_size parameter for LZMA_3 (0 = the entry's size, what Zip.Compress.LZMA_E passes).
         "trained_fork" = 0: TrainedCompression works through every entry's whole stream (the same bytes; for measurements)."""
         if self.lib.zada_set_knob(self.ctx, name.encode(), int(value)) != 0:
@@ -1180,8 +1183,9 @@ class Encoder:
         ent = np.ascontiguousarray(entries, dtype=self.zip_dtypes()[0])
         return int(self.lib.zada_zip_bound_ex(len(ent), ent.ctypes.data if len(ent) else None, archive_base, 1 if encrypted else 0))
 
-    def zip_device_ex(self, entries, d_archive_ptr, cap, method, archive_base=0, password=None, headers=None):
-        """zada_zip_device_ex: zip_device with every method Zip.Create takes but Shrink and Reduce, and with a password (bytes, or str taken as Latin-1).
+    def zip_device_ex(self, entries, d_archive_ptr, cap, method, archive_base=0, password=None, headers=None, legacy=False):
+        """zada_zip_device_ex: zip_device with every method Zip.Create takes -- Shrink_1 and Reduce_1 .. _4 only with legacy=True, which sets the knob
+        "zip_legacy" around the call --, and with a password (bytes, or str taken as Latin-1).
         headers: eleven bytes per entry for the encryption headers -- one bytes object, or a list of them --, os.urandom by default.  An LZMA_3* entry
         the coder refuses raises ReferenceDefect."""
         import numpy as np
@@ -1200,8 +1204,14 @@ class Encoder:
                 raise ValueError("zip_device_ex: %d header bytes for %d entries" % (len(headers), len(ent)))
             keep = (ctypes.create_string_buffer(pw, len(pw)), ctypes.create_string_buffer(bytes(headers), max(len(headers), 1)))
             crypt = (ctypes.c_uint64 * 3)(ctypes.addressof(keep[0]), len(pw), ctypes.addressof(keep[1]))
-        rc = self.lib.zada_zip_device_ex(self.ctx, method, len(ent), ent.ctypes.data if len(ent) else None, d_archive_ptr, cap, archive_base,
-                                         ctypes.addressof(crypt) if crypt is not None else None, ctypes.byref(alen), res.ctypes.data if len(ent) else None)
+        if legacy:
+            self.set_knob("zip_legacy", 1)
+        try:
+            rc = self.lib.zada_zip_device_ex(self.ctx, method, len(ent), ent.ctypes.data if len(ent) else None, d_archive_ptr, cap, archive_base,
+                                             ctypes.addressof(crypt) if crypt is not None else None, ctypes.byref(alen), res.ctypes.data if len(ent) else None)
+        finally:
+            if legacy:
+                self.set_knob("zip_legacy", 0)
         if rc != 0:
             self._err(rc, "zada_zip_device_ex")
         return alen.value, res
@@ -1568,9 +1578,10 @@ class ZipCreate:
             self.entries.append(dict(name=nm, flag=flag | (0x0002 if zt == 14 else 0), zip_type=zt, time=int(tab["time"][k]),
                                      crc=int(r["crc"]), csize=int(r["csize"]), usize=usize, offset=int(r["offset"])))
 
-    def write_device_ex(self, names, tensors, file_time=None, unicode_name=True, password=None, _headers=None):
-        """write_device through zada_zip_device_ex: any method of this ZipCreate but Shrink and Reduce -- BZip2, LZMA, Preselection_1 / _2 by the
-        entries' names and sizes -- and, with a password (bytes, or str taken as Latin-1), encrypted entries; _headers (test hook): eleven bytes per
+    def write_device_ex(self, names, tensors, file_time=None, unicode_name=True, password=None, _headers=None, legacy=False):
+        """write_device through zada_zip_device_ex: any method of this ZipCreate -- BZip2, LZMA, Preselection_1 / _2 by the entries' names and sizes;
+        Shrink_1 and Reduce_1 .. _4 only with legacy=True (one wave per entry: a batch of small entries fills the device, one large entry is slow) --
+        and, with a password (bytes, or str taken as Latin-1), encrypted entries; _headers (test hook): eleven bytes per
         entry.  The archive is the one add_streams + finish write for the same inputs; self.entries is what add_compressed would have recorded,
         flag bits included.  write_device's rules hold: contiguous torch.uint8 tensors on the encoder's device, empty ones allowed, only on a
         ZipCreate without entries.  Returns the archive as a view of a tensor of zada_zip_bound_ex bytes."""
@@ -1580,7 +1591,7 @@ class ZipCreate:
         cap = self.enc.zip_bound_ex(tab, self._bias, pw is not None)
         out = torch.empty(cap, dtype=torch.uint8, device=dev)
         torch.cuda.current_stream(dev).synchronize()
-        alen, res = self.enc.zip_device_ex(tab, out.data_ptr(), cap, self.method, self._bias, password=pw, headers=_headers)
+        alen, res = self.enc.zip_device_ex(tab, out.data_ptr(), cap, self.method, self._bias, password=pw, headers=_headers, legacy=legacy)
         self._device_entries(tab, nms, res, (0x0800 if unicode_name else 0) | (0x0001 if pw else 0))
         return out[:alen]
 
@@ -2088,18 +2099,23 @@ class CompZip:
 class ReZip:
     """ReZip (tools/rezip_lib.adb, `rezip -int`) on an archive that lies in device memory: every entry is extracted and compressed on the device with
     each considered approach, and the new archive keeps per entry the smallest stream, the source's own where nothing beats it (zada_rezip_device).
-    Divergences from the reference: Shrink_1 and Reduce_4, which it tries on entries of at most 6 000 and 9 000 bytes, are not among the approaches here (they
-    are refused by name: the device writer under ReZip does not take them, though Encoder.shrink_batch / reduce_batch encode them); an LZMA_3 entry the coder refuses loses that approach instead of getting a stream that does not decode; more than 65 534
+    legacy=True: the approaches shrink and reduce_4, which the reference tries on entries of at most 6 000 and 9 000 bytes, are taken, approaches=None
+    then means all twelve, and source entries of methods 1 .. 6 (Shrink, Reduce, Implode) are read (the knobs "zip_legacy" and "unzip_legacy" are set
+    around the call).  The C format mask cannot name the formats of these methods: they count as in the format set exactly when the set is "all".
+    Without legacy=True the two approaches and such sources are refused by name.
+    Divergences from the reference: an LZMA_3 entry the coder refuses loses that approach instead of getting a stream that does not decode; more than 65 534
     kept entries are refused; the headers carry the directory's CRC-32; with lower=True two names that differ only in case are refused as duplicates,
-    where the reference writes both."""
+    where the reference writes both; a kept Implode stream keeps general-purpose bits 1 and 2 of its source, which the reference's mask 0xFFF5 would
+    cut to bit 2 alone (its own output then no longer decodes)."""
     _FORMATS = {"all": RZ_ALL_FORMATS, "deflate_or_store": RZ_DEFLATE_OR_STORE, "fast_decompression": RZ_FAST_DECOMPRESSION}
 
-    def __init__(self, encoder):
+    def __init__(self, encoder, legacy=False):
         self.enc = encoder
+        self.legacy = bool(legacy)
 
     def rezip_device(self, info, formats="all", approaches=None, touch=None, lower=False, delete_comment=False, report=False):
         """info: ZipInfo.load_device of a tensor on the encoder's device.  formats: "all", "deflate_or_store", "fast_decompression" or a bit set;
-        approaches: None (every built one), a bit mask, or names of RZ_APPROACHES; touch: one DOS time stamp for all entries; lower: names in lower
+        approaches: None (the default ten; with legacy=True all twelve), a bit mask, or names of RZ_APPROACHES; touch: one DOS time stamp for all entries; lower: names in lower
         case; delete_comment: the archive comment is left out.  Entries are written in Zip.Load's order (zip_load_order; a duplicate raises).
         Returns the new archive as a torch.uint8 tensor on the device, or (tensor, report) with report = {"entries": [(name, {approach: size},
         choice)], "totals": {approach: {"count": wins, "saved": bytes saved against original}}}."""
@@ -2112,7 +2128,7 @@ class ReZip:
             raise ZadaError("ReZip.rezip_device: the archive tensor lies on %s, not on the encoder's device" % t.device)
         fmt = self._FORMATS[formats] if isinstance(formats, str) else int(formats)
         if approaches is None:
-            mask = RZ_DEFAULT
+            mask = RZ_DEFAULT | (RZ_LEGACY if self.legacy else 0)
         elif isinstance(approaches, int):
             mask = approaches
         else:
@@ -2120,7 +2136,7 @@ class ReZip:
             for a in approaches:
                 mask |= 1 << RZ_APPROACHES.index(a)
         order = zip_load_order(info, "ReZip.rezip_device")
-        reader = UnZip(self.enc, bzip2=True, lzma=True)
+        reader = UnZip(self.enc, bzip2=True, lzma=True, legacy=self.legacy)
         for _, e in order:
             ex = reader._unsupported(e)
             if ex is not None:
@@ -2141,7 +2157,15 @@ class ReZip:
         cap = self.enc.rezip_bound(tab, len(comment))
         out = torch.empty(cap, dtype=torch.uint8, device=t.device)
         torch.cuda.current_stream(t.device).synchronize()
-        alen, res, sizes = self.enc.rezip_device(t.data_ptr(), t.numel(), tab, out.data_ptr(), cap, mask, fmt, 0, comment)
+        if self.legacy:
+            self.enc.set_knob("zip_legacy", 1)
+            self.enc.set_knob("unzip_legacy", 1)
+        try:
+            alen, res, sizes = self.enc.rezip_device(t.data_ptr(), t.numel(), tab, out.data_ptr(), cap, mask, fmt, 0, comment)
+        finally:
+            if self.legacy:
+                self.enc.set_knob("zip_legacy", 0)
+                self.enc.set_knob("unzip_legacy", 0)
         if not report:
             return out[:alen]
         rep = {"entries": [], "totals": {a: {"count": 0, "saved": 0} for a in RZ_APPROACHES}}

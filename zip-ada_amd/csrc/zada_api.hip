@@ -1138,6 +1138,7 @@ int zada_set_knob(zada_ctx *z, const char *name, int value) {
   else if (!strcmp(name, "bz_small_wg")) { if (value < 0 || value > 1) return ZADA_E_INVALID; z->c.knob_bz_small_wg = value; }
   else if (!strcmp(name, "bz_lists")) { if (value < -1) return ZADA_E_INVALID; z->c.knob_bz_lists = value; }
   else if (!strcmp(name, "unzip_legacy")) { if (value < 0 || value > 1) return ZADA_E_INVALID; z->c.knob_unzip_legacy = value; }
+  else if (!strcmp(name, "zip_legacy")) { if (value < 0 || value > 1) return ZADA_E_INVALID; z->c.knob_zip_legacy = value; }
   else if (!strcmp(name, "batch_mib")) { if (value < 1 || value > 1024) return ZADA_E_INVALID; z->c.knob_batch_mib = value; }
   else if (!strcmp(name, "inflate_par_chunk_kib")) { if (value < 4 || value > 65536) return ZADA_E_INVALID; z->c.knob_infp_chunk_kib = value; }
   else if (!strcmp(name, "inflate_par_repair_pct")) { if (value < 0 || value > 100) return ZADA_E_INVALID; z->c.knob_infp_repair_pct = value; }
@@ -1833,39 +1834,68 @@ int zada_lzma_batch(zada_ctx *z, int method, int count, const uint8_t *const *in
 // delivered, so a slot holds the entry's size), k_batch_crc's tables behind those.
 // --------------------------------------------------------------------------------------------
 static bool is_legacy_method(int method) { return method >= ZADA_SHRINK_1 && method <= ZADA_REDUCE_4; }
-constexpr uint64_t LEGACY_ENTRY_MAX = (1ull << 30) - 65536;
+}  // extern "C"
+namespace zada {
+// A launch group cut into layout and launch, as a Deflate, BZip2 or LZMA batch is: the layout books the buffers and says where entry e's slot lies
+// (d_in + start [e]); the caller fills the slots on the context's stream -- the host-pointer calls with one copy from the host, zada_zip_device_ex
+// with k_zw_pack --; the launch leaves entry e's stream, bytes [e] long (whatever of it fits the slot of cap [e] bytes), at d_out + off [e] in device
+// memory, its CRC register in reg [e], and has synchronised the stream.
+int legacy_batch_layout(Ctx *c, uint32_t E, const uint64_t *n, const uint32_t *crc_in, DevBatch &D) {
+  D = DevBatch();
+  D.E = E; D.kind = 3;
+  D.start.resize(E); D.off.resize(E); D.bytes.resize(E); D.cap.resize(E); D.len.resize(E); D.reg.resize(E);
+  uint64_t total = 0, ototal = 0;
+  for (uint32_t e = 0; e < E; e++) {
+    D.start[e] = total; D.len[e] = (uint32_t)n[e]; D.off[e] = ototal; D.cap[e] = legacy_slot(n[e]); D.reg[e] = crc_in ? crc_in[e] : 0xFFFFFFFFu;
+    total += legacy_slot(n[e]); ototal += legacy_slot(n[e]);
+  }
+  D.total = total; D.ototal = ototal;
+  if (total + ototal >= (1ull << 32)) return ZADA_E_TOO_LARGE;
+  const int rc = ensure_rin(c, total + ototal + 16ull * (E + 1) + 64);
+  if (rc) return rc;
+  D.d_in = c->ws.rin_own; D.d_out = D.d_in + total;
+  return 0;
+}
+int legacy_batch_launch(Ctx *c, int method, DevBatch &D) {
+  hipStream_t st = c->stream;
+  const uint32_t E = D.E;
+  std::vector<LegacyJob> jobs(E);
+  std::vector<uint32_t> tab(3 * (size_t)E);
+  for (uint32_t e = 0; e < E; e++) {
+    jobs[e].in_off = (uint32_t)D.start[e]; jobs[e].n = D.len[e]; jobs[e].out_off = (uint32_t)D.off[e]; jobs[e].cap = (uint32_t)D.cap[e];
+    tab[e] = (uint32_t)D.start[e]; tab[E + e] = D.len[e]; tab[2 * (size_t)E + e] = D.reg[e];
+  }
+  uint32_t *d_tab = (uint32_t *)(D.d_out + D.ototal);
+  hipMemcpyAsync(d_tab, tab.data(), 12ull * E, hipMemcpyHostToDevice, st);
+  hipLaunchKernelGGL(k_batch_crc, dim3(E), dim3(64), 0, st, E, D.d_in, d_tab, d_tab + E, d_tab + 2 * E);
+  hipMemcpyAsync(D.reg.data(), d_tab + 2 * E, 4ull * E, hipMemcpyDeviceToHost, st);
+  c->tmark("k_batch_crc");
+  return method == ZADA_SHRINK_1 ? shrink_encode_group(c, E, D.d_in, jobs.data(), D.d_out, D.bytes.data())
+                                 : reduce_encode_group(c, method - ZADA_REDUCE_1 + 1, E, D.d_in, jobs.data(), D.d_out, D.ototal, D.bytes.data());
+}
+}  // namespace zada
+extern "C" {
 // entries idx [0 .. E) of the caller's arrays through one launch group.  device: E = 1, and in [0] / out [0] are device addresses.
 static int legacy_group(Ctx *c, int method, const int *idx, uint32_t E, const uint8_t *const *in, const uint64_t *n, uint8_t *const *out, bool device,
                         const uint64_t *cap, uint64_t *out_len, uint32_t *crc, int *rc_out) {
   hipStream_t st = c->stream;
-  std::vector<LegacyJob> jobs(E);
-  std::vector<uint32_t> tab(3 * (size_t)E);
-  uint64_t total = 0, ototal = 0;
-  for (uint32_t e = 0; e < E; e++) {
-    const uint64_t ln = n[idx[e]];
-    jobs[e].in_off = (uint32_t)total; jobs[e].n = (uint32_t)ln; jobs[e].out_off = (uint32_t)ototal; jobs[e].cap = (uint32_t)legacy_slot(ln);
-    tab[e] = (uint32_t)total; tab[E + e] = (uint32_t)ln; tab[2 * (size_t)E + e] = crc ? crc[idx[e]] : 0xFFFFFFFFu;
-    total += legacy_slot(ln); ototal += legacy_slot(ln);
-  }
-  if (total + ototal >= (1ull << 32)) return ZADA_E_TOO_LARGE;
-  int rc = ensure_rin(c, total + ototal + 16ull * (E + 1) + 64);
+  std::vector<uint64_t> lens(E);
+  std::vector<uint32_t> regs(E, 0xFFFFFFFFu);
+  for (uint32_t e = 0; e < E; e++) { lens[e] = n[idx[e]]; if (crc) regs[e] = crc[idx[e]]; }
+  DevBatch D;
+  int rc = legacy_batch_layout(c, E, lens.data(), regs.data(), D);
+  const uint64_t total = D.total;
   if (!rc && !device) rc = grow_pinned((void **)&c->bstage, &c->cap_bstage, total + 64);
   if (rc) return rc;
-  uint8_t *d_in = c->ws.rin_own, *d_out = d_in + total;
-  uint32_t *d_tab = (uint32_t *)(d_out + ototal);
+  uint8_t *d_in = D.d_in, *d_out = D.d_out;
+  const std::vector<uint64_t> &bytes = D.bytes;
   if (device) { if (n[idx[0]]) hipMemcpyAsync(d_in, in[idx[0]], n[idx[0]], hipMemcpyDeviceToDevice, st); }
   else {
-    parallel_entries(E, total, [&](uint32_t e) { if (jobs[e].n) memcpy(c->bstage + jobs[e].in_off, in[idx[e]], jobs[e].n); });
+    parallel_entries(E, total, [&](uint32_t e) { if (D.len[e]) memcpy(c->bstage + D.start[e], in[idx[e]], D.len[e]); });
     hipMemcpyAsync(d_in, c->bstage, total, hipMemcpyHostToDevice, st);
   }
   c->tbegin(); c->tmark("legacy:begin");
-  hipMemcpyAsync(d_tab, tab.data(), 12ull * E, hipMemcpyHostToDevice, st);
-  hipLaunchKernelGGL(k_batch_crc, dim3(E), dim3(64), 0, st, E, d_in, d_tab, d_tab + E, d_tab + 2 * E);
-  hipMemcpyAsync(tab.data() + 2 * (size_t)E, d_tab + 2 * E, 4ull * E, hipMemcpyDeviceToHost, st);
-  c->tmark("k_batch_crc");
-  std::vector<uint64_t> bytes(E);
-  rc = method == ZADA_SHRINK_1 ? shrink_encode_group(c, E, d_in, jobs.data(), d_out, bytes.data())
-                               : reduce_encode_group(c, method - ZADA_REDUCE_1 + 1, E, d_in, jobs.data(), d_out, ototal, bytes.data());
+  rc = legacy_batch_launch(c, method, D);
   if (rc) { c->tend(); return rc; }
   // the verdicts, and the streams that are delivered: in one copy of the arena's used part for a large group, one by one otherwise
   bool bad = false;
@@ -1874,10 +1904,10 @@ static int legacy_group(Ctx *c, int method, const int *idx, uint32_t E, const ui
   for (uint32_t e = 0; e < E; e++) {
     const int i = idx[e];
     out_len[i] = bytes[e];
-    if (crc) crc[i] = tab[2 * (size_t)E + e];
+    if (crc) crc[i] = D.reg[e];
     rc_out[i] = bytes[e] >= n[i] ? ZADA_INEFFICIENT : ZADA_OK;                      // Write_Block, zip-compress.adb:468-490
     if (rc_out[i] == ZADA_OK && bytes[e] > cap[i]) { rc_out[i] = ZADA_E_INVALID; bad = true; }
-    if (rc_out[i] == ZADA_OK) { deliver++; used = jobs[e].out_off + bytes[e]; }
+    if (rc_out[i] == ZADA_OK) { deliver++; used = D.off[e] + bytes[e]; }
   }
   if (bad) c->err = ERR_OUTPUT_TOO_SMALL;
   if (device) {
@@ -1886,10 +1916,10 @@ static int legacy_group(Ctx *c, int method, const int *idx, uint32_t E, const ui
     if ((rc = grow_pinned((void **)&c->bstage, &c->cap_bstage, used + 64))) { c->tend(); return rc; }
     hipMemcpyAsync(c->bstage, d_out, used, hipMemcpyDeviceToHost, st);
     if (hip_check(c, hipStreamSynchronize(st), "legacy batch out")) { c->tend(); return ZADA_E_HIP; }
-    parallel_entries(E, used, [&](uint32_t e) { if (rc_out[idx[e]] == ZADA_OK) memcpy(out[idx[e]], c->bstage + jobs[e].out_off, bytes[e]); });
+    parallel_entries(E, used, [&](uint32_t e) { if (rc_out[idx[e]] == ZADA_OK) memcpy(out[idx[e]], c->bstage + D.off[e], bytes[e]); });
   } else {
     for (uint32_t e = 0; e < E; e++)
-      if (rc_out[idx[e]] == ZADA_OK) hipMemcpyAsync(out[idx[e]], d_out + jobs[e].out_off, bytes[e], hipMemcpyDeviceToHost, st);
+      if (rc_out[idx[e]] == ZADA_OK) hipMemcpyAsync(out[idx[e]], d_out + D.off[e], bytes[e], hipMemcpyDeviceToHost, st);
   }
   c->tmark("legacy:out");
   const int sync = hip_check(c, hipStreamSynchronize(st), "legacy out");

@@ -279,6 +279,7 @@ struct Ctx {
   void *lg = nullptr;                                // Shrink / Reduce state (zada_shrink.hip, zada_reduce.hip), made on first use
   int knob_reduce_group_mib = 4096;                  // "reduce_group_mib": MiB of HBM the work arrays of one launch group of zada_reduce_batch may take (328 KiB + raw bytes per entry)
   int knob_unzip_legacy = 0;                         // "unzip_legacy": 1 = zada_unzip_device, zada_compzip_device and zada_findzip_device know methods 1 .. 6 (Shrink, Reduce, Implode: zada_unlegacy.hip)
+  int knob_zip_legacy = 0;                           // "zip_legacy": 1 = zada_zip_device_ex takes Shrink_1 and Reduce_1 .. _4, zada_rezip_device the approaches shrink and reduce_4
   int knob_unzip_piece = 14;                         // "unzip_piece" (test knob): log2 of the bytes of one piece of a stored entry (8 .. 14)
   void *lz_tab = nullptr; size_t cap_lz_tab = 0;     // LZMA (zada_lzma.hip): job table + results
   void *lz_save = nullptr; size_t cap_lz_save = 0;   // ... the coder's state between the launches of one stream
@@ -510,6 +511,9 @@ int bzip2_batch_layout(Ctx *c, int method, uint32_t E, const uint64_t *n, const 
 int bzip2_batch_launch(Ctx *c, int method, DevBatch &D, uint8_t *h_out, uint64_t h_cap);     // h_out: the streams also go to the host (pinned), null: they stay
 int lzma_batch_layout(Ctx *c, int method, uint32_t E, const uint64_t *n, const uint32_t *crc_in, DevBatch &D);
 int lzma_batch_launch(Ctx *c, int method, DevBatch &D);
+// (Shrink_1 / Reduce_1 .. _4, kind 3: 64-byte slots in rin_own, the output slots behind them; no method in the layout: the slots are the same for all five)
+int legacy_batch_layout(Ctx *c, uint32_t E, const uint64_t *n, const uint32_t *crc_in, DevBatch &D);
+int legacy_batch_launch(Ctx *c, int method, DevBatch &D);
 bool lzma_batch_refused(Ctx *c, const DevBatch &D);                                          // sets the error text of the first refused entry
 int batch_geometry(Ctx *c, uint32_t E, const uint32_t *d_total_atoms);
 int entropy_analyze(Ctx *c);

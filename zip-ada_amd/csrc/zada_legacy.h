@@ -3,19 +3,12 @@
 #include <stdint.h>
 #include <vector>
 #include "zada_internal.h"
+#include "zada_legacy_plan.h"
 
 namespace zada {
 
 // one entry of a launch group: its bytes in the input arena, its slot in the output arena
 struct LegacyJob { uint32_t in_off, n, out_off, cap; };
-
-// A stream that is not shorter than its input is not delivered (Write_Block's rule, zip-compress.adb:468-490), so an entry's slot in the output
-// arena holds its n bytes, rounded up to 64: the kernels write nothing beyond the slot and go on counting.
-inline uint64_t legacy_slot(uint64_t n) { return n < 64 ? 64 : (n + 63) & ~63ull; }
-// Reduce: a literal 144 takes two raw bytes, a pair three or four for at least four input bytes
-inline uint64_t reduce_raw_bound(uint64_t n) { return 2 * n + 16; }
-// device memory Reduce takes per entry besides its slots: pair counts, follower positions, followers, Slen, raw bytes
-inline uint64_t reduce_footprint(uint64_t n) { return 256 * 256 * 4 + 256 * 256 + 256 * 32 + 256 + ((reduce_raw_bound(n) + 63) & ~63ull); }
 
 // E entries of d_in (jobs [e].in_off, .n) into their slots of d_out, one wave per entry; bytes [e] = the stream's length (a stream that is longer
 // than its slot of jobs [e].cap bytes is cut there, never written beyond).  The output arena need not be cleared.  Synchronises the context's stream.
@@ -25,6 +18,9 @@ int reduce_encode_group(Ctx *c, int factor, uint32_t E, const uint8_t *d_in, con
 // what the last reduce_encode_group left on the device, for the tests: what = 0 the raw bytes of `entry`, 1 its Slen (256), 2 its followers (256 x 32)
 uint64_t reduce_last_record(Ctx *c, int what, uint32_t entry, uint8_t *dst, uint64_t cap);
 void legacy_destroy(Ctx *c);
+// one stream from device memory into device memory behind the argument checks (zada_api.hip): ZADA_OK, ZADA_INEFFICIENT (nothing is written: the
+// stream does not beat its input), ZADA_E_TOO_LARGE, or ZADA_E_INVALID with ERR_OUTPUT_TOO_SMALL; `who` names the entry point in the other texts
+int legacy_device_one(::zada_ctx *z, int method, const void *d_in, uint64_t n, void *d_out, uint64_t cap, uint64_t *out_len, uint32_t *crc_inout, const char *who);
 
 // the device buffers of these two methods, made on first use (Ctx::lg)
 struct LegacyState {

@@ -339,7 +339,7 @@ int rz_group(RzRun &R, const std::vector<int> &idx) {
   uint64_t bytes = 0;
   for (int k = 0; k < n; k++) {
     const zada_rezip_entry &e = R.ent[idx[k]];
-    ue[k] = zada_unzip_entry{e.in_off, e.n_in, bytes, e.method == 0 ? e.n_in : e.usize, e.method, (uint8_t)(e.flags & 2u), 0, 0};
+    ue[k] = zada_unzip_entry{e.in_off, e.n_in, bytes, e.method == 0 ? e.n_in : e.usize, e.method, (uint8_t)(e.flags & (e.method == 6 ? 6u : 2u)), 0, 0};   // (Implode: bits 1 and 2 say how it is read)
     bytes += uz_slot(ue[k].cap);
   }
   int rc = rz_grow(c, R.S->arena_a, bytes + 16, "hipMalloc (rezip extraction arena)");
@@ -367,7 +367,7 @@ int rz_group(RzRun &R, const std::vector<int> &idx) {
     const zada_rezip_entry &e = R.ent[idx[k]];
     size[(size_t)k * RZ_NA] = e.n_in;
     best[k] = RzWinner{(uint64_t)(uintptr_t)R.src + e.in_off, e.n_in, e.method, e.method == 14 && (e.flags & 2u)};
-    rz_methods(R.considered, R.p2[idx[k]], R.p1[idx[k]], need[k]);
+    rz_methods(R.considered, R.p2[idx[k]], R.p1[idx[k]], need[k], e.usize);
     methods.insert(methods.end(), need[k].begin(), need[k].end());
   }
   std::sort(methods.begin(), methods.end());
@@ -413,7 +413,7 @@ int rz_group(RzRun &R, const std::vector<int> &idx) {
       if (refused[j]) { R.res[idx[k]].flags |= 2u; continue; }
       const uint64_t stream = (uint64_t)(uintptr_t)at + zr[j].offset + zw_local_len(tabs[m][j], zr[j].offset);
       for (int a = 1; a < RZ_NA; a++) {
-        if (!((R.considered >> a) & 1u) || rz_method_of(a, R.p2[idx[k]], R.p1[idx[k]]) != methods[m]) continue;
+        if (!((rz_considered_entry(R.considered, R.ent[idx[k]].usize) >> a) & 1u) || rz_method_of(a, R.p2[idx[k]], R.p1[idx[k]]) != methods[m]) continue;
         uint64_t *sz = &size[(size_t)k * RZ_NA];
         sz[a] = zr[j].csize;
         bool lead = true;                                             // smallest (size, rank) among the approaches other than original so far
@@ -429,11 +429,11 @@ int rz_group(RzRun &R, const std::vector<int> &idx) {
     const int i = idx[k];
     const zada_rezip_entry &e = R.ent[i];
     const uint64_t *sz = &size[(size_t)k * RZ_NA];
-    const int a = rz_choose(sz, rz_format_in(R.formats, e.method));
+    const int a = rz_choose(sz, rz_original_allowed(R.formats, e.method));
     if (a == RZ_ORIGINAL) best[k] = RzWinner{(uint64_t)(uintptr_t)R.src + e.in_off, e.n_in, e.method, e.method == 14 && (e.flags & 2u)};
     const RzWinner &W = best[k];
     const uint64_t dst = R.A.pos, hat = blob.size();
-    const uint32_t hl = rz_add(R.A, e, W.csize, W.zip_type, W.eos, blob);
+    const uint32_t hl = rz_add(R.A, e, W.csize, W.zip_type, W.eos, blob, a == RZ_ORIGINAL);
     if (R.A.pos > R.cap) { c->err = "zada_rezip_device: archive buffer too small"; return ZADA_E_INVALID; }
     zw_cut(hat, (uint64_t)(uintptr_t)R.archive + dst, hl, pieces);
     for (size_t q = pieces.size() - zw_piece_count(hl); q < pieces.size(); q++) pieces[q].pad = 1;
@@ -457,16 +457,16 @@ int zada_rezip_device(zada_ctx *z, const void *d_src, uint64_t src_len, int coun
   c->lz_stopped = false;
   if (!archive_len || (count && (!ent || !res)) || (comment_len && !comment)) { c->err = "zada_rezip_device: null argument"; return ZADA_E_INVALID; }
   if (!d_archive || (src_len && !d_src)) { c->err = "zada_rezip_device: null archive"; return ZADA_E_INVALID; }
-  if (approaches & RZ_UNBUILT) {
+  if ((approaches & RZ_UNBUILT) && !c->knob_zip_legacy) {
     c->err = std::string("zada_rezip_device: approach ") + ((approaches >> RZ_SHRINK) & 1u ? "shrink (Shrink_1)" : "reduce_4 (Reduce_4)") + " is not taken by the device writer";
     return ZADA_E_INVALID;
   }
   if (approaches >> RZ_NA || formats >> 5 || comment_len > 65535u) { c->err = "zada_rezip_device: approaches, formats or comment length out of range"; return ZADA_E_INVALID; }
   int bad = -1, why = 0;
-  int rc = rz_check(ent, count, (uint64_t)(uintptr_t)d_src, src_len, (uint64_t)(uintptr_t)d_archive, cap, &bad, &why);
+  int rc = rz_check(ent, count, (uint64_t)(uintptr_t)d_src, src_len, (uint64_t)(uintptr_t)d_archive, cap, &bad, &why, c->knob_unzip_legacy);
   if (rc) {
     char buf[240];
-    if (bad >= 0) snprintf(buf, sizeof buf, "zada_rezip_device: entry %d: %s", bad, rz_why_text(why));
+    if (bad >= 0) snprintf(buf, sizeof buf, "zada_rezip_device: entry %d: %s", bad, rz_why_text(why, c->knob_unzip_legacy));
     else snprintf(buf, sizeof buf, "zada_rezip_device: %s", rz_why_text(why));
     c->err = buf;
     return rc;
@@ -476,7 +476,7 @@ int zada_rezip_device(zada_ctx *z, const void *d_src, uint64_t src_len, int coun
   if (!S) { c->err = "rezip: no memory for the tables"; return ZADA_E_NOMEM; }
   RzRun R;
   R.z = z; R.c = c; R.S = S; R.src = (const uint8_t *)d_src; R.src_len = src_len; R.ent = ent; R.formats = formats;
-  R.considered = rz_considered(approaches | 1u, formats);
+  R.considered = rz_considered(approaches | 1u, formats, c->knob_zip_legacy);
   R.archive = (uint8_t *)d_archive; R.cap = cap; R.A.base = archive_base; R.res = res; R.sizes = sizes;
   R.p2.assign(count, 0); R.p1.assign(count, 0);
   for (int i = 0; i < count; i++) {

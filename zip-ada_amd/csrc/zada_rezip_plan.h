@@ -76,22 +76,28 @@ inline void cz_groups(const zada_unzip_entry *a, const zada_unzip_entry *b, int 
 inline uint64_t cz_piece_count(uint64_t n) { return (n + CZ_PIECE - 1) >> CZ_PIECE_LOG; }
 
 // ---- ReZip (tools/rezip_lib.adb) ----
-// The approaches in the reference's order (rezip_lib.adb:79-91); the rank is the bit in the mask.  Method 0: not a single method here (original,
-// the two Preselections, and Shrink_1 / Reduce_4, which the device writer does not take).
+// The approaches in the reference's order (rezip_lib.adb:79-91); the rank is the bit in the mask.  Method 0: original.  Shrink_1 and Reduce_4 are
+// taken only with the knob "zip_legacy" (RZ_UNBUILT: the approaches a call without it refuses).
 constexpr int RZ_NA = 12, RZ_ORIGINAL = 0, RZ_PRESEL_2 = 1, RZ_PRESEL_1 = 2, RZ_SHRINK = 3, RZ_REDUCE_4 = 4, RZ_LZMA_3 = 10;
-constexpr int RZ_METHOD[RZ_NA] = {0, ZADA_PRESELECTION_2, ZADA_PRESELECTION_1, 0, 0, ZADA_DEFLATE_3, ZADA_DEFLATE_R, ZADA_BZIP2_3, ZADA_BZIP2_2, ZADA_BZIP2_1, ZADA_LZMA_3, ZADA_LZMA_2};
+constexpr int RZ_METHOD[RZ_NA] = {0, ZADA_PRESELECTION_2, ZADA_PRESELECTION_1, ZADA_SHRINK_1, ZADA_REDUCE_4, ZADA_DEFLATE_3, ZADA_DEFLATE_R, ZADA_BZIP2_3, ZADA_BZIP2_2, ZADA_BZIP2_1,
+                                  ZADA_LZMA_3, ZADA_LZMA_2};
 constexpr uint32_t RZ_BUILT = 0x0FE7, RZ_UNBUILT = (1u << RZ_SHRINK) | (1u << RZ_REDUCE_4);
+constexpr uint64_t RZ_SHRINK_MAX = 6000, RZ_REDUCE_4_MAX = 9000;      // the largest entries these two are tried on (rezip_lib.adb:819-832)
 constexpr uint64_t RZ_NOT_TRIED = ~0ull;
 constexpr uint32_t RZ_MAX_ENTRIES = 65534;
 // the bit of a zip type in a format set (Zip.PKZip_Format: store, deflate, deflate_64, bzip2_fmt, lzma_fmt); -1: not one ReZip writes or reads here
 inline int rz_format_bit(uint16_t zt) { return zt == 0 ? 0 : zt == 8 ? 1 : zt == 9 ? 2 : zt == 12 ? 3 : zt == 14 ? 4 : -1; }
 inline bool rz_format_in(uint32_t formats, uint16_t zt) { const int b = rz_format_bit(zt); return b >= 0 && ((formats >> b) & 1u); }
 // consider_a_priori (rezip_lib.adb:1072-1089) over the built approaches of the mask: original always; a single method when its format is in the set;
-// the Preselections only with all formats.
-inline uint32_t rz_considered(uint32_t approaches, uint32_t formats) {
+// the Preselections only with all formats.  legacy (the knob "zip_legacy"): shrink and reduce_4 are single methods whose formats the five-bit mask
+// cannot name; such a format counts as in the set exactly when the set is all formats, which is so for every named set of the reference
+// (all_formats, deflate_or_store, fast_decompression).  Without it the two are never considered.
+inline bool rz_all_formats(uint32_t formats) { return (formats & ZADA_RZ_ALL_FORMATS) == ZADA_RZ_ALL_FORMATS; }
+inline uint32_t rz_considered(uint32_t approaches, uint32_t formats, int legacy = 0) {
   uint32_t c = 1u;
   for (int a = 1; a < RZ_NA; a++) {
-    if (!((approaches >> a) & 1u) || ((RZ_UNBUILT >> a) & 1u)) continue;
+    if (!((approaches >> a) & 1u)) continue;
+    if ((RZ_UNBUILT >> a) & 1u) { if (legacy && rz_all_formats(formats)) c |= 1u << a; continue; }
     const bool multi = a == RZ_PRESEL_1 || a == RZ_PRESEL_2;
     if (multi ? (formats & ZADA_RZ_ALL_FORMATS) == ZADA_RZ_ALL_FORMATS : rz_format_in(formats, zw_zip_type(RZ_METHOD[a]))) c |= 1u << a;
   }
@@ -109,11 +115,23 @@ inline int rz_choose(const uint64_t size[RZ_NA], bool original_allowed) {
   if (best < 0) return RZ_ORIGINAL;
   return original_allowed && size[RZ_ORIGINAL] <= size[best] ? RZ_ORIGINAL : best;
 }
+// The considered approaches of one entry of usize bytes: shrink only up to 6 000 bytes, reduce_4 only up to 9 000 (rezip_lib.adb:819-832); the
+// entry's size row says RZ_NOT_TRIED for the others.
+inline uint32_t rz_considered_entry(uint32_t considered, uint64_t usize) {
+  if (usize > RZ_SHRINK_MAX) considered &= ~(1u << RZ_SHRINK);
+  if (usize > RZ_REDUCE_4_MAX) considered &= ~(1u << RZ_REDUCE_4);
+  return considered;
+}
+// original's format is allowed (rezip_lib.adb:880-886): the source's zip type is in the format set; a Shrink, Reduce or Implode source (1 .. 6)
+// by the rule of rz_considered, only with all formats.
+inline bool rz_original_allowed(uint32_t formats, uint16_t method) { return method >= 1 && method <= 6 ? rz_all_formats(formats) : rz_format_in(formats, method); }
 // The method approach a runs on an entry: its single method, or what zada_preselect gave for the entry (p2, p1).
 inline int rz_method_of(int a, int p2, int p1) { return a == RZ_PRESEL_2 ? p2 : a == RZ_PRESEL_1 ? p1 : RZ_METHOD[a]; }
 // The distinct methods of an entry over its considered approaches, ascending; an (entry, method) pair that serves several approaches is run once.
-inline void rz_methods(uint32_t considered, int p2, int p1, std::vector<int> &out) {
+// usize: the entry's size, for the limits of shrink and reduce_4.
+inline void rz_methods(uint32_t considered, int p2, int p1, std::vector<int> &out, uint64_t usize = 0) {
   out.clear();
+  considered = rz_considered_entry(considered, usize);
   for (int a = 1; a < RZ_NA; a++) if ((considered >> a) & 1u) out.push_back(rz_method_of(a, p2, p1));
   std::sort(out.begin(), out.end());
   out.erase(std::unique(out.begin(), out.end()), out.end());
@@ -122,7 +140,9 @@ inline void rz_methods(uint32_t considered, int p2, int p1, std::vector<int> &ou
 inline bool rz_dropped(const zada_rezip_entry &e) { return e.name_len == 0 || e.name[e.name_len - 1] == '/' || e.name[e.name_len - 1] == '\\'; }
 
 enum RzWhy { RZ_W_NONE = 0, RZ_W_RANGE, RZ_W_METHOD, RZ_W_ENCRYPTED, RZ_W_DUPLICATE, RZ_W_TOO_LARGE, RZ_W_NAME, RZ_W_OVERLAP, RZ_W_COUNT };
-inline const char *rz_why_text(int why) {
+// legacy: the knob "unzip_legacy" is set, so that source methods 1 .. 6 are known (the reader's text then)
+inline const char *rz_why_text(int why, int legacy = 0) {
+  if (legacy && why == RZ_W_METHOD) return uz_why_text(UZ_W_METHOD, 1);
   switch (why) {
     case RZ_W_RANGE: return "its data lie beyond the source archive";
     case RZ_W_METHOD: return "unknown source method (0 Store, 8 Deflate, 9 Deflate64, 12 BZip2, 14 LZMA)";
@@ -136,7 +156,8 @@ inline const char *rz_why_text(int why) {
   }
 }
 // The argument checks, entry after entry; then the count of kept entries; the overlap of [d_archive, d_archive + cap) with the source is *bad = -1.
-inline int rz_check(const zada_rezip_entry *ent, int count, uint64_t d_src, uint64_t src_len, uint64_t d_archive, uint64_t cap, int *bad, int *why) {
+inline int rz_check(const zada_rezip_entry *ent, int count, uint64_t d_src, uint64_t src_len, uint64_t d_archive, uint64_t cap, int *bad, int *why,
+                    int legacy = 0) {
   *bad = -1; *why = RZ_W_NONE;
   if (src_len && cap && d_src < d_archive + cap && d_archive < d_src + src_len) { *why = RZ_W_OVERLAP; return ZADA_E_INVALID; }
   std::vector<int> order;
@@ -145,7 +166,7 @@ inline int rz_check(const zada_rezip_entry *ent, int count, uint64_t d_src, uint
     const zada_rezip_entry &e = ent[i];
     int w = RZ_W_NONE;
     if (e.name_len > 65535u || (e.name_len && !e.name)) w = RZ_W_NAME;
-    else if (!uz_method_known(e.method)) w = RZ_W_METHOD;
+    else if (!uz_method_known(e.method, legacy)) w = RZ_W_METHOD;
     else if (e.flags & 1u) w = RZ_W_ENCRYPTED;
     else if (e.n_in >= UZ_MAX_BYTES || e.usize >= UZ_MAX_BYTES) w = RZ_W_TOO_LARGE;
     else if (e.in_off > src_len || e.n_in > src_len - e.in_off) w = RZ_W_RANGE;
@@ -194,9 +215,13 @@ inline void rz_groups(const zada_rezip_entry *ent, int count, uint64_t limit, st
 struct RzDirEnt { uint64_t csize, usize, offset; uint32_t crc, time; uint16_t version, flag, zip_type; const uint8_t *name; uint32_t name_len; };
 struct RzArchive { uint64_t base = 0, pos = 0; std::vector<RzDirEnt> dir; };
 // The winner's local header appended to blob, the entry added to the directory; returns the header's length.  Kept from the source's local header:
-// version needed, time, and the bit flag and 0xFFF5 (no data descriptor, no EOS), bit 1 set again when the winner ends on a marker.
-inline uint32_t rz_add(RzArchive &A, const zada_rezip_entry &e, uint64_t csize, uint16_t zip_type, bool eos, std::vector<uint8_t> &blob) {
-  RzDirEnt d{csize, e.usize, A.base + A.pos, e.crc, e.time, e.version, (uint16_t)((e.flags & 0xFFF5u) | (eos ? 2u : 0u)), zip_type, e.name, e.name_len};
+// version needed, time, and the bit flag and 0xFFF5 (no data descriptor, no EOS; rezip_lib.adb:1002-1003), bit 1 set again when the winner ends on a
+// marker.  kept_original: the winner is the source's own stream.  For a kept Implode stream (method 6) bits 1 and 2 say how it is read -- an 8 KiB
+// dictionary, three trees -- and the mask would drop bit 1, so that the reference's own output no longer decodes: here the two bits of the source
+// stay.  A departure from the reference, on purpose.  A Shrink or Reduce winner has no flag bits of its own.
+inline uint32_t rz_add(RzArchive &A, const zada_rezip_entry &e, uint64_t csize, uint16_t zip_type, bool eos, std::vector<uint8_t> &blob, bool kept_original = false) {
+  const uint32_t implode = kept_original && e.method == 6 ? e.flags & 6u : 0u;
+  RzDirEnt d{csize, e.usize, A.base + A.pos, e.crc, e.time, e.version, (uint16_t)((e.flags & 0xFFF5u) | (eos ? 2u : 0u) | implode), zip_type, e.name, e.name_len};
   const bool z64 = zw_needs_zip64(csize, e.usize, d.offset);
   const size_t at = blob.size();
   zw_put(blob, 0x04034B50u, 4); zw_put(blob, d.version, 2); zw_put(blob, d.flag, 2); zw_put(blob, zip_type, 2); zw_put(blob, d.time, 4); zw_put(blob, d.crc, 4);

@@ -14,7 +14,8 @@
 // zada_zip_device_ex is the same walk with a method per entry -- BZip2 and LZMA batches on entries gathered by k_zw_pack
 // (bzip2_batch_layout / _launch, lzma_batch_layout / _launch, zada_api.hip), Preselection, one launch sequence per distinct method of a group with
 // the streams kept in a holding buffer until the group is placed once -- and with passwords: the payloads then go to their place through
-// k_zc_place (zada_crypt.hip), an out-of-place Encode.  Both entry points run the host code below: zada_zip_device is the case of one Store or Deflate
+// k_zc_place (zada_crypt.hip), an out-of-place Encode.  With the knob "zip_legacy" Shrink_1 and Reduce_1 .. _4 are methods as well: the
+// launch group of zada_shrink_batch / zada_reduce_batch (legacy_batch_layout / _launch, zada_api.hip) on entries gathered by k_zw_pack.  Both entry points run the host code below: zada_zip_device is the case of one Store or Deflate
 // method for all entries and no password, with its own texts and the launches, marks and bytes it always had.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -27,6 +28,7 @@
 #include "../../include/zada.h"
 #include "zada_internal.h"
 #include "zada_zip_plan.h"
+#include "zada_legacy.h"
 
 struct zada_ctx { zada::Ctx c; };
 
@@ -131,7 +133,7 @@ static uint64_t zw_up256(uint64_t v) { return (v + 255) & ~255ull; }
 //      with several methods, passwords (zada_zip_device: one method, Store or Deflate, and no password) ----
 struct ZxCall {
   const char *who = ""; bool ex = false;   // the entry point's name, for the error texts; it is zada_zip_device_ex
-  Ctx *c; ZwState *S; const zada_zip_entry *ent; zada_zip_result *res; uint8_t *archive; uint64_t cap; ZwArchive A;
+  zada_ctx *z = nullptr; Ctx *c; ZwState *S; const zada_zip_entry *ent; zada_zip_result *res; uint8_t *archive; uint64_t cap; ZwArchive A;
   std::vector<int> m;                  // the method of every entry (Preselection: zada_preselect on its name and size)
   bool enc = false;                    // a password: k0 are its keys, random11 eleven bytes per entry
   uint32_t k0[3] = {0, 0, 0}; const uint8_t *random11 = nullptr;
@@ -246,6 +248,16 @@ static int zx_method_run(ZxCall &Z, int method, const std::vector<int> &idx, int
     }
     return 0;
   }
+  if (zw_is_legacy(method)) {
+    // Shrink_1 / Reduce_1 .. _4: the launch group of zada_shrink_batch / zada_reduce_batch on gathered entries; a stream that does not fit its slot
+    // is cut there and stored by the rule of zw_group_place_ex (its length is not below the entry's)
+    DevBatch D;
+    if ((rc = legacy_batch_layout(c, E, lens.data(), nullptr, D))) return rc;
+    if ((rc = zx_pack(Z, idx, D.start.data(), D.d_in))) return rc;
+    if ((rc = legacy_batch_launch(c, method, D))) return rc;
+    for (uint32_t e = 0; e < E; e++) V[idx[e] - g0] = ZwVerdict{(uint64_t)(uintptr_t)D.d_out + D.off[e], D.bytes[e], D.reg[e], zw_zip_type(method), 0};
+    return 0;
+  }
   BatchLayout L;
   if ((rc = batch_layout(c, E, lens.data(), nullptr, L))) return rc;
   batch_segends_all(c, L);
@@ -321,7 +333,8 @@ static int zx_single(ZxCall &Z, int i) {
   uint64_t ol = 0;
   bool stored = true;                                    // (an empty entry: any stream is longer)
   if (e.n) {
-    const int rc = zw_is_bzip2(method) ? bzip2_device_one(c, method, e.d_data, e.n, Z.archive + payoff, Z.cap - payoff, &ol, &reg)
+    const int rc = zw_is_legacy(method) ? legacy_device_one(Z.z, method, e.d_data, e.n, Z.archive + payoff, Z.cap - payoff, &ol, &reg, Z.who)
+                 : zw_is_bzip2(method) ? bzip2_device_one(c, method, e.d_data, e.n, Z.archive + payoff, Z.cap - payoff, &ol, &reg)
                  : zw_is_lzma(method)  ? lzma_device_one(c, method, e.d_data, e.n, Z.archive + payoff, Z.cap - payoff, &ol, &reg)
                                        : deflate_device_one(c, method, e.d_data, e.n, Z.archive + payoff, Z.cap - payoff, &ol, &reg);
     if (rc == ZADA_E_INVALID && c->err == ERR_OUTPUT_TOO_SMALL) return zx_too_small(Z);    // (the stream alone is beyond the buffer; any other refusal keeps its text)
@@ -449,9 +462,9 @@ static int zx_open(zada_ctx *z, ZxCall &Z, bool ex, int method, int count, const
   c->lz_stopped = c->lz_run_stopped = false;                       // (as every entry point: zada_lzma_export_state)
   const char *who = ex ? "zada_zip_device_ex" : "zada_zip_device";
   char buf[320];
-  if (!(ex ? zw_method_ok_ex(method) : zw_method_ok(method))) {
+  if (!(ex ? zw_method_ok_ex(method, c->knob_zip_legacy) : zw_method_ok(method))) {
     snprintf(buf, sizeof buf, "%s: method %d (%s) is not one it takes: Store (0), %s", who, method, zw_method_name(method),
-             ex ? "Deflate_Fixed .. Preselection_2 (6 .. 35)" : "Deflate_Fixed .. Deflate_R (6 .. 11)");
+             !ex ? "Deflate_Fixed .. Deflate_R (6 .. 11)" : c->knob_zip_legacy ? "Shrink_1 .. Preselection_2 (1 .. 35)" : "Deflate_Fixed .. Preselection_2 (6 .. 35)");
     c->err = buf;
     return ZADA_E_INVALID;
   }
@@ -475,7 +488,7 @@ static int zx_open(zada_ctx *z, ZxCall &Z, bool ex, int method, int count, const
   if (hipSetDevice(c->device) != hipSuccess) return ZADA_E_HIP;
   if (!c->zw) c->zw = new (std::nothrow) ZwState();
   if (!c->zw) { c->err = "zip: no memory for the tables"; return ZADA_E_NOMEM; }
-  Z.who = who; Z.ex = ex; Z.c = c; Z.S = (ZwState *)c->zw; Z.ent = ent; Z.res = res; Z.archive = (uint8_t *)d_archive; Z.cap = cap;
+  Z.who = who; Z.ex = ex; Z.z = z; Z.c = c; Z.S = (ZwState *)c->zw; Z.ent = ent; Z.res = res; Z.archive = (uint8_t *)d_archive; Z.cap = cap;
   Z.A.base = archive_base;
   Z.m.assign((size_t)count, method);
   return 1;                                              // (go on)
@@ -515,7 +528,16 @@ int zada_zip_device_ex(zada_ctx *z, int method, int count, const zada_zip_entry 
   }
   std::vector<ZwGroup> groups;
   if (method == 0) zw_groups(ent, count, 0, 0, groups);
-  else {
+  else if (zw_is_legacy(method)) {
+    const int big = zw_legacy_too_large(ent, count);
+    if (big >= 0) {
+      char buf[160];
+      snprintf(buf, sizeof buf, "zada_zip_device_ex: entry %d: Shrink and Reduce take entries below 1 GiB - 64 KiB", big);
+      c->err = buf;
+      return ZADA_E_TOO_LARGE;
+    }
+    zw_groups_legacy(ent, count, method, (uint64_t)c->knob_batch_mib << 20, (uint64_t)c->knob_reduce_group_mib << 20, groups);
+  } else {
     const uint64_t mib = (uint64_t)c->knob_batch_mib << 20, limit = mib < (1ull << 30) ? mib : 1ull << 30;
     zw_groups_ex(ent, count, Z.m.data(), lit.data(), limit, (uint64_t)c->knob_bz_batch_mib << 20, (uint64_t)c->knob_lzma_lit_mib << 20, groups);
   }

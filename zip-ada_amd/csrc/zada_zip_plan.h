@@ -6,6 +6,7 @@
 #include <string.h>
 #include <vector>
 #include "../../include/zada.h"
+#include "zada_legacy_plan.h"
 
 namespace zada {
 
@@ -193,11 +194,14 @@ inline void zw_single_place(ZwArchive &A, const zada_zip_entry *ent, int i, bool
   if (res) res[i] = zada_zip_result{ZADA_OK, zt, 0, crc, csize, A.base + dst};
 }
 
-// ---- zada_zip_device_ex: every method but Shrink and Reduce, a method per entry (Preselection), passwords ----
-inline bool zw_method_ok_ex(int m) { return m == 0 || (m >= ZADA_DEFLATE_FIXED && m <= ZADA_PRESELECTION_2); }
+// ---- zada_zip_device_ex: every method, a method per entry (Preselection), passwords.  legacy: the knob "zip_legacy" is set, so that Shrink_1 and
+//      Reduce_1 .. _4 are taken too ----
+inline bool zw_is_legacy(int m) { return m >= ZADA_SHRINK_1 && m <= ZADA_REDUCE_4; }
+inline bool zw_method_ok_ex(int m, int legacy = 0) { return m == 0 || (m >= ZADA_DEFLATE_FIXED && m <= ZADA_PRESELECTION_2) || (legacy && zw_is_legacy(m)); }
 inline bool zw_is_bzip2(int m) { return m >= ZADA_BZIP2_1 && m <= ZADA_BZIP2_3; }
 inline bool zw_is_lzma(int m) { return m >= ZADA_LZMA_0 && m <= ZADA_LZMA_FOR_AU; }
-inline uint16_t zw_zip_type(int m) { return m == 0 ? 0 : m <= ZADA_DEFLATE_R ? 8 : zw_is_bzip2(m) ? 12 : 14; }      // of a single method
+// of a single method (Shrink_1: 1; Reduce_1 .. _4: 2 .. 5)
+inline uint16_t zw_zip_type(int m) { return m == 0 ? 0 : zw_is_legacy(m) ? (uint16_t)(m - ZADA_SHRINK_1 + 1) : m <= ZADA_DEFLATE_R ? 8 : zw_is_bzip2(m) ? 12 : 14; }
 // the longest entry that is one block whatever it holds (zada_bzip2_batch's rule)
 inline uint64_t zw_bz_one_block(int m) { return ((m == ZADA_BZIP2_1 ? 100000ull : m == ZADA_BZIP2_2 ? 400000ull : 900000ull) - 16) * 4 / 5; }
 // zw_check for zada_zip_device_ex: with a password an entry of 4 GiB - 11 .. 4 GiB - 1 bytes is refused as well.  The form of its local header is decided
@@ -240,6 +244,33 @@ inline void zw_groups_ex(const zada_zip_entry *ent, int count, const int *m, con
     if (ent[i].n > ZW_ENTRY_MAX || (b && ent[i].n > zw_bz_one_block(m[i]))) { flush(i); flush(i + 1); continue; }
     if (bytes + slot > limit || bz + b > bz_limit || lt + l > lit_limit) flush(i);
     bytes += slot; bz += b; lt += l;
+  }
+  flush(count);
+}
+// The first entry that Shrink and Reduce do not take (LEGACY_ENTRY_MAX bytes and more), or -1.
+inline int zw_legacy_too_large(const zada_zip_entry *ent, int count) {
+  for (int i = 0; i < count; i++) if (ent[i].n >= LEGACY_ENTRY_MAX) return i;
+  return -1;
+}
+// The groups of Shrink_1 or Reduce_1 .. _4 (the same method for all), by the rules of zada_shrink_batch / zada_reduce_batch: an entry takes
+// 2 * legacy_slot (n) bytes, its slots in the input and in the output arena, and a group's slots stay within `limit` bytes -- at most 1 GiB, so that
+// both arenas together stay below 2 ** 32 (LegacyJob's offsets have 32 bits) --; for Reduce the work arrays of a group, reduce_footprint (n) per
+// entry, stay within work_limit.  An entry above ZW_ENTRY_MAX ends the group before it and runs alone; a group of one takes the single-stream path.
+inline void zw_groups_legacy(const zada_zip_entry *ent, int count, int method, uint64_t limit, uint64_t work_limit, std::vector<ZwGroup> &out) {
+  out.clear();
+  if (limit > (1ull << 30)) limit = 1ull << 30;
+  const bool reduce = method != ZADA_SHRINK_1;
+  int g0 = 0;
+  uint64_t bytes = 0, work = 0;
+  auto flush = [&](int g1) {
+    if (g1 > g0) out.push_back(ZwGroup{g0, g1, g1 - g0 == 1 ? ZW_G_SINGLE : ZW_G_BATCH});
+    g0 = g1; bytes = work = 0;
+  };
+  for (int i = 0; i < count; i++) {
+    if (ent[i].n > ZW_ENTRY_MAX) { flush(i); flush(i + 1); continue; }
+    const uint64_t slot = 2 * legacy_slot(ent[i].n), w = reduce ? reduce_footprint(ent[i].n) : 0;
+    if (bytes + slot > limit || work + w > work_limit) flush(i);
+    bytes += slot; work += w;
   }
   flush(count);
 }
