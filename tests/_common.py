@@ -97,6 +97,17 @@ def hostcheck():
     return _cache["h"]
 
 
+def plan_library(folder, name, *headers):
+    """tests/<folder>/lib<name>.so, the host plan tests/<folder>/<name>.cpp around headers of zip-ada_amd/csrc: __graft_entry__.build() makes it; it is
+    made here when it is missing or older than its sources (a tests directory without build products), as _rezip.build_plan does."""
+    d = os.path.join(ROOT, "tests", folder)
+    p, src = os.path.join(d, "lib%s.so" % name), os.path.join(d, name + ".cpp")
+    deps = [src, os.path.join(ROOT, "include", "zada.h")] + [os.path.join(ROOT, "zip-ada_amd", "csrc", h) for h in headers]
+    if not os.path.exists(p) or os.path.getmtime(p) < max(os.path.getmtime(x) for x in deps):
+        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", p, src], check=True)
+    return p
+
+
 def booked_atoms(span, atoms_pct=50):
     """Atoms the entropy workspace of a context with no history holds once deflate_spans has booked it for spans of `span` bytes
     (zada_sizing.h through hostcheck: the product's own arithmetic)."""

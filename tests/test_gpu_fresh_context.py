@@ -6,10 +6,13 @@ orders, on one context made for that order), one context open at a time:
 
   * streams that go through one context span after span ("span_mib"), at the span sizes and guesses ("atoms_pct") where a span once asked
     for more atoms than the stream had booked (zada_sizing.h; tests/test_hostlogic.py checks the arithmetic exhaustively),
-  * a fixed list of calls to every kind of entry point, alone and in four orders on one context: the bytes never depend on what ran before,
+  * a fixed list of calls to every kind of entry point, alone and in four orders on one context: the bytes never depend on what ran before
+    (the readers, the archive tools, the legacy coders and the trained handles each with one larger call: _later_families; every ordered pair
+    of small calls is tests/test_gpu_call_orders.py's),
   * a stopped LZMA stream is exported right after its stop or not at all.
 
-Expected bytes are the CPU oracles' and models' (oracle_deflate, tests/rich, _bzip2, _lzmah, _crypt, zlib), computed once per module."""
+Expected bytes are the CPU oracles' and models' (oracle_deflate, tests/rich, _bzip2, _lzmah, _crypt, zlib; tests/_orders.py for the archives),
+computed once per module."""
 import zlib
 
 import numpy as np
@@ -245,7 +248,122 @@ def _calls(inputs, expected_streams):
     c = zlib.compressobj(9, zlib.DEFLATED, -15)
     p_inf = c.compress(d_inf) + c.flush()
     add("inflate(600 KB)", len(d_inf), lambda enc: enc.inflate(p_inf, len(d_inf)), (d_inf, len(p_inf), crc_reg(d_inf)))
+    _later_families(add, inputs, mix, text)
     return calls
+
+
+def _later_families(add, inputs, mix, text):
+    """One larger call per family that came after the list above, so that the four orders grow and shrink each family's own state objects (the readers',
+    the archive writer's, ReZip's, Find_Zip's, the legacy coders', the trained handles').  Expected values as in tests/_orders.py: the CPU models', the
+    oracle's, the standard library's."""
+    import bz2
+    import io
+    import zipfile
+
+    import _findzip
+    import _legacy as L
+    import _orders
+    import _trained
+    import _unlegacy as U
+    import _unlzma
+    from _inflate import zlib_raw
+    from test_gpu_unlegacy import _mixed_entries
+    za = product()
+
+    ents = _mixed_entries()
+    want = []
+    for m, f, s, cap, d in ents:
+        want.append((0, d, len(d), U.host_decode(m, f, s, cap)[3], crc_reg(d)))
+    add("unlegacy_batch(%d entries)" % len(ents), sum(len(e[4]) for e in ents),
+        lambda enc: enc.unlegacy_batch([e[2] for e in ents], [e[3] for e in ents], [e[0] for e in ents], [e[1] for e in ents]), want)
+
+    d_bu = mix[:1200000]
+    p_bu = bz2.compress(d_bu, 9)                               # level 9: blocks of 900 000 bytes, two of them
+    add("bunzip2(1.2 MB, two level-9 blocks)", len(d_bu), lambda enc: enc.bunzip2(p_bu, len(d_bu)) + (len(enc.bunzip2_last_records(blocks=True)),),
+        (d_bu, len(p_bu), crc_reg(d_bu), 2))
+    d_ul = mix[MIB:2 * MIB]
+    p_ul = _unlzma.raw_payload(d_ul, dict_size=MIB)
+    add("unlzma(1 MiB)", len(d_ul), lambda enc: enc.unlzma(p_ul, len(d_ul)), (d_ul, len(p_ul), crc_reg(d_ul)))
+    d_par = inputs["mix_10m"][:8 * MIB]
+    p_par = zlib_raw(d_par, 6, zlib.Z_DEFAULT_STRATEGY)
+    add("inflate_par(8 MiB)", len(d_par), lambda enc: enc.inflate_par(p_par, len(d_par)), (d_par, len(p_par), crc_reg(d_par)))
+
+    half = MIB // 2
+    z_entries = [("big/d%d.bin" % k, mix[k * half:(k + 1) * half]) for k in range(4)] + [("big/bz0.txt", text[:half]), ("big/bz1.bin", mix[2 * MIB:2 * MIB + half]),
+                                                                                         ("big/stored.bin", mix[3 * MIB:3 * MIB + half]), ("big/lz.bin", mix[3 * MIB + half:3 * MIB + half + 200000])]
+    z_methods = [zipfile.ZIP_DEFLATED] * 4 + [zipfile.ZIP_BZIP2] * 2 + [zipfile.ZIP_STORED, zipfile.ZIP_LZMA]
+    bio = io.BytesIO()
+    with zipfile.ZipFile(bio, "w") as zf:
+        for (nm, d), m in zip(z_entries, z_methods):
+            zf.writestr(zipfile.ZipInfo(nm, (2024, 5, 6, 7, 8, 10)), d, compress_type=m)
+    z_arc = bio.getvalue()
+    z_size = sum(len(d) for _, d in z_entries)
+
+    def extract(enc):
+        import torch
+        t = torch.from_numpy(np.frombuffer(z_arc, dtype=np.uint8).copy()).cuda()
+        got = za.UnZip(enc, bzip2=True, lzma=True).extract_device(za.ZipInfo.load_device(t))
+        return {nm: v.cpu().numpy().tobytes() for nm, v in got.items()}
+    add("extract_device(archive of 3.7 MiB)", z_size, extract, dict(z_entries))
+
+    w_entries = [("w/e%d.bin" % k, mix[k * half + 777:(k + 1) * half + 777]) for k in range(8)]          # (the last one ends with the corpus: 777 bytes shorter)
+
+    def write(enc):
+        import torch
+        tensors = [torch.from_numpy(np.frombuffer(d, dtype=np.uint8).copy()).cuda() for _, d in w_entries]
+        return za.ZipCreate(enc, 10).write_device_ex([nm for nm, _ in w_entries], tensors).cpu().numpy().tobytes()
+    add("write_device_ex(4 MiB, Deflate_3)", sum(len(d) for _, d in w_entries), write, _orders.cpu_archive(w_entries, 10))
+
+    # ReZip with {original, deflate_3, bzip2_3}: a single LZMA_3 stream of half a megabyte runs on one wave for seconds (test_gpu_rezip_device.py
+    # leaves the LZMA approaches out of its large entry for the same reason)
+    mask = (1 << 0) | (1 << 5) | (1 << 7)
+    want = _orders.rezip_model(z_arc, {nm.encode(): d for nm, d in z_entries}, mask)
+
+    def rezip(enc):
+        import torch
+        t = torch.from_numpy(np.frombuffer(z_arc, dtype=np.uint8).copy()).cuda()
+        arc, rep = za.ReZip(enc).rezip_device(za.ZipInfo.load_device(t), approaches=mask, report=True)
+        return arc.cpu().numpy().tobytes(), rep["entries"]
+    add("rezip_device(archive of 3.7 MiB)", z_size + 1, rezip, want)
+
+    needle = text[100000:100005]
+    found = []
+    for nm, d in sorted((nm.encode(), d) for nm, d in z_entries):
+        occ, first = _findzip.closed_form(d, needle, True)
+        if occ:
+            found.append((nm, occ, first))
+    assert found
+
+    def findzip(enc):
+        r = za.FindZip(enc).find(z_arc, needle)
+        return [(e[4], e[1], e[2]) for e in r.entries if e[1] > 0], r.damaged
+    add("findzip(archive of 3.7 MiB)", z_size + 2, findzip, (found, 0))
+
+    lg_datas = L.batch_inputs(100)
+    for method, name in ((1, "shrink_batch"), (5, "reduce_batch")):
+        want = [(rc, s if rc == 0 else None, reg) for rc, s, reg in (L.model_result(d, method) for d in lg_datas)]
+        add("%s(100 entries)" % name, sum(map(len, lg_datas)) + method,
+            (lambda enc: enc.shrink_batch(lg_datas)) if method == 1 else (lambda enc: enc.reduce_batch(lg_datas, 5)), want)
+
+    trainer = _trained.fixture("wsbase.csv")[:9000]
+    src = _trained.fixture("wm1ns.csv")
+    tr_datas = [src[37 * k:37 * k + (k * 7) % 300] for k in range(200)]
+    stub = _trained.stub_of(trainer)
+    skip = max(0, len(stub) - _trained.MARGIN)
+    msgs = [_trained.message_of(trainer, d, skip) for d in tr_datas]
+
+    def trained(enc):
+        tc = td = None
+        try:
+            tc = za.TrainedCompression(enc, trainer)
+            got = tc.encode(tr_datas)
+            td = za.TrainedCompression.for_decoding(enc, tc.stub, tc.skip, tc.trainer_len)
+            return tc.stub, got, td.decode(msgs, [len(d) for d in tr_datas])
+        finally:
+            for h in (tc, td):
+                if h is not None:
+                    h.close()
+    add("trained(200 messages)", sum(map(len, tr_datas)), trained, (stub, msgs, tr_datas))
 
 
 @pytest.fixture(scope="module")

@@ -8,7 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from _common import ROOT
+from _common import ROOT, plan_library
 
 E_INVALID, E_TOO_LARGE = -1, -4
 W_METHOD, W_TOO_LARGE, W_IN, W_OUT, W_KEYS, W_OVERLAP = 1, 2, 3, 4, 5, 6
@@ -19,8 +19,7 @@ SRC = os.path.join(ROOT, "tests", "unzip", "unzip_plan_host.cpp")
 
 @pytest.fixture(scope="module")
 def plan():
-    p = os.path.join(ROOT, "tests", "unzip", "libunzip_plan_host.so")
-    L = ctypes.CDLL(p)                                                       # made by __graft_entry__.build(); a missing library is an error
+    L = ctypes.CDLL(plan_library("unzip", "unzip_plan_host", "zada_unzip_plan.h"))
     vp, u64, i32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int
     L.up_check.argtypes = [vp, i32, u64, u64, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.up_payload.restype = u64

@@ -9,7 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from _common import ROOT, product
+from _common import ROOT, plan_library, product
 
 E_INVALID, E_TOO_LARGE = -1, -4
 W_NULL, W_NAME, W_TOO_LARGE, W_OVERLAP = 1, 2, 3, 4
@@ -24,7 +24,7 @@ MARGIN = 22 + 56 + 20 + 2 ** 16 + 10
 
 @pytest.fixture(scope="module")
 def plan():
-    L = ctypes.CDLL(os.path.join(ROOT, "tests", "zip", "libzip_plan_host.so"))    # made by __graft_entry__.build(); a missing library is an error
+    L = ctypes.CDLL(plan_library("zip", "zip_plan_host", "zada_zip_plan.h", "zada_legacy_plan.h"))
     vp, u64, i32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int
     L.zp_method_name.restype = ctypes.c_char_p
     L.zp_why_text.restype = ctypes.c_char_p

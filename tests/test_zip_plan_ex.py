@@ -9,7 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from _common import ROOT, product
+from _common import ROOT, plan_library, product
 
 G_BATCH, G_SINGLE, G_STORE = 0, 1, 2
 K_BLOB, K_STREAM, K_DATA = 0, 1, 2
@@ -24,7 +24,7 @@ BASES = (0, 77, M32 - 1000, M32 - 30, M32, (1 << 32) - MARGIN - 100, 1 << 33)
 
 @pytest.fixture(scope="module")
 def plan():
-    L = ctypes.CDLL(os.path.join(ROOT, "tests", "zip", "libzip_plan_ex_host.so"))    # made by __graft_entry__.build(); a missing library is an error
+    L = ctypes.CDLL(plan_library("zip", "zip_plan_ex_host", "zada_zip_plan.h", "zada_legacy_plan.h"))
     vp, u64, i32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int
     L.zpx_one_block.restype = u64
     L.zpx_bound.restype = u64
