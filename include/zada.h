@@ -109,7 +109,15 @@ typedef struct zada_ctx zada_ctx;
  * Called with a monotone 0..100 at kernel-phase granularity. */
 typedef int (*zada_feedback_fn)(int percents_done, void *user);
 
-/* Context = device + stream + workspace.  device >= 0 selects a HIP device. */
+/* Context = device + stream + workspace.  device >= 0 selects a HIP device.
+ * Ordering against the caller's queued work, for every call that takes a device address (the *_device calls and the tables of device addresses):
+ * (1) work queued on the legacy default (null) stream before the call is ordered before the call's accesses -- the context's streams are made by
+ * hipStreamCreate, so they are blocking with respect to the null stream (PyTorch's default stream is the null stream), and every other stream the
+ * library owns touches caller memory only behind an event recorded on, or a host wait for, the context's stream; (2) work on any OTHER stream is
+ * the caller's to finish before the call -- the library waits for no stream it does not know; the tensor-taking methods of the Python package do
+ * that for torch's current stream (torch.cuda.current_stream (device).synchronize () just before their one C call), the raw-pointer methods of
+ * Encoder and the Ada shim do not; (3) every call returns with its work complete: what it wrote may be read, and what it read may be
+ * overwritten, on any stream at once.  tests/test_gpu_stream_order.py holds all three behind a producer that is provably still pending. */
 zada_ctx *zada_create(int device);
 void zada_destroy(zada_ctx *ctx);
 const char *zada_last_error(const zada_ctx *ctx);
