@@ -295,7 +295,11 @@ int zada_inflate_batch(zada_ctx *ctx, int count, const int *format, const uint8_
  * repairs, has fewer than two live chunks, is Deflate64 (format 9) or whose workspace cannot be had runs on zada_inflate_device's one wave
  * instead, with nothing written to d_out before; zada_inflate_par_last says which way the last call went.  Opt-in: no other entry point takes
  * this path unless the knob "inflate_par_min_kib" (0 = off) is set, which sends the Deflate entries of zada_unzip_device whose compressed size
- * is at least that many KiB through it, one after the other.  EXPERIMENTAL: see profiles/inflate_par/NOTES.md for what it gains. */
+ * is at least that many KiB through it, one after the other.  EXPERIMENTAL: see profiles/inflate_par/NOTES.md for what it gains.
+ * The knob "inflate_par_deflate64" (0 or 1, default 0; anything else is ZADA_E_INVALID): with 1, Deflate64 (format 9) streams take the method
+ * too -- in these two calls, and for the method 9 entries of zada_unzip_device that "inflate_par_min_kib" selects --, with every other reason
+ * to hand the stream to the one wave unchanged.  A Deflate64 marker's offset takes 16 bits (its window is 65 536), so its symbols have 32 bits:
+ * a workspace of 4 bytes per output byte where Deflate takes 2.  With 0, a format 9 call answers as before: the one wave, reason "format". */
 int zada_inflate_par(zada_ctx *ctx, int format, const uint8_t *in, uint64_t n_in, uint8_t *out, uint64_t cap,
                      uint64_t *out_len, uint64_t *in_used, uint32_t *crc_inout);
 int zada_inflate_par_device(zada_ctx *ctx, int format, const void *d_in, uint64_t n_in, void *d_out, uint64_t cap,

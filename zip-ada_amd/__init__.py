@@ -347,13 +347,15 @@ class Encoder:
             pass
 
     def set_knob(self, name, value):
-        """Tuning / test knobs ("budget", "max_demand_rounds", "inner_budget", "shard_kib", "span_mib", "batch_mib", "bunzip_batch_mib", "inflate_par_chunk_kib", "inflate_par_repair_pct", "inflate_par_min_kib"); none changes a byte of output.
+        """Tuning / test knobs ("budget", "max_demand_rounds", "inner_budget", "shard_kib", "span_mib", "batch_mib", "bunzip_batch_mib", "inflate_par_chunk_kib", "inflate_par_repair_pct", "inflate_par_min_kib", "inflate_par_deflate64"); none changes a byte of output.
+        "inflate_par_deflate64" = 1: inflate_par* and unzip_device's parallel path take Deflate64 (format 9) streams too (UnZip (..., parallel_deflate64=True) sets it around its calls).
         "unzip_legacy" = 1: unzip_device, compzip_device and findzip_device know methods 1 .. 6 (UnZip / CompZip / FindZip set it around their calls).
         "zip_legacy" = 1: zip_device_ex takes Shrink_1 and Reduce_1 .. _4, rezip_device the approaches shrink and reduce_4 (legacy=True sets it around the calls).
         "lzma_dict" is the reference's dictionary_size parameter for LZMA_3 (0 = the entry's size, what Zip.Compress.LZMA_E passes).
         "trained_fork" = 0: TrainedCompression works through every entry's whole stream (the same bytes; for measurements)."""
         if self.lib.zada_set_knob(self.ctx, name.encode(), int(value)) != 0:
             raise ZadaError("unknown knob %r" % name)
+        self.__dict__.setdefault("_knobs_set", {})[name] = int(value)          # (what a caller that sets a knob around a call puts back)
 
     def _err(self, rc, what):
         if rc == E_DATA:
@@ -1777,6 +1779,8 @@ class UnZip:
     UnZip (encoder, parallel_inflate=KiB) -- experimental -- sends Deflate entries whose compressed size is at least that many KiB through
     Encoder.inflate_par, one stream on many waves: extract calls it entry by entry (last_parallel lists their records), extract_device sets the knob
     "inflate_par_min_kib" around its call (Encoder.inflate_par_last then holds the sums).  Results, exceptions and texts are the default's.
+    With parallel_deflate64=True as well, Deflate64 entries of that size go the same way (the knob "inflate_par_deflate64", set around the calls
+    and put back; 4 bytes of workspace per output byte where Deflate takes 2).
     UnZip (encoder, legacy=True) also decodes Shrink (1), Reduce (2 .. 5) and Implode (6) entries: all of a call through ONE unlegacy_batch (one wave
     per entry; an Implode entry's general-purpose bits 1 and 2 say how it was written); extract_device sets the knob "unzip_legacy" around its call.
     Without legacy=True they are UnsupportedMethod, in the words of before."""
@@ -1784,7 +1788,7 @@ class UnZip:
     _NAMES = {1: "Shrink", 2: "Reduce_1", 3: "Reduce_2", 4: "Reduce_3", 5: "Reduce_4", 6: "Implode", 12: "BZip2", 14: "LZMA", 98: "PPMd", 99: "AES"}
     _STREAMS = {1: "Shrink", 2: "Reduce", 3: "Reduce", 4: "Reduce", 5: "Reduce", 6: "Implode", 8: "Deflate", 9: "Deflate64", 12: "BZip2", 14: "LZMA"}
 
-    def __init__(self, encoder, bzip2=False, lzma=False, parallel_inflate=None, legacy=False):
+    def __init__(self, encoder, bzip2=False, lzma=False, parallel_inflate=None, legacy=False, parallel_deflate64=False):
         self.enc = encoder
         self.bzip2 = bool(bzip2)
         self.lzma = bool(lzma)
@@ -1792,6 +1796,9 @@ class UnZip:
         if parallel_inflate is not None and int(parallel_inflate) < 1:
             raise ZadaError("UnZip: parallel_inflate is a size in KiB, at least 1, or None")
         self.parallel_inflate = None if parallel_inflate is None else int(parallel_inflate)
+        if parallel_deflate64 and self.parallel_inflate is None:
+            raise ZadaError("UnZip: parallel_deflate64 needs parallel_inflate, the size in KiB from which an entry goes the parallel way")
+        self.parallel_deflate64 = bool(parallel_deflate64)
         self.last_parallel = []                            # extract: (name, inflate_par_last ()) of the entries that went through inflate_par
 
     def _unsupported(self, e):
@@ -1869,15 +1876,19 @@ class UnZip:
                 res[k] = ex if ex is not None else None if test_only else out
         self.last_parallel = []
         if self.parallel_inflate is not None:
-            for k, e in enumerate(ents):
-                if k in res or e.method != 8 or len(payload[k]) < self.parallel_inflate << 10:
-                    continue
-                try:
-                    out, used, reg = self.enc.inflate_par(payload[k], e.usize)
-                    settle([k], [(0, out, len(out), used, reg)])
-                except DataError:
-                    settle([k], [(E_DATA, None, 0, 0, 0)])
-                self.last_parallel.append((e.name, self.enc.inflate_par_last()))
+            was = self._deflate64_knob()
+            try:
+                for k, e in enumerate(ents):
+                    if k in res or e.method not in ((8, 9) if self.parallel_deflate64 else (8,)) or len(payload[k]) < self.parallel_inflate << 10:
+                        continue
+                    try:
+                        out, used, reg = self.enc.inflate_par(payload[k], e.usize, format=e.method)
+                        settle([k], [(0, out, len(out), used, reg)])
+                    except DataError:
+                        settle([k], [(E_DATA, None, 0, 0, 0)])
+                    self.last_parallel.append((e.name, self.enc.inflate_par_last()))
+            finally:
+                self._deflate64_knob(was)
         todo = [k for k in range(len(ents)) if k not in res and ents[k].method in (8, 9)]
         if todo:
             settle(todo, self.enc.inflate_batch([payload[k] for k in todo], [ents[k].usize for k in todo], [ents[k].method for k in todo], deliver=not test_only))
@@ -1898,6 +1909,16 @@ class UnZip:
             ex = self._verdict(e, 0, len(d), (zlib.crc32(d) & 0xFFFFFFFF) ^ 0xFFFFFFFF)
             res[k] = ex if ex is not None else None if test_only else d
         return self._finish(ents, res, test_only, errors)
+
+    def _deflate64_knob(self, back=None):
+        """parallel_deflate64=True: sets the knob "inflate_par_deflate64" and returns the value it had; with that value, puts it back."""
+        if not self.parallel_deflate64:
+            return None
+        if back is None:
+            back = getattr(self.enc, "_knobs_set", {}).get("inflate_par_deflate64", 0)
+            self.enc.set_knob("inflate_par_deflate64", 1)
+            return back
+        self.enc.set_knob("inflate_par_deflate64", back)
 
     def extract_device(self, info, what=None, password=None, test_only=False, errors="raise"):
         """extract for an archive that lies in device memory: info is a ZipInfo.load_device of a tensor on the encoder's device.  Returns
@@ -1946,6 +1967,7 @@ class UnZip:
             torch.cuda.current_stream(t.device).synchronize()
             if self.parallel_inflate is not None:
                 self.enc.set_knob("inflate_par_min_kib", self.parallel_inflate)
+            was = self._deflate64_knob()
             if self.legacy:
                 self.enc.set_knob("unzip_legacy", 1)
             try:
@@ -1953,6 +1975,7 @@ class UnZip:
             finally:
                 if self.parallel_inflate is not None:
                     self.enc.set_knob("inflate_par_min_kib", 0)
+                self._deflate64_knob(was)
                 if self.legacy:
                     self.enc.set_knob("unzip_legacy", 0)
             good = (r["rc"] == 0) & (r["out_len"] == usize) & ((r["crc"] ^ np.uint32(0xFFFFFFFF)) == col(lambda e: e.crc, np.uint32))

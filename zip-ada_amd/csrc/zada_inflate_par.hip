@@ -1,14 +1,15 @@
-// zada_inflate_par.hip -- one large raw Deflate stream (Zip format 8) on many waves: the method of zada_inflate_par_logic.h (two-stage decoding
-// with window markers).  Every dependency between chunks is a kernel boundary or a host step: no kernel waits on another workgroup.
+// zada_inflate_par.hip -- one large raw Deflate stream (Zip format 8; Deflate64, format 9, with the knob "inflate_par_deflate64") on many waves:
+// the method of zada_inflate_par_logic.h (two-stage decoding with window markers).  Every dependency between chunks is a kernel boundary or a host step: no kernel waits on another workgroup.
 //   k_infp_scout : one wave per chunk: find the first candidate block start (64 bit offsets per step through infp_filter, read from the staged
 //                  input in LDS; survivors one at a time through inf_dynamic_header), then count from it without writing.
 //   (host)       : the chain over the records (infp_walk); a chunk whose start is not the end of the one before is scouted again, exactly.
-//   k_infp_decode: one wave per live chunk: k_inflate's token queue and expansion, on 16-bit symbols in a workspace of 2 bytes per output byte.
-//   k_infp_window: one workgroup, the live chunks in order: the markers in the last 32 KiB of each chunk become symbols.
+//   k_infp_decode: one wave per live chunk: k_inflate's token queue and expansion, on 16-bit symbols in a workspace of 2 bytes per output byte
+//                  (Deflate64: 32-bit symbols, 4 bytes per output byte -- InfpFmt in zada_inflate_par_logic.h says why).
+//   k_infp_window: one workgroup, the live chunks in order: the markers in the last 32 KiB (Deflate64: 64 KiB) of each chunk become symbols.
 //   k_infp_finish: symbols to bytes in d_out, all chunks in parallel.
 //   CRC-32       : the encoder's k_crc_chunks / k_crc_fold (crc_launch / crc_finish), the bytes before d_out's first 16-byte boundary on the host.
-// A stream the method does not take (damaged, too many repairs, one live chunk, Deflate64, no memory) is decoded by zada_inflate_device's one
-// wave, whose verdict is the answer; nothing has been written to d_out before that.
+// A stream the method does not take (damaged, too many repairs, one live chunk, Deflate64 without its knob, no memory) is decoded by
+// zada_inflate_device's one wave, whose verdict is the answer; nothing has been written to d_out before that.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -24,8 +25,6 @@ struct zada_ctx { zada::Ctx c; };
 
 namespace zada {
 
-typedef __attribute__((address_space(1))) uint16_t gu16;
-
 // the reader of a wave behind the interface infp_blocks asks for
 struct InfpWaveEnvBase {
   gcu8 *in; uint64_t n_in; uint32_t *stage;
@@ -39,13 +38,17 @@ struct InfpCountEnv : InfpWaveEnvBase {
 };
 
 // inf_expand on symbols: lane q holds token q, written behind `pos`; base: the chunk's first output position.  A source before base is a marker.
-__device__ __forceinline__ void infp_expand(gu16 *sym, uint64_t base, uint64_t pos, uint32_t q, uint32_t my_len, uint32_t my_dist, uint32_t my_val, uint64_t &fence_pos) {
+// (A Deflate64 token has up to 65 538 symbols and may begin at base itself: every source of a token lies before its first symbol P, so the i % D
+// loop reads nothing the token writes, whatever its length, and the fence rule asks only where the sources end.)
+template <int FORMAT> __device__ __forceinline__ void infp_expand(__attribute__((address_space(1))) typename InfpFmt<FORMAT>::sym_t *sym, uint64_t base, uint64_t pos,
+                                                                  uint32_t q, uint32_t my_len, uint32_t my_dist, uint32_t my_val, uint64_t &fence_pos) {
+  typedef typename InfpFmt<FORMAT>::sym_t sym_t;
   const uint32_t lane = threadIdx.x;
   uint32_t len = lane < q ? my_len : 0u, incl = len;
 #pragma unroll
   for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t u = __shfl_up(incl, d, 64); if (lane >= d) incl += u; }
   const uint64_t start = pos + (incl - len);
-  if (len && my_dist == 0) sym[start] = (uint16_t)my_val;
+  if (len && my_dist == 0) sym[start] = (sym_t)my_val;
   uint64_t mask = __ballot(len != 0 && my_dist != 0);
   while (mask) {
     const int k = __ffsll((unsigned long long)mask) - 1;
@@ -63,15 +66,15 @@ __device__ __forceinline__ void infp_expand(gu16 *sym, uint64_t base, uint64_t p
     }
     for (uint32_t i = lane; i < L; i += INF_WAVE) {
       const uint64_t sp = P - D + (D >= L ? i : i % D);
-      sym[P + i] = sp >= base ? sym[sp] : (uint16_t)infp_marker(base, sp);
+      sym[P + i] = sp >= base ? sym[sp] : (sym_t)infp_marker<FORMAT>(base, sp);
     }
   }
 }
 
 // decode: the token queue of k_inflate; pos is the position in the whole output, so "distance beyond the bytes written so far" is exact
-struct InfpDecodeEnv : InfpWaveEnvBase {
-  gu16 *sym; uint64_t base, limit, pos, qpos, fence_pos; uint32_t q, my_len, my_dist, my_val;
-  __device__ __forceinline__ void flush() { infp_expand(sym, base, qpos, q, my_len, my_dist, my_val, fence_pos); q = 0; my_len = 0; qpos = pos; }
+template <int FORMAT> struct InfpDecodeEnv : InfpWaveEnvBase {
+  __attribute__((address_space(1))) typename InfpFmt<FORMAT>::sym_t *sym; uint64_t base, limit, pos, qpos, fence_pos; uint32_t q, my_len, my_dist, my_val;
+  __device__ __forceinline__ void flush() { infp_expand<FORMAT>(sym, base, qpos, q, my_len, my_dist, my_val, fence_pos); q = 0; my_len = 0; qpos = pos; }
   __device__ __forceinline__ uint32_t stored(uint64_t at, uint32_t len) {
     if (pos + len > limit) return INF_R_OUTPUT_FULL;
     flush();
@@ -89,8 +92,8 @@ struct InfpDecodeEnv : InfpWaveEnvBase {
   }
 };
 
-__global__ void __launch_bounds__(INF_WAVE) k_infp_scout(const uint8_t *in_, uint64_t n_in, uint64_t chunk_bytes, const InfpJob *__restrict__ jobs, uint32_t njobs,
-                                                         InfpRec *recs) {
+template <bool D64> __global__ void __launch_bounds__(INF_WAVE) k_infp_scout(const uint8_t *in_, uint64_t n_in, uint64_t chunk_bytes, const InfpJob *__restrict__ jobs,
+                                                                             uint32_t njobs, InfpRec *recs) {
   __shared__ InfTables T;
   __shared__ uint32_t stage[INF_STAGE / 4 + 2];
   const uint32_t lane = threadIdx.x;
@@ -115,13 +118,13 @@ __global__ void __launch_bounds__(INF_WAVE) k_infp_scout(const uint8_t *in_, uin
       const uint32_t b = (uint32_t)((my >> 3) - br.base), w0 = b >> 2, sh = (b & 3u) * 8u + (uint32_t)(my & 7u);      // sh <= 31
       const uint64_t q0 = (uint64_t)stage[w0] | (uint64_t)stage[w0 + 1] << 32, q1 = (uint64_t)stage[w0 + 2] | (uint64_t)stage[w0 + 3] << 32;
       const uint64_t lo = sh ? (q0 >> sh) | (q1 << (64u - sh)) : q0, hi = q1 >> sh;
-      uint64_t mask = __ballot(my < hi_bit && infp_filter(lo, hi));
+      uint64_t mask = __ballot(my < hi_bit && infp_filter(lo, hi, D64));
       while (mask) {
         const int k = __ffsll((unsigned long long)mask) - 1;
         mask &= mask - 1;
         const uint64_t cand = o + (uint32_t)k;
         infp_seek(br, env, cand);
-        if (infp_candidate(br, T, lane, INF_WAVE)) { start = cand; found = true; break; }      // (a survivor's header may move the stage: asked again above)
+        if (infp_candidate(br, T, lane, INF_WAVE, D64)) { start = cand; found = true; break; }      // (a survivor's header may move the stage: asked again above)
       }
     }
   }
@@ -131,60 +134,71 @@ __global__ void __launch_bounds__(INF_WAVE) k_infp_scout(const uint8_t *in_, uin
     // ---- count ----
     infp_seek(br, env, start);
     uint32_t final = 0;
-    R.rule = infp_blocks(br, T, n_in, stop_bits, lane, INF_WAVE, env, final);
+    R.rule = infp_blocks(br, T, n_in, stop_bits, lane, INF_WAVE, env, final, D64);
     R.end_bit = br.used_bits(); R.bytes = env.bytes;
     if (final) R.flags |= INFP_F_FINAL;
   }
   if (lane == 0) recs[J.chunk] = R;
 }
 
-__global__ void __launch_bounds__(INF_WAVE) k_infp_decode(const uint8_t *in_, uint64_t n_in, InfpLive *live, uint32_t nlive, uint16_t *sym_) {
+template <int FORMAT> __global__ void __launch_bounds__(INF_WAVE) k_infp_decode(const uint8_t *in_, uint64_t n_in, InfpLive *live, uint32_t nlive,
+                                                                                typename InfpFmt<FORMAT>::sym_t *sym_) {
   __shared__ InfTables T;
   __shared__ uint32_t stage[INF_STAGE / 4 + 2];
   const uint32_t lane = threadIdx.x;
   if (blockIdx.x >= nlive) return;
   const InfpLive J = live[blockIdx.x];
-  InfpDecodeEnv env;
+  InfpDecodeEnv<FORMAT> env;
   env.in = (gcu8 *)in_; env.n_in = n_in; env.stage = stage;
-  env.sym = (gu16 *)sym_; env.base = J.off; env.limit = J.off + J.bytes; env.pos = env.qpos = J.off; env.fence_pos = J.off;
+  env.sym = (__attribute__((address_space(1))) typename InfpFmt<FORMAT>::sym_t *)sym_;
+  env.base = J.off; env.limit = J.off + J.bytes; env.pos = env.qpos = J.off; env.fence_pos = J.off;
   env.q = 0; env.my_len = env.my_dist = env.my_val = 0;
   InfWaveReader br;
   infp_seek(br, env, J.start_bit);
   uint32_t final = 0;
-  uint32_t rule = infp_blocks(br, T, n_in, J.stop_bits, lane, INF_WAVE, env, final);
+  uint32_t rule = infp_blocks(br, T, n_in, J.stop_bits, lane, INF_WAVE, env, final, InfpFmt<FORMAT>::D64);
   if (!rule) env.flush();
   if (!rule && env.pos != env.limit) rule = INF_R_OUTPUT_FULL;          // (not what the count saw: the stream goes to the one-wave decoder)
   if (lane == 0) { live[blockIdx.x].end_bit = br.used_bits(); live[blockIdx.x].rule = rule; live[blockIdx.x].final = final; }
 }
 
-constexpr uint32_t INFP_WIN_THREADS = 1024;
-__global__ void __launch_bounds__(INFP_WIN_THREADS) k_infp_window(const InfpLive *__restrict__ live, uint32_t nlive, uint16_t *sym, uint64_t *markers) {
+constexpr uint32_t INFP_WIN_THREADS = 1024, INFP_WIN_PIECE = 32768, INFP_WIN_DONE = 0x40000000u;      // (the flag of a resolved symbol: no bit of either marker layout)
+template <int FORMAT> __global__ void __launch_bounds__(INFP_WIN_THREADS) k_infp_window(const InfpLive *__restrict__ live, uint32_t nlive,
+                                                                                        typename InfpFmt<FORMAT>::sym_t *sym, uint64_t *markers) {
+  typedef typename InfpFmt<FORMAT>::sym_t sym_t;
+  constexpr uint32_t WINDOW = InfpFmt<FORMAT>::WINDOW, MARK = InfpFmt<FORMAT>::MARK, PER = INFP_WIN_PIECE / INFP_WIN_THREADS;
   uint32_t mine = 0;
   for (uint32_t j = 1; j < nlive; j++) {
     const uint64_t base = live[j].off, end = base + live[j].bytes;
-    const uint64_t from = end - base > INFP_WINDOW ? end - INFP_WINDOW : base;
-    // a thread's 32 symbols first, then what its markers point at, then the stores: the loads of a step do not wait for one another (a chunk is
+    const uint64_t from = end - base > WINDOW ? end - WINDOW : base;
+    // The window in pieces of 32 Ki symbols -- one for Deflate, two for Deflate64: the markers of a chunk point in front of it, never into it, so
+    // its pieces do not depend on one another and a thread holds 32 symbols at a time for either format.
+    // A thread's 32 symbols first, then what its markers point at, then the stores: the loads of a step do not wait for one another (a chunk is
     // two memory latencies and a barrier, not sixty-four)
-    uint32_t v[INFP_WINDOW / INFP_WIN_THREADS];
+#pragma unroll 1
+    for (uint32_t piece = 0; piece < WINDOW / INFP_WIN_PIECE; piece++) {
+      const uint64_t first = from + (uint64_t)piece * INFP_WIN_PIECE + threadIdx.x;
+      uint32_t v[PER];
 #pragma unroll
-    for (uint32_t k = 0; k < INFP_WINDOW / INFP_WIN_THREADS; k++) {
-      const uint64_t i = from + threadIdx.x + (uint64_t)k * INFP_WIN_THREADS;
-      v[k] = i < end ? sym[i] : 0u;
+      for (uint32_t k = 0; k < PER; k++) {
+        const uint64_t i = first + (uint64_t)k * INFP_WIN_THREADS;
+        v[k] = i < end ? sym[i] : 0u;
+      }
+#pragma unroll
+      for (uint32_t k = 0; k < PER; k++)
+        if (v[k] & MARK) v[k] = INFP_WIN_DONE | sym[infp_marker_source<FORMAT>(base, v[k])];
+#pragma unroll
+      for (uint32_t k = 0; k < PER; k++)
+        if (v[k] & INFP_WIN_DONE) { sym[first + (uint64_t)k * INFP_WIN_THREADS] = (sym_t)(v[k] & ~INFP_WIN_DONE); mine++; }
     }
-#pragma unroll
-    for (uint32_t k = 0; k < INFP_WINDOW / INFP_WIN_THREADS; k++)
-      if (v[k] & INFP_MARK) v[k] = 0x10000u | sym[infp_marker_source(base, v[k])];
-#pragma unroll
-    for (uint32_t k = 0; k < INFP_WINDOW / INFP_WIN_THREADS; k++)
-      if (v[k] & 0x10000u) { sym[from + threadIdx.x + (uint64_t)k * INFP_WIN_THREADS] = (uint16_t)v[k]; mine++; }
     __syncthreads();            // the next chunk reads what this one resolved
   }
   if (mine) atomicAdd((unsigned long long *)markers, (unsigned long long)mine);
 }
 
 constexpr uint32_t INFP_FIN_THREADS = 256, INFP_FIN_PIECE = 16384;
-__global__ void __launch_bounds__(INFP_FIN_THREADS) k_infp_finish(const InfpLive *__restrict__ live, uint32_t nlive, const uint16_t *__restrict__ sym, uint8_t *out,
-                                                                  uint64_t *markers) {
+template <int FORMAT> __global__ void __launch_bounds__(INFP_FIN_THREADS) k_infp_finish(const InfpLive *__restrict__ live, uint32_t nlive,
+                                                                                        const typename InfpFmt<FORMAT>::sym_t *__restrict__ sym, uint8_t *out, uint64_t *markers) {
   const uint32_t j = blockIdx.x;
   if (j >= nlive) return;
   const uint64_t base = live[j].off, bytes = live[j].bytes;
@@ -193,7 +207,7 @@ __global__ void __launch_bounds__(INFP_FIN_THREADS) k_infp_finish(const InfpLive
     const uint64_t p1 = p0 + INFP_FIN_PIECE < bytes ? p0 + INFP_FIN_PIECE : bytes;
     for (uint64_t i = base + p0 + threadIdx.x; i < base + p1; i += INFP_FIN_THREADS) {
       uint32_t v = sym[i];
-      if (v & INFP_MARK) { v = sym[infp_marker_source(base, v)]; mine++; }
+      if (v & InfpFmt<FORMAT>::MARK) { v = sym[infp_marker_source<FORMAT>(base, v)]; mine++; }
       out[i] = (uint8_t)v;
     }
   }
@@ -201,9 +215,21 @@ __global__ void __launch_bounds__(INFP_FIN_THREADS) k_infp_finish(const InfpLive
 }
 
 // ---- host side ----
+// the launches that know the symbol: sym is the workspace of InfpFmt <FORMAT>::sym_t
+template <int FORMAT> static void infp_launch_decode(hipStream_t st, const uint8_t *in, uint64_t n_in, InfpLive *d_live, uint32_t nl, void *sym) {
+  hipLaunchKernelGGL(k_infp_decode<FORMAT>, dim3(nl), dim3(INF_WAVE), 0, st, in, n_in, d_live, nl, (typename InfpFmt<FORMAT>::sym_t *)sym);
+}
+template <int FORMAT> static void infp_launch_resolve(Ctx *c, hipStream_t st, const InfpLive *d_live, uint32_t nl, void *sym, uint8_t *out, uint64_t *d_mark) {
+  typedef typename InfpFmt<FORMAT>::sym_t sym_t;
+  hipLaunchKernelGGL(k_infp_window<FORMAT>, dim3(1), dim3(INFP_WIN_THREADS), 0, st, d_live, nl, (sym_t *)sym, d_mark);
+  c->tmark("inflate_par:k_infp_window");
+  hipLaunchKernelGGL(k_infp_finish<FORMAT>, dim3(nl, 8), dim3(INFP_FIN_THREADS), 0, st, d_live, nl, (const sym_t *)sym, out, d_mark);
+  c->tmark("inflate_par:k_infp_finish");
+}
+
 struct InfpState {
   uint8_t *tabs = nullptr; uint64_t cap_tabs = 0;      // jobs, records, live chunks, the marker counter
-  uint16_t *sym = nullptr; uint64_t cap_sym = 0;       // 2 bytes per output byte
+  void *sym = nullptr; uint64_t cap_sym = 0;           // the symbols: 2 bytes per output byte, Deflate64 4
   zada_inflate_par_info last{};
 };
 static InfpState *infp_state(Ctx *c) {
@@ -243,7 +269,8 @@ int inflate_par_try(Ctx *c, int format, const void *d_in, uint64_t n_in, void *d
   memset(&I, 0, sizeof I);
   I.streams = 1;
   auto fall = [&](int reason) { I.fell_back = 1; I.reason = reason; return 1; };
-  if (format != 8) return fall(INFP_FORMAT);
+  if (format != 8 && !(format == 9 && c->knob_infp_deflate64)) return fall(INFP_FORMAT);
+  const bool d64 = format == 9;
   const uint64_t chunk_bytes = (uint64_t)c->knob_infp_chunk_kib << 10;
   const uint64_t nch64 = (n_in + chunk_bytes - 1) / chunk_bytes;
   I.chunks = nch64;
@@ -261,7 +288,11 @@ int inflate_par_try(Ctx *c, int format, const void *d_in, uint64_t n_in, void *d
   for (uint32_t k = 0; k < nch; k++) jobs[k] = InfpJob{k ? INFP_SEARCH : 0ull, k, 0};
   hipMemcpyAsync(S->tabs + o_jobs, jobs.data(), (size_t)nch * sizeof(InfpJob), hipMemcpyHostToDevice, st);
   c->tmark("inflate_par:begin");
-  hipLaunchKernelGGL(k_infp_scout, dim3(nch), dim3(INF_WAVE), 0, st, in, n_in, chunk_bytes, (const InfpJob *)(S->tabs + o_jobs), nch, (InfpRec *)(S->tabs + o_recs));
+  auto scout = [&](uint32_t njobs) {
+    hipLaunchKernelGGL(d64 ? k_infp_scout<true> : k_infp_scout<false>, dim3(njobs), dim3(INF_WAVE), 0, st, in, n_in, chunk_bytes, (const InfpJob *)(S->tabs + o_jobs), njobs,
+                       (InfpRec *)(S->tabs + o_recs));
+  };
+  scout(nch);
   c->tmark("inflate_par:k_infp_scout");
   hipMemcpyAsync(recs.data(), S->tabs + o_recs, (size_t)nch * sizeof(InfpRec), hipMemcpyDeviceToHost, st);
   if (hip_check(c, hipGetLastError(), "inflate_par scout launch") || hip_check(c, hipStreamSynchronize(st), "inflate_par scout")) return ZADA_E_HIP_;
@@ -279,7 +310,7 @@ int inflate_par_try(Ctx *c, int format, const void *d_in, uint64_t n_in, void *d
     if (W.repairs > bound) return fall(INFP_REPAIRS);
     const InfpJob J{W.expect, W.cur, 0};
     hipMemcpyAsync(S->tabs + o_jobs, &J, sizeof J, hipMemcpyHostToDevice, st);
-    hipLaunchKernelGGL(k_infp_scout, dim3(1), dim3(INF_WAVE), 0, st, in, n_in, chunk_bytes, (const InfpJob *)(S->tabs + o_jobs), 1u, (InfpRec *)(S->tabs + o_recs));
+    scout(1u);
     hipMemcpyAsync(&recs[W.cur], S->tabs + o_recs + (uint64_t)W.cur * sizeof(InfpRec), sizeof(InfpRec), hipMemcpyDeviceToHost, st);
     if (hip_check(c, hipGetLastError(), "inflate_par repair launch") || hip_check(c, hipStreamSynchronize(st), "inflate_par repair")) return ZADA_E_HIP_;
     I.scout_rounds++;
@@ -288,7 +319,7 @@ int inflate_par_try(Ctx *c, int format, const void *d_in, uint64_t n_in, void *d
   if (W.total > cap) return fall(INFP_DAMAGED);
   if (W.live < 2) return fall(INFP_SINGLE_CHUNK);
   const uint64_t total = W.total;
-  if (total && !infp_grow(c, (void **)&S->sym, &S->cap_sym, total * 2)) return fall(INFP_MEMORY);
+  if (total && !infp_grow(c, &S->sym, &S->cap_sym, total * (d64 ? sizeof(InfpFmt<9>::sym_t) : sizeof(InfpFmt<8>::sym_t)))) return fall(INFP_MEMORY);
   // the live chunks, in order
   std::vector<InfpLive> live;
   live.reserve(W.live);
@@ -300,7 +331,7 @@ int inflate_par_try(Ctx *c, int format, const void *d_in, uint64_t n_in, void *d
   InfpLive *d_live = (InfpLive *)(S->tabs + o_live);
   uint64_t *d_mark = (uint64_t *)(S->tabs + o_mark);
   std::vector<InfpLive> back(nl);
-  hipLaunchKernelGGL(k_infp_decode, dim3(nl), dim3(INF_WAVE), 0, st, in, n_in, d_live, nl, S->sym);
+  if (d64) infp_launch_decode<9>(st, in, n_in, d_live, nl, S->sym); else infp_launch_decode<8>(st, in, n_in, d_live, nl, S->sym);
   c->tmark("inflate_par:k_infp_decode");
   hipMemcpyAsync(back.data(), d_live, (size_t)nl * sizeof(InfpLive), hipMemcpyDeviceToHost, st);
   if (hip_check(c, hipGetLastError(), "inflate_par decode launch") || hip_check(c, hipStreamSynchronize(st), "inflate_par decode")) return ZADA_E_HIP_;
@@ -314,10 +345,7 @@ int inflate_par_try(Ctx *c, int format, const void *d_in, uint64_t n_in, void *d
     }
   }
   if (total) {
-    hipLaunchKernelGGL(k_infp_window, dim3(1), dim3(INFP_WIN_THREADS), 0, st, (const InfpLive *)d_live, nl, S->sym, d_mark);
-    c->tmark("inflate_par:k_infp_window");
-    hipLaunchKernelGGL(k_infp_finish, dim3(nl, 8), dim3(INFP_FIN_THREADS), 0, st, (const InfpLive *)d_live, nl, (const uint16_t *)S->sym, (uint8_t *)d_out, d_mark);
-    c->tmark("inflate_par:k_infp_finish");
+    if (d64) infp_launch_resolve<9>(c, st, d_live, nl, S->sym, (uint8_t *)d_out, d_mark); else infp_launch_resolve<8>(c, st, d_live, nl, S->sym, (uint8_t *)d_out, d_mark);
   }
   uint64_t marks = 0;
   uint8_t head[16];

@@ -1,4 +1,4 @@
-// zada_inflate_par_logic.h -- one large raw Deflate stream (Zip format 8) decoded by many waves: two-stage decoding with window markers, as in
+// zada_inflate_par_logic.h -- one large raw Deflate (Zip format 8) or Deflate64 (format 9) stream decoded by many waves: two-stage decoding with window markers, as in
 // pugz and rapidgzip.  Host + device inline code with no HIP calls, in the style of zada_inflate_logic.h: the kernels of zada_inflate_par.hip run
 // it with one wave per chunk, tests/inflate_par/inflate_par_host.cpp compiles the same text into a CPU model with one "lane".
 //
@@ -15,6 +15,8 @@
 //            in the already resolved tail of an earlier chunk (a marker reaches at most 32 768 back from its chunk's first byte).
 //   finish : symbols to bytes, all chunks in parallel; a marker that is left reads the resolved tail in front of its chunk.
 // Damaged streams, too many repairs, fewer than two live chunks: the stream goes to the one-wave decoder, whose verdict is the answer.
+// The above is said for Deflate.  Deflate64 differs by its 32 distance codes and its length code 285 (d64 = true in zada_inflate_logic.h), by its
+// window of 65 536 and by the symbol: a marker's offset then takes 16 bits, so the symbol is 32 bits wide (InfpFmt <9>).
 #pragma once
 #include "zada_inflate_logic.h"
 
@@ -22,6 +24,11 @@ namespace zada {
 
 constexpr uint32_t INFP_MARK = 0x8000u;               // a symbol with this bit is a marker; Deflate's window of 32 768 fits the other 15 bits (Deflate64's does not)
 constexpr uint32_t INFP_WINDOW = 32768u;
+// What depends on the format.  A marker's offset is base - 1 - sp, in 0 .. WINDOW - 1; Deflate64's 65 536 offsets and the 256 literals are 65 792
+// values, more than 16 bits hold: its symbol has 32 bits, the flag in the topmost, far from the offset.
+template <int FORMAT> struct InfpFmt;
+template <> struct InfpFmt<8> { typedef uint16_t sym_t; static constexpr bool D64 = false; static constexpr uint32_t MARK = INFP_MARK, WINDOW = INFP_WINDOW; };
+template <> struct InfpFmt<9> { typedef uint32_t sym_t; static constexpr bool D64 = true; static constexpr uint32_t MARK = 0x80000000u, WINDOW = 65536u; };
 constexpr uint64_t INFP_SEARCH = ~0ull;               // InfpJob::start_bit: find the start
 constexpr uint32_t INFP_REPAIR_FLOOR = 2;             // repairs allowed whatever the share says: a stream's final block is never a candidate
 
@@ -32,10 +39,11 @@ struct InfpLive { uint64_t start_bit, stop_bits, off, bytes, end_bit; uint32_t r
 enum InfpReason { INFP_NONE = 0, INFP_DAMAGED = 1, INFP_REPAIRS = 2, INFP_SINGLE_CHUNK = 3, INFP_FORMAT = 4, INFP_MEMORY = 5 };
 
 // ---- the candidate filter: the 81 bits at a bit offset, lo = bits 0 .. 63, hi = bits 64 .. ----
-// BFINAL = 0 and BTYPE = 2; HLIT <= 29 and HDIST <= 29; the HCLEN + 4 lengths of the code-length code exactly complete by their Kraft sum.
-ZINF_HD bool infp_filter(uint64_t lo, uint64_t hi) {
+// BFINAL = 0 and BTYPE = 2; HLIT <= 29 and HDIST <= 29 (Deflate64: any HDIST, it has 32 distance codes); the HCLEN + 4 lengths of the code-length
+// code exactly complete by their Kraft sum.
+ZINF_HD bool infp_filter(uint64_t lo, uint64_t hi, bool d64 = false) {
   if ((lo & 7u) != 4u) return false;
-  if (((lo >> 3) & 31u) > 29u || ((lo >> 8) & 31u) > 29u) return false;
+  if (((lo >> 3) & 31u) > 29u || (!d64 && ((lo >> 8) & 31u) > 29u)) return false;
   const uint32_t ncl = (uint32_t)((lo >> 13) & 15u) + 4u;
   // the lengths from bit 17 on: 15 of them in lo (bits 17 .. 61), the rest from bit 62
   uint32_t kraft = 0;
@@ -51,8 +59,8 @@ ZINF_HD bool infp_filter(uint64_t lo, uint64_t hi) {
 ZINF_HD bool infp_stop(bool final, uint64_t bitpos, uint64_t stop_bits) { return final || bitpos >= stop_bits; }
 
 // ---- marker arithmetic: base = output position of the chunk's first byte, sp < base = the position a match reads ----
-ZINF_HD uint32_t infp_marker(uint64_t base, uint64_t sp) { return INFP_MARK | (uint32_t)(base - 1u - sp); }
-ZINF_HD uint64_t infp_marker_source(uint64_t base, uint32_t sym) { return base - 1u - (uint64_t)(sym & (INFP_MARK - 1u)); }
+template <int FORMAT = 8> ZINF_HD uint32_t infp_marker(uint64_t base, uint64_t sp) { return InfpFmt<FORMAT>::MARK | (uint32_t)(base - 1u - sp); }
+template <int FORMAT = 8> ZINF_HD uint64_t infp_marker_source(uint64_t base, uint32_t sym) { return base - 1u - (uint64_t)(sym & (InfpFmt<FORMAT>::WINDOW - 1u)); }
 
 // a reader R (zada_inflate_logic.h) that stands at `bit`; Env::reopen (br, byte) opens it at a byte
 template <class R, class Env> ZINF_HD void infp_seek(R &br, Env &env, uint64_t bit) {
@@ -62,19 +70,20 @@ template <class R, class Env> ZINF_HD void infp_seek(R &br, Env &env, uint64_t b
 }
 
 // is a dynamic, non-final block's whole header valid at the reader's position?  (every rule of inf_dynamic_header)
-template <class R> ZINF_HD bool infp_candidate(R &br, InfTables &T, uint32_t lane, uint32_t nl) {
+template <class R> ZINF_HD bool infp_candidate(R &br, InfTables &T, uint32_t lane, uint32_t nl, bool d64 = false) {
   br.need32();
   const uint32_t hdr = (uint32_t)br.hold & 7u;
   br.drop(3);
   if (hdr != 4u) return false;
-  return inf_dynamic_header(br, T, false, lane, nl) == INF_OK && !br.overrun();
+  return inf_dynamic_header(br, T, d64, lane, nl) == INF_OK && !br.overrun();
 }
 
 // Blocks from the reader's position to the first block end where infp_stop says so.  Env takes what they hold:
 //   env.stored (at, len): len bytes of the input from byte `at`; env.token (len, dist, val): a literal `val` (dist = 0, len = 1) or a match;
 //   both return an InfRule; env.reopen (br, byte).
 // Returns the InfRule broken; final: the last block was the stream's.
-template <class R, class Env> ZINF_HD uint32_t infp_blocks(R &br, InfTables &T, uint64_t n_in, uint64_t stop_bits, uint32_t lane, uint32_t nl, Env &env, uint32_t &final) {
+template <class R, class Env> ZINF_HD uint32_t infp_blocks(R &br, InfTables &T, uint64_t n_in, uint64_t stop_bits, uint32_t lane, uint32_t nl, Env &env, uint32_t &final,
+                                                      bool d64 = false) {
   int loaded = INF_TAB_NONE;
   final = 0;
   for (;;) {
@@ -107,12 +116,12 @@ template <class R, class Env> ZINF_HD uint32_t infp_blocks(R &br, InfTables &T, 
         loaded = INF_TAB_FIXED;
       } else {
         loaded = INF_TAB_DYNAMIC;
-        const uint32_t rule = inf_dynamic_header(br, T, false, lane, nl);
+        const uint32_t rule = inf_dynamic_header(br, T, d64, lane, nl);
         if (rule) return rule;
       }
       for (;;) {
         uint32_t a = 0, b = 0;
-        const int32_t k = inf_token(br, T, false, a, b);
+        const int32_t k = inf_token(br, T, d64, a, b);
         if (k < 0) return (uint32_t)-k;
         if (br.overrun()) return INF_R_TRUNCATED;
         if (k == 2) break;

@@ -268,6 +268,7 @@ struct Ctx {
   void *infp = nullptr;                              // parallel Inflate state (zada_inflate_par.hip), made on first use
   int knob_infp_chunk_kib = 64;                      // "inflate_par_chunk_kib": KiB of compressed stream per chunk (4 .. 65 536)
   int knob_infp_repair_pct = 25;                     // "inflate_par_repair_pct": repairs a stream may take, in chunks per hundred (+ INFP_REPAIR_FLOOR)
+  int knob_infp_deflate64 = 0;                       // "inflate_par_deflate64": 1 = the parallel path takes Deflate64 (format 9) streams as well, on 32-bit symbols (4 bytes of workspace per output byte)
   int knob_infp_min_kib = 0;                         // "inflate_par_min_kib": zada_unzip_device sends Deflate entries of at least this many KiB of stream through the parallel path (0 = off)
   void *bzd = nullptr;                               // BZip2 reader state (zada_bunzip2.hip), made on first use
   void *ulz = nullptr;                               // LZMA reader state (zada_unlzma.hip), made on first use

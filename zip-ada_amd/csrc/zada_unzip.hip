@@ -418,17 +418,17 @@ static int uz_group(Ctx *c, UzState *S, const uint8_t *archive, const zada_unzip
   std::vector<ReaderJob> rj;
   std::vector<ReaderRes> rr;
   std::vector<uint32_t> rk;
-  // "inflate_par_min_kib": the large Deflate entries one after the other on many waves each (zada_inflate_par.hip); an entry that path does not
+  // "inflate_par_min_kib": the large Deflate entries (with "inflate_par_deflate64" the Deflate64 ones too) one after the other on many waves each (zada_inflate_par.hip); an entry that path does not
   // take, a damaged one among them, is left to the batch below, whose verdict and error text are the answer
   if (c->knob_infp_min_kib > 0) {
     zada_inflate_par_info sum{}, one{};
     for (uint32_t k = 0; k < n; k++) {
       const zada_unzip_entry &e = ent[idx[k]];
-      if (done[k] || e.method != 8 || uz_payload(e) < ((uint64_t)c->knob_infp_min_kib << 10)) continue;
+      if (done[k] || !(e.method == 8 || (e.method == 9 && c->knob_infp_deflate64)) || uz_payload(e) < ((uint64_t)c->knob_infp_min_kib << 10)) continue;
       zada_unzip_result &R = res[idx[k]];
       uint64_t ol = 0, iu = 0;
       uint32_t reg = R.crc;
-      const int rc = inflate_par_try(c, 8, (const void *)(uintptr_t)src[k], uz_payload(e), (void *)(uintptr_t)out[k], e.cap, &ol, &iu, &reg);
+      const int rc = inflate_par_try(c, (int)e.method, (const void *)(uintptr_t)src[k], uz_payload(e), (void *)(uintptr_t)out[k], e.cap, &ol, &iu, &reg);
       if (rc < 0) return rc;
       inflate_par_record(c, &one, nullptr);
       sum.chunks += one.chunks; sum.live_chunks += one.live_chunks; sum.repairs += one.repairs; sum.scout_rounds += one.scout_rounds;
