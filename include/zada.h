@@ -295,7 +295,16 @@ int zada_inflate_batch(zada_ctx *ctx, int count, const int *format, const uint8_
  * repairs, has fewer than two live chunks, is Deflate64 (format 9) or whose workspace cannot be had runs on zada_inflate_device's one wave
  * instead, with nothing written to d_out before; zada_inflate_par_last says which way the last call went.  Opt-in: no other entry point takes
  * this path unless the knob "inflate_par_min_kib" (0 = off) is set, which sends the Deflate entries of zada_unzip_device whose compressed size
- * is at least that many KiB through it, one after the other.  EXPERIMENTAL: see profiles/inflate_par/NOTES.md for what it gains.
+ * is at least that many KiB through it: one after the other, each with its own launches and synchronisations, or -- with the knob
+ * "inflate_par_batch" (0 or 1, default 0; anything else is ZADA_E_INVALID) at 1 -- all selected entries of a group in the same launches
+ * (DESIGN.md 18.2): one scout launch over the chunks of every stream, one launch per round of repairs for all streams that asked for one, one
+ * decode launch over all live chunks, one window workgroup per stream, one finish launch, and the CRC-32 of all of them through the stored
+ * entries' kernels (k_uz_store / k_uz_fold, sum only).  The longest wave of each step is paid once per pass, not once per entry.  Results,
+ * verdicts and texts per entry are the same either way; so is the record, except scout_rounds, which counts the launches made.  The knob
+ * "inflate_par_batch_mib" (default 8 192; 1 .. 1 048 576, anything else is ZADA_E_INVALID) bounds the symbol workspace one pass may promise
+ * (2 bytes per byte of an entry's cap, Deflate64 4): the selected entries are taken in table order until the next one would pass the bound; an
+ * entry that alone exceeds it is a pass of its own.  With "inflate_par_min_kib" = 0 neither knob does anything.  zada_inflate_par and
+ * zada_inflate_par_device take one stream and are not affected.  EXPERIMENTAL: see profiles/inflate_par/NOTES.md for what it gains.
  * The knob "inflate_par_deflate64" (0 or 1, default 0; anything else is ZADA_E_INVALID): with 1, Deflate64 (format 9) streams take the method
  * too -- in these two calls, and for the method 9 entries of zada_unzip_device that "inflate_par_min_kib" selects --, with every other reason
  * to hand the stream to the one wave unchanged.  A Deflate64 marker's offset takes 16 bits (its window is 65 536), so its symbols have 32 bits:

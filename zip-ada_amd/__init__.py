@@ -348,6 +348,8 @@ class Encoder:
 
     def set_knob(self, name, value):
         """Tuning / test knobs ("budget", "max_demand_rounds", "inner_budget", "shard_kib", "span_mib", "batch_mib", "bunzip_batch_mib", "inflate_par_chunk_kib", "inflate_par_repair_pct", "inflate_par_min_kib", "inflate_par_deflate64"); none changes a byte of output.
+        "inflate_par_batch" = 1: the entries "inflate_par_min_kib" selects in a group of unzip_device go through the same launches instead of one after the other (UnZip (..., parallel_batch=True)
+        sets it around its call); "inflate_par_batch_mib" (default 8 192, 1 .. 1 048 576): MiB of symbol workspace one pass of that may promise.
         "inflate_par_deflate64" = 1: inflate_par* and unzip_device's parallel path take Deflate64 (format 9) streams too (UnZip (..., parallel_deflate64=True) sets it around its calls).
         "unzip_legacy" = 1: unzip_device, compzip_device and findzip_device know methods 1 .. 6 (UnZip / CompZip / FindZip set it around their calls).
         "zip_legacy" = 1: zip_device_ex takes Shrink_1 and Reduce_1 .. _4, rezip_device the approaches shrink and reduce_4 (legacy=True sets it around the calls).
@@ -1781,6 +1783,9 @@ class UnZip:
     "inflate_par_min_kib" around its call (Encoder.inflate_par_last then holds the sums).  Results, exceptions and texts are the default's.
     With parallel_deflate64=True as well, Deflate64 entries of that size go the same way (the knob "inflate_par_deflate64", set around the calls
     and put back; 4 bytes of workspace per output byte where Deflate takes 2).
+    With parallel_batch=True as well -- experimental too -- extract_device sets the knob "inflate_par_batch" around its call and puts it back: the
+    entries parallel_inflate selects then share their launches instead of running one after the other, which is what an archive of many entries
+    of some MiB wants (README, "Parallel Inflate, batched").  extract on host bytes ignores it: that path calls inflate_par entry by entry.
     UnZip (encoder, legacy=True) also decodes Shrink (1), Reduce (2 .. 5) and Implode (6) entries: all of a call through ONE unlegacy_batch (one wave
     per entry; an Implode entry's general-purpose bits 1 and 2 say how it was written); extract_device sets the knob "unzip_legacy" around its call.
     Without legacy=True they are UnsupportedMethod, in the words of before."""
@@ -1788,7 +1793,7 @@ class UnZip:
     _NAMES = {1: "Shrink", 2: "Reduce_1", 3: "Reduce_2", 4: "Reduce_3", 5: "Reduce_4", 6: "Implode", 12: "BZip2", 14: "LZMA", 98: "PPMd", 99: "AES"}
     _STREAMS = {1: "Shrink", 2: "Reduce", 3: "Reduce", 4: "Reduce", 5: "Reduce", 6: "Implode", 8: "Deflate", 9: "Deflate64", 12: "BZip2", 14: "LZMA"}
 
-    def __init__(self, encoder, bzip2=False, lzma=False, parallel_inflate=None, legacy=False, parallel_deflate64=False):
+    def __init__(self, encoder, bzip2=False, lzma=False, parallel_inflate=None, legacy=False, parallel_deflate64=False, parallel_batch=False):
         self.enc = encoder
         self.bzip2 = bool(bzip2)
         self.lzma = bool(lzma)
@@ -1799,6 +1804,9 @@ class UnZip:
         if parallel_deflate64 and self.parallel_inflate is None:
             raise ZadaError("UnZip: parallel_deflate64 needs parallel_inflate, the size in KiB from which an entry goes the parallel way")
         self.parallel_deflate64 = bool(parallel_deflate64)
+        if parallel_batch and self.parallel_inflate is None:
+            raise ZadaError("UnZip: parallel_batch needs parallel_inflate, the size in KiB from which an entry goes the parallel way")
+        self.parallel_batch = bool(parallel_batch)
         self.last_parallel = []                            # extract: (name, inflate_par_last ()) of the entries that went through inflate_par
 
     def _unsupported(self, e):
@@ -1920,6 +1928,16 @@ class UnZip:
             return back
         self.enc.set_knob("inflate_par_deflate64", back)
 
+    def _batch_knob(self, back=None):
+        """parallel_batch=True: sets the knob "inflate_par_batch" and returns the value it had; with that value, puts it back."""
+        if not self.parallel_batch:
+            return None
+        if back is None:
+            back = getattr(self.enc, "_knobs_set", {}).get("inflate_par_batch", 0)
+            self.enc.set_knob("inflate_par_batch", 1)
+            return back
+        self.enc.set_knob("inflate_par_batch", back)
+
     def extract_device(self, info, what=None, password=None, test_only=False, errors="raise"):
         """extract for an archive that lies in device memory: info is a ZipInfo.load_device of a tensor on the encoder's device.  Returns
         {name: torch.uint8 tensor} -- views of ONE output tensor, every entry at a multiple of 256 bytes --, with what, password, test_only, errors, the
@@ -1968,6 +1986,7 @@ class UnZip:
             if self.parallel_inflate is not None:
                 self.enc.set_knob("inflate_par_min_kib", self.parallel_inflate)
             was = self._deflate64_knob()
+            was_batch = self._batch_knob()
             if self.legacy:
                 self.enc.set_knob("unzip_legacy", 1)
             try:
@@ -1976,6 +1995,7 @@ class UnZip:
                 if self.parallel_inflate is not None:
                     self.enc.set_knob("inflate_par_min_kib", 0)
                 self._deflate64_knob(was)
+                self._batch_knob(was_batch)
                 if self.legacy:
                     self.enc.set_knob("unzip_legacy", 0)
             good = (r["rc"] == 0) & (r["out_len"] == usize) & ((r["crc"] ^ np.uint32(0xFFFFFFFF)) == col(lambda e: e.crc, np.uint32))

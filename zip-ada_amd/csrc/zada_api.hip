@@ -1143,6 +1143,8 @@ int zada_set_knob(zada_ctx *z, const char *name, int value) {
   else if (!strcmp(name, "inflate_par_chunk_kib")) { if (value < 4 || value > 65536) return ZADA_E_INVALID; z->c.knob_infp_chunk_kib = value; }
   else if (!strcmp(name, "inflate_par_repair_pct")) { if (value < 0 || value > 100) return ZADA_E_INVALID; z->c.knob_infp_repair_pct = value; }
   else if (!strcmp(name, "inflate_par_deflate64")) { if (value < 0 || value > 1) return ZADA_E_INVALID; z->c.knob_infp_deflate64 = value; }
+  else if (!strcmp(name, "inflate_par_batch")) { if (value < 0 || value > 1) return ZADA_E_INVALID; z->c.knob_infp_batch = value; }
+  else if (!strcmp(name, "inflate_par_batch_mib")) { if (value < 1 || value > 1048576) return ZADA_E_INVALID; z->c.knob_infp_batch_mib = value; }
   else if (!strcmp(name, "inflate_par_min_kib")) { if (value < 0) return ZADA_E_INVALID; z->c.knob_infp_min_kib = value; }
   else if (!strcmp(name, "unzip_piece")) { if (value < 8 || value > 14) return ZADA_E_INVALID; z->c.knob_unzip_piece = value; }
   else if (!strcmp(name, "atoms_pct")) { if (value < 1 || value > 100) return ZADA_E_INVALID; z->c.knob_atoms_pct = value; z->c.ws.cap_atoms = 0; }   // (the next call books the entropy workspace anew)

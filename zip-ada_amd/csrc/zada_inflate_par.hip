@@ -8,6 +8,9 @@
 //   k_infp_window: one workgroup, the live chunks in order: the markers in the last 32 KiB (Deflate64: 64 KiB) of each chunk become symbols.
 //   k_infp_finish: symbols to bytes in d_out, all chunks in parallel.
 //   CRC-32       : the encoder's k_crc_chunks / k_crc_fold (crc_launch / crc_finish), the bytes before d_out's first 16-byte boundary on the host.
+// The batch forms k_infpb_* ("inflate_par_batch") do the same over a table of streams: the large entries of one zada_unzip_device
+// group share every launch -- a wave per (stream, chunk) job, a wave per live row, a window workgroup per stream -- by the plan of
+// zada_inflate_par_batch_plan.h; their CRC-32 goes through the stored entries' k_uz_store / k_uz_fold (unzip_sum_entries).
 // A stream the method does not take (damaged, too many repairs, one live chunk, Deflate64 without its knob, no memory) is decoded by
 // zada_inflate_device's one wave, whose verdict is the answer; nothing has been written to d_out before that.
 #include <hip/hip_runtime.h>
@@ -19,6 +22,7 @@
 #include "../../include/zada.h"
 #include "zada_internal.h"
 #include "zada_inflate_par_logic.h"
+#include "zada_inflate_par_batch_plan.h"
 #include "zada_inflate_wave.h"
 
 struct zada_ctx { zada::Ctx c; };
@@ -92,21 +96,17 @@ template <int FORMAT> struct InfpDecodeEnv : InfpWaveEnvBase {
   }
 };
 
-template <bool D64> __global__ void __launch_bounds__(INF_WAVE) k_infp_scout(const uint8_t *in_, uint64_t n_in, uint64_t chunk_bytes, const InfpJob *__restrict__ jobs,
-                                                                             uint32_t njobs, InfpRec *recs) {
-  __shared__ InfTables T;
-  __shared__ uint32_t stage[INF_STAGE / 4 + 2];
+// ---- what a wave does with one chunk, one workgroup with one stream's live rows: shared by the kernels of one stream and their batch forms ----
+// scout: the chunk `chunk` of the stream (in, n_in), bit positions the stream's own; start_bit exact or INFP_SEARCH
+template <bool D64> __device__ __forceinline__ InfpRec infp_scout_chunk(gcu8 *in, uint64_t n_in, uint64_t chunk_bytes, uint32_t chunk, uint64_t start_bit, InfTables &T, uint32_t *stage) {
   const uint32_t lane = threadIdx.x;
-  if (blockIdx.x >= njobs) return;
-  const InfpJob J = jobs[blockIdx.x];
-  gcu8 *in = (gcu8 *)in_;
-  const uint64_t lo_bit = (uint64_t)J.chunk * chunk_bytes * 8, total_bits = n_in * 8;
+  const uint64_t lo_bit = (uint64_t)chunk * chunk_bytes * 8, total_bits = n_in * 8;
   const uint64_t stop_bits = lo_bit + chunk_bytes * 8;
   const uint64_t hi_bit = stop_bits < total_bits ? stop_bits : total_bits;
   InfpCountEnv env;
   env.in = in; env.n_in = n_in; env.stage = stage; env.bytes = 0;
   InfWaveReader br;
-  uint64_t start = J.start_bit;
+  uint64_t start = start_bit;
   bool found = start != INFP_SEARCH;
   if (!found) {
     // ---- find: 64 bit offsets per step; every lane takes the 96 bits at its offset from the stage ----
@@ -129,7 +129,7 @@ template <bool D64> __global__ void __launch_bounds__(INF_WAVE) k_infp_scout(con
     }
   }
   InfpRec R;
-  R.start_bit = found ? start : 0; R.end_bit = 0; R.bytes = 0; R.flags = (found ? INFP_F_FOUND : 0u) | (J.start_bit != INFP_SEARCH ? INFP_F_EXACT : 0u); R.rule = 0;
+  R.start_bit = found ? start : 0; R.end_bit = 0; R.bytes = 0; R.flags = (found ? INFP_F_FOUND : 0u) | (start_bit != INFP_SEARCH ? INFP_F_EXACT : 0u); R.rule = 0;
   if (found) {
     // ---- count ----
     infp_seek(br, env, start);
@@ -138,33 +138,30 @@ template <bool D64> __global__ void __launch_bounds__(INF_WAVE) k_infp_scout(con
     R.end_bit = br.used_bits(); R.bytes = env.bytes;
     if (final) R.flags |= INFP_F_FINAL;
   }
-  if (lane == 0) recs[J.chunk] = R;
+  return R;
 }
 
-template <int FORMAT> __global__ void __launch_bounds__(INF_WAVE) k_infp_decode(const uint8_t *in_, uint64_t n_in, InfpLive *live, uint32_t nlive,
-                                                                                typename InfpFmt<FORMAT>::sym_t *sym_) {
-  __shared__ InfTables T;
-  __shared__ uint32_t stage[INF_STAGE / 4 + 2];
-  const uint32_t lane = threadIdx.x;
-  if (blockIdx.x >= nlive) return;
-  const InfpLive J = live[blockIdx.x];
+// decode: one live chunk from start_bit into the symbols sym [off, off + bytes) of its stream; -> the rule broken, end_bit and final as found
+template <int FORMAT> __device__ __forceinline__ uint32_t infp_decode_chunk(gcu8 *in, uint64_t n_in, uint64_t start_bit, uint64_t stop_bits, uint64_t off, uint64_t bytes,
+                                                                            typename InfpFmt<FORMAT>::sym_t *sym_, InfTables &T, uint32_t *stage, uint64_t &end_bit, uint32_t &final) {
   InfpDecodeEnv<FORMAT> env;
-  env.in = (gcu8 *)in_; env.n_in = n_in; env.stage = stage;
+  env.in = in; env.n_in = n_in; env.stage = stage;
   env.sym = (__attribute__((address_space(1))) typename InfpFmt<FORMAT>::sym_t *)sym_;
-  env.base = J.off; env.limit = J.off + J.bytes; env.pos = env.qpos = J.off; env.fence_pos = J.off;
+  env.base = off; env.limit = off + bytes; env.pos = env.qpos = off; env.fence_pos = off;
   env.q = 0; env.my_len = env.my_dist = env.my_val = 0;
   InfWaveReader br;
-  infp_seek(br, env, J.start_bit);
-  uint32_t final = 0;
-  uint32_t rule = infp_blocks(br, T, n_in, J.stop_bits, lane, INF_WAVE, env, final, InfpFmt<FORMAT>::D64);
+  infp_seek(br, env, start_bit);
+  final = 0;
+  uint32_t rule = infp_blocks(br, T, n_in, stop_bits, threadIdx.x, INF_WAVE, env, final, InfpFmt<FORMAT>::D64);
   if (!rule) env.flush();
   if (!rule && env.pos != env.limit) rule = INF_R_OUTPUT_FULL;          // (not what the count saw: the stream goes to the one-wave decoder)
-  if (lane == 0) { live[blockIdx.x].end_bit = br.used_bits(); live[blockIdx.x].rule = rule; live[blockIdx.x].final = final; }
+  end_bit = br.used_bits();
+  return rule;
 }
 
+// window: one workgroup walks the live rows live [1 .. nlive) of ONE stream in order; Row: InfpLive or InfpbLive.  -> the markers this thread resolved
 constexpr uint32_t INFP_WIN_THREADS = 1024, INFP_WIN_PIECE = 32768, INFP_WIN_DONE = 0x40000000u;      // (the flag of a resolved symbol: no bit of either marker layout)
-template <int FORMAT> __global__ void __launch_bounds__(INFP_WIN_THREADS) k_infp_window(const InfpLive *__restrict__ live, uint32_t nlive,
-                                                                                        typename InfpFmt<FORMAT>::sym_t *sym, uint64_t *markers) {
+template <int FORMAT, class Row> __device__ __forceinline__ uint32_t infp_window_walk(const Row *__restrict__ live, uint32_t nlive, typename InfpFmt<FORMAT>::sym_t *sym) {
   typedef typename InfpFmt<FORMAT>::sym_t sym_t;
   constexpr uint32_t WINDOW = InfpFmt<FORMAT>::WINDOW, MARK = InfpFmt<FORMAT>::MARK, PER = INFP_WIN_PIECE / INFP_WIN_THREADS;
   uint32_t mine = 0;
@@ -193,15 +190,13 @@ template <int FORMAT> __global__ void __launch_bounds__(INFP_WIN_THREADS) k_infp
     }
     __syncthreads();            // the next chunk reads what this one resolved
   }
-  if (mine) atomicAdd((unsigned long long *)markers, (unsigned long long)mine);
+  return mine;
 }
 
+// finish: the symbols [base, base + bytes) of one live row to bytes, the pieces blockIdx.y, blockIdx.y + gridDim.y, ... of it; out [0] is the
+// stream's first byte, at any alignment: byte stores, so that two streams' adjacent ranges never share a store
 constexpr uint32_t INFP_FIN_THREADS = 256, INFP_FIN_PIECE = 16384;
-template <int FORMAT> __global__ void __launch_bounds__(INFP_FIN_THREADS) k_infp_finish(const InfpLive *__restrict__ live, uint32_t nlive,
-                                                                                        const typename InfpFmt<FORMAT>::sym_t *__restrict__ sym, uint8_t *out, uint64_t *markers) {
-  const uint32_t j = blockIdx.x;
-  if (j >= nlive) return;
-  const uint64_t base = live[j].off, bytes = live[j].bytes;
+template <int FORMAT> __device__ __forceinline__ uint32_t infp_finish_row(uint64_t base, uint64_t bytes, const typename InfpFmt<FORMAT>::sym_t *__restrict__ sym, uint8_t *out) {
   uint32_t mine = 0;
   for (uint64_t p0 = (uint64_t)blockIdx.y * INFP_FIN_PIECE; p0 < bytes; p0 += (uint64_t)gridDim.y * INFP_FIN_PIECE) {
     const uint64_t p1 = p0 + INFP_FIN_PIECE < bytes ? p0 + INFP_FIN_PIECE : bytes;
@@ -211,6 +206,91 @@ template <int FORMAT> __global__ void __launch_bounds__(INFP_FIN_THREADS) k_infp
       out[i] = (uint8_t)v;
     }
   }
+  return mine;
+}
+
+// ---- one stream ----
+template <bool D64> __global__ void __launch_bounds__(INF_WAVE) k_infp_scout(const uint8_t *in_, uint64_t n_in, uint64_t chunk_bytes, const InfpJob *__restrict__ jobs,
+                                                                             uint32_t njobs, InfpRec *recs) {
+  __shared__ InfTables T;
+  __shared__ uint32_t stage[INF_STAGE / 4 + 2];
+  if (blockIdx.x >= njobs) return;
+  const InfpJob J = jobs[blockIdx.x];
+  const InfpRec R = infp_scout_chunk<D64>((gcu8 *)in_, n_in, chunk_bytes, J.chunk, J.start_bit, T, stage);
+  if (threadIdx.x == 0) recs[J.chunk] = R;
+}
+
+template <int FORMAT> __global__ void __launch_bounds__(INF_WAVE) k_infp_decode(const uint8_t *in_, uint64_t n_in, InfpLive *live, uint32_t nlive,
+                                                                                typename InfpFmt<FORMAT>::sym_t *sym_) {
+  __shared__ InfTables T;
+  __shared__ uint32_t stage[INF_STAGE / 4 + 2];
+  if (blockIdx.x >= nlive) return;
+  const InfpLive J = live[blockIdx.x];
+  uint64_t end_bit;
+  uint32_t final;
+  const uint32_t rule = infp_decode_chunk<FORMAT>((gcu8 *)in_, n_in, J.start_bit, J.stop_bits, J.off, J.bytes, sym_, T, stage, end_bit, final);
+  if (threadIdx.x == 0) { live[blockIdx.x].end_bit = end_bit; live[blockIdx.x].rule = rule; live[blockIdx.x].final = final; }
+}
+
+template <int FORMAT> __global__ void __launch_bounds__(INFP_WIN_THREADS) k_infp_window(const InfpLive *__restrict__ live, uint32_t nlive,
+                                                                                        typename InfpFmt<FORMAT>::sym_t *sym, uint64_t *markers) {
+  const uint32_t mine = infp_window_walk<FORMAT>(live, nlive, sym);
+  if (mine) atomicAdd((unsigned long long *)markers, (unsigned long long)mine);
+}
+
+template <int FORMAT> __global__ void __launch_bounds__(INFP_FIN_THREADS) k_infp_finish(const InfpLive *__restrict__ live, uint32_t nlive,
+                                                                                        const typename InfpFmt<FORMAT>::sym_t *__restrict__ sym, uint8_t *out, uint64_t *markers) {
+  const uint32_t j = blockIdx.x;
+  if (j >= nlive) return;
+  const uint32_t mine = infp_finish_row<FORMAT>(live[j].off, live[j].bytes, sym, out);
+  if (mine) atomicAdd((unsigned long long *)markers, (unsigned long long)mine);
+}
+
+// ---- the batch forms ("inflate_par_batch"): the same work over a table of streams (zada_inflate_par_batch_plan.h) ----
+// scout: one wave per job = (stream, chunk, start); the record goes to the chunk's global index, and to back [job] where the host asks for the
+// records of a repair round alone
+template <bool D64> __global__ void __launch_bounds__(INF_WAVE) k_infpb_scout(const InfpbStream *__restrict__ streams, uint64_t chunk_bytes, const InfpbJob *__restrict__ jobs,
+                                                                              uint32_t njobs, InfpRec *recs, InfpRec *back) {
+  __shared__ InfTables T;
+  __shared__ uint32_t stage[INF_STAGE / 4 + 2];
+  if (blockIdx.x >= njobs) return;
+  const InfpbJob J = jobs[blockIdx.x];
+  const InfpbStream S = streams[J.stream];
+  const InfpRec R = infp_scout_chunk<D64>((gcu8 *)S.in, S.n_in, chunk_bytes, J.chunk - S.first, J.start_bit, T, stage);
+  if (threadIdx.x == 0) { recs[J.chunk] = R; if (back) back[blockIdx.x] = R; }
+}
+
+// decode: one wave per live row; off / bytes are positions in the stream's own output, the symbols lie from the stream's base on
+template <int FORMAT> __global__ void __launch_bounds__(INF_WAVE) k_infpb_decode(const InfpbStream *__restrict__ streams, InfpbLive *live, uint32_t nlive,
+                                                                                 typename InfpFmt<FORMAT>::sym_t *sym_) {
+  __shared__ InfTables T;
+  __shared__ uint32_t stage[INF_STAGE / 4 + 2];
+  if (blockIdx.x >= nlive) return;
+  const InfpbLive J = live[blockIdx.x];
+  const InfpbStream S = streams[J.stream];
+  uint64_t end_bit;
+  uint32_t final;
+  const uint32_t rule = infp_decode_chunk<FORMAT>((gcu8 *)S.in, S.n_in, J.start_bit, J.stop_bits, J.off, J.bytes, sym_ + S.sym, T, stage, end_bit, final);
+  if (threadIdx.x == 0) { live[blockIdx.x].end_bit = end_bit; live[blockIdx.x].rule = rule; live[blockIdx.x].final = final; }
+}
+
+// window: one workgroup per stream, the streams' walks independent of one another (n_live = 0: the stream left after the decode)
+template <int FORMAT> __global__ void __launch_bounds__(INFP_WIN_THREADS) k_infpb_window(const InfpbStream *__restrict__ streams, uint32_t nstreams, const InfpbLive *__restrict__ live,
+                                                                                         typename InfpFmt<FORMAT>::sym_t *sym, uint64_t *markers) {
+  if (blockIdx.x >= nstreams) return;
+  const InfpbStream S = streams[blockIdx.x];
+  const uint32_t mine = infp_window_walk<FORMAT>(live + S.first_live, S.n_live, sym + S.sym);
+  if (mine) atomicAdd((unsigned long long *)markers, (unsigned long long)mine);
+}
+
+// finish: all live rows of the streams that stayed, in parallel, each into its stream's own output range
+template <int FORMAT> __global__ void __launch_bounds__(INFP_FIN_THREADS) k_infpb_finish(const InfpbStream *__restrict__ streams, const InfpbLive *__restrict__ live, uint32_t nlive,
+                                                                                         const typename InfpFmt<FORMAT>::sym_t *__restrict__ sym, uint64_t *markers) {
+  const uint32_t j = blockIdx.x;
+  if (j >= nlive) return;
+  const InfpbStream S = streams[live[j].stream];
+  if (!S.n_live) return;
+  const uint32_t mine = infp_finish_row<FORMAT>(live[j].off, live[j].bytes, sym + S.sym, (uint8_t *)S.out);
   if (mine) atomicAdd((unsigned long long *)markers, (unsigned long long)mine);
 }
 
@@ -370,6 +450,141 @@ int inflate_par_try(Ctx *c, int format, const void *d_in, uint64_t n_in, void *d
   if (out_len) *out_len = total;
   if (in_used) *in_used = (recs[W.last].end_bit + 7) / 8;
   if (crc_inout) *crc_inout = reg;
+  return 0;
+}
+
+// ---- the batch ("inflate_par_batch"): the plan of zada_inflate_par_batch_plan.h between the launches of the k_infpb_* kernels ----
+template <int FORMAT> static void infpb_launch_decode(hipStream_t st, const InfpbStream *d_str, InfpbLive *d_live, uint32_t nl, void *sym) {
+  hipLaunchKernelGGL(k_infpb_decode<FORMAT>, dim3(nl), dim3(INF_WAVE), 0, st, d_str, d_live, nl, (typename InfpFmt<FORMAT>::sym_t *)sym);
+}
+template <int FORMAT> static void infpb_launch_resolve(Ctx *c, hipStream_t st, const InfpbStream *d_str, uint32_t ns, const InfpbLive *d_live, uint32_t nl, void *sym, uint64_t *d_mark) {
+  typedef typename InfpFmt<FORMAT>::sym_t sym_t;
+  hipLaunchKernelGGL(k_infpb_window<FORMAT>, dim3(ns), dim3(INFP_WIN_THREADS), 0, st, d_str, ns, d_live, (sym_t *)sym, d_mark);
+  c->tmark("inflate_par_batch:k_infpb_window");
+  hipLaunchKernelGGL(k_infpb_finish<FORMAT>, dim3(nl, 8), dim3(INFP_FIN_THREADS), 0, st, d_str, d_live, nl, (const sym_t *)sym, d_mark);
+  c->tmark("inflate_par_batch:k_infpb_finish");
+}
+
+// One sub-pass: the streams rows [idx [..]] (one format, two chunks or more each).  It synchronises after the scout, after each repair round, after
+// the decode and once at the end (inside unzip_sum_entries).  0, or < 0: a HIP error
+static int infpb_sub(Ctx *c, InfpState *S, const InfpbIn *rows, InfpbRes *res, const std::vector<uint32_t> &idx, uint32_t format, uint64_t chunk_bytes, zada_inflate_par_info &I) {
+  hipStream_t st = c->stream;
+  const bool d64 = format == 9;
+  InfpbSub B;
+  std::vector<InfpbJob> jobs;
+  std::vector<InfpbStream> streams;
+  std::vector<InfpbLive> lives;
+  auto leave = [&]() { infpb_results(B, res); I.scout_rounds += B.launches; return 0; };
+  if (!infpb_begin(B, rows, idx, format, chunk_bytes, (uint32_t)c->knob_infp_repair_pct, jobs)) return leave();
+  const uint32_t ns = (uint32_t)idx.size(), nch = (uint32_t)B.nchunks;
+  // the tables: streams [ns], jobs [nch], records [nch], a round's records [ns] (a stream has one pending job at the most), live rows [nch], the marker counter
+  auto up = [](uint64_t v) { return (v + 255) & ~255ull; };
+  const uint64_t o_str = 0, o_jobs = o_str + up((uint64_t)ns * sizeof(InfpbStream)), o_recs = o_jobs + up((uint64_t)nch * sizeof(InfpbJob)),
+                 o_back = o_recs + up((uint64_t)nch * sizeof(InfpRec)), o_live = o_back + up((uint64_t)ns * sizeof(InfpRec)), o_mark = o_live + up((uint64_t)nch * sizeof(InfpbLive)),
+                 total_tabs = o_mark + 16;
+  if (!infp_grow(c, (void **)&S->tabs, &S->cap_tabs, total_tabs)) { infpb_drop(B, INFP_MEMORY); return leave(); }
+  const InfpbStream *d_str = (const InfpbStream *)(S->tabs + o_str);
+  InfpbLive *d_live = (InfpbLive *)(S->tabs + o_live);
+  uint64_t *d_mark = (uint64_t *)(S->tabs + o_mark);
+  streams.resize(ns);
+  for (uint32_t s = 0; s < ns; s++) { const InfpbIn &R = rows[B.st[s].row]; streams[s] = InfpbStream{R.in, R.n_in, R.out, 0, B.st[s].first, 0, 0, 0}; }
+  hipMemcpyAsync(S->tabs + o_str, streams.data(), (size_t)ns * sizeof(InfpbStream), hipMemcpyHostToDevice, st);
+  hipMemcpyAsync(S->tabs + o_jobs, jobs.data(), (size_t)nch * sizeof(InfpbJob), hipMemcpyHostToDevice, st);
+  auto scout = [&](uint32_t njobs, InfpRec *d_back) {
+    hipLaunchKernelGGL(d64 ? k_infpb_scout<true> : k_infpb_scout<false>, dim3(njobs), dim3(INF_WAVE), 0, st, d_str, chunk_bytes, (const InfpbJob *)(S->tabs + o_jobs), njobs,
+                       (InfpRec *)(S->tabs + o_recs), d_back);
+  };
+  scout(nch, nullptr);
+  c->tmark("inflate_par_batch:k_infpb_scout");
+  hipMemcpyAsync(B.recs.data(), S->tabs + o_recs, (size_t)nch * sizeof(InfpRec), hipMemcpyDeviceToHost, st);
+  if (hip_check(c, hipGetLastError(), "inflate_par_batch scout launch") || hip_check(c, hipStreamSynchronize(st), "inflate_par_batch scout")) return ZADA_E_HIP_;
+  B.launches = 1;
+  // the chain in rounds: the one pending repair of every stream that asked for one in the same launch, exactly those records back
+  std::vector<InfpRec> back(ns);
+  for (;;) {
+    infpb_round(B, rows, jobs);
+    const uint32_t nj = (uint32_t)jobs.size();
+    if (!nj) break;
+    hipMemcpyAsync(S->tabs + o_jobs, jobs.data(), (size_t)nj * sizeof(InfpbJob), hipMemcpyHostToDevice, st);
+    scout(nj, (InfpRec *)(S->tabs + o_back));
+    hipMemcpyAsync(back.data(), S->tabs + o_back, (size_t)nj * sizeof(InfpRec), hipMemcpyDeviceToHost, st);
+    if (hip_check(c, hipGetLastError(), "inflate_par_batch repair launch") || hip_check(c, hipStreamSynchronize(st), "inflate_par_batch repair")) return ZADA_E_HIP_;
+    B.launches++;
+    for (uint32_t j = 0; j < nj; j++) B.recs[jobs[j].chunk] = back[j];
+  }
+  c->tmark("inflate_par_batch:chain");
+  const uint64_t nsym = infpb_tables(B, rows, streams, lives);
+  const uint32_t nsl = (uint32_t)streams.size(), nl = (uint32_t)lives.size();
+  if (!nsl) return leave();
+  if (nsym && !infp_grow(c, &S->sym, &S->cap_sym, nsym * infpb_sym_bytes(format))) { infpb_drop(B, INFP_MEMORY); return leave(); }
+  // (from here on the stream table holds the chained streams alone, in order: a live row's `stream` is its row of this table, InfpbState::slot)
+  hipMemcpyAsync(S->tabs + o_str, streams.data(), (size_t)nsl * sizeof(InfpbStream), hipMemcpyHostToDevice, st);
+  hipMemcpyAsync(d_live, lives.data(), (size_t)nl * sizeof(InfpbLive), hipMemcpyHostToDevice, st);
+  hipMemsetAsync(d_mark, 0, 16, st);
+  std::vector<InfpbLive> got(nl);
+  if (d64) infpb_launch_decode<9>(st, d_str, d_live, nl, S->sym); else infpb_launch_decode<8>(st, d_str, d_live, nl, S->sym);
+  c->tmark("inflate_par_batch:k_infpb_decode");
+  hipMemcpyAsync(got.data(), d_live, (size_t)nl * sizeof(InfpbLive), hipMemcpyDeviceToHost, st);
+  if (hip_check(c, hipGetLastError(), "inflate_par_batch decode launch") || hip_check(c, hipStreamSynchronize(st), "inflate_par_batch decode")) return ZADA_E_HIP_;
+  // a stream with a row that is not what the count saw leaves before a byte of it is written
+  const uint32_t left = infpb_compare(B, got, streams);
+  if (left == nsl) return leave();
+  if (left) hipMemcpyAsync(S->tabs + o_str, streams.data(), (size_t)nsl * sizeof(InfpbStream), hipMemcpyHostToDevice, st);
+  if (nsym) {
+    if (d64) infpb_launch_resolve<9>(c, st, d_str, nsl, d_live, nl, S->sym, d_mark); else infpb_launch_resolve<8>(c, st, d_str, nsl, d_live, nl, S->sym, d_mark);
+  }
+  uint64_t marks = 0;
+  hipMemcpyAsync(&marks, d_mark, 8, hipMemcpyDeviceToHost, st);
+  if (hip_check(c, hipGetLastError(), "inflate_par_batch finish launch")) return ZADA_E_HIP_;
+  // the CRC-32 of every stream that stayed: k_uz_store / k_uz_fold over the bytes in place, parallel inside a stream, one synchronisation for all
+  std::vector<uint64_t> at, len;
+  std::vector<uint32_t> reg, who;
+  for (const InfpbState &T : B.st) {
+    if (T.state != INFPB_CHAINED) continue;
+    res[T.row].crc = rows[T.row].crc;
+    if (!T.W.total) continue;
+    at.push_back(rows[T.row].out); len.push_back(T.W.total); reg.push_back(rows[T.row].crc); who.push_back(T.row);
+  }
+  if (at.empty()) { if (hip_check(c, hipStreamSynchronize(st), "inflate_par_batch finish")) return ZADA_E_HIP_; }
+  else {
+    const int rc = unzip_sum_entries(c, (uint32_t)at.size(), at.data(), len.data(), reg.data());
+    if (rc) return rc < 0 ? rc : ZADA_E_HIP_;
+    for (size_t k = 0; k < who.size(); k++) res[who[k]].crc = reg[k];
+  }
+  c->tmark("inflate_par_batch:crc");
+  I.marker_bytes += marks;
+  return leave();
+}
+
+// The selected entries of one zada_unzip_device group (formats 8 and, where the knob allows them, 9).  res [k].taken: entry k is done; otherwise
+// nothing was written to its output range and its register is untouched: the one-wave batch decodes it.  0, or < 0: an error
+int inflate_par_batch(Ctx *c, uint32_t n, const InfpbIn *rows, InfpbRes *res) {
+  InfpState *S = infp_state(c);
+  if (!S) { c->err = "inflate_par: no memory for the state"; return ZADA_E_NOMEM; }
+  zada_inflate_par_info I;
+  memset(&I, 0, sizeof I);
+  const uint64_t chunk_bytes = (uint64_t)c->knob_infp_chunk_kib << 10;
+  for (uint32_t k = 0; k < n; k++) {
+    res[k] = InfpbRes{0, 0, infpb_chunks(rows[k].n_in, chunk_bytes), 0, 0, rows[k].crc, 0, INFP_SINGLE_CHUNK, 0};      // (what a stream of one chunk leaves; the others: infpb_results)
+  }
+  std::vector<uint32_t> ends, idx;
+  infpb_passes(rows, n, (uint64_t)c->knob_infp_batch_mib << 20, ends);
+  c->tmark("inflate_par_batch:begin");
+  uint32_t p0 = 0;
+  for (uint32_t p1 : ends) {
+    for (uint32_t format = 8; format <= 9; format++) {
+      idx.clear();
+      for (uint32_t k = p0; k < p1; k++) if (rows[k].format == format && res[k].chunks >= 2) idx.push_back(k);
+      if (idx.empty()) continue;
+      const int rc = infpb_sub(c, S, rows, res, idx, format, chunk_bytes, I);
+      if (rc < 0) return rc;
+    }
+    p0 = p1;
+  }
+  uint64_t sum[6];
+  infpb_sum(res, n, sum);
+  I.chunks = sum[0]; I.live_chunks = sum[1]; I.repairs = sum[2]; I.fell_back = (int32_t)sum[3]; I.reason = (int32_t)sum[4]; I.streams = sum[5];
+  S->last = I;
   return 0;
 }
 

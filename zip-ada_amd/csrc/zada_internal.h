@@ -269,6 +269,8 @@ struct Ctx {
   int knob_infp_chunk_kib = 64;                      // "inflate_par_chunk_kib": KiB of compressed stream per chunk (4 .. 65 536)
   int knob_infp_repair_pct = 25;                     // "inflate_par_repair_pct": repairs a stream may take, in chunks per hundred (+ INFP_REPAIR_FLOOR)
   int knob_infp_deflate64 = 0;                       // "inflate_par_deflate64": 1 = the parallel path takes Deflate64 (format 9) streams as well, on 32-bit symbols (4 bytes of workspace per output byte)
+  int knob_infp_batch = 0;                           // "inflate_par_batch": 1 = the entries "inflate_par_min_kib" selects in a group of zada_unzip_device share their launches (zada_inflate_par_batch_plan.h); 0 = one after the other
+  int knob_infp_batch_mib = 8192;                    // "inflate_par_batch_mib": MiB of symbol workspace one pass of the batched path may promise (1 .. 1 048 576)
   int knob_infp_min_kib = 0;                         // "inflate_par_min_kib": zada_unzip_device sends Deflate entries of at least this many KiB of stream through the parallel path (0 = off)
   void *bzd = nullptr;                               // BZip2 reader state (zada_bunzip2.hip), made on first use
   void *ulz = nullptr;                               // LZMA reader state (zada_unlzma.hip), made on first use
@@ -360,6 +362,11 @@ int inflate_crc_entries(Ctx *c, uint32_t E, const uint64_t *out, const uint64_t 
 void inflate_par_destroy(Ctx *c);                   // parallel Inflate (zada_inflate_par.hip)
 // ... one stream through it.  0: done; 1: not taken (the record says why), nothing was written to d_out and the caller runs the one-wave decoder; < 0: an error
 int inflate_par_try(Ctx *c, int format, const void *d_in, uint64_t n_in, void *d_out, uint64_t cap, uint64_t *out_len, uint64_t *in_used, uint32_t *crc_inout);
+// ... the selected entries of a zada_unzip_device group through it in shared launches ("inflate_par_batch"): res [k].taken says whether entry k is done
+// (out_len, in_used and crc are set) or left to the one-wave batch with nothing written; the record holds the sums.  0, or < 0: an error
+struct InfpbIn;
+struct InfpbRes;
+int inflate_par_batch(Ctx *c, uint32_t n, const InfpbIn *rows, InfpbRes *res);
 void inflate_par_record(Ctx *c, ::zada_inflate_par_info *get, const ::zada_inflate_par_info *set);   // the record zada_inflate_par_last gives: read and / or replaced
 void bunzip2_destroy(Ctx *c);                       // the BZip2 reader (zada_bunzip2.hip)
 void unlzma_destroy(Ctx *c);                        // the LZMA reader (zada_unlzma.hip)
@@ -371,6 +378,9 @@ void find_destroy(Ctx *c);                          // Find_Zip (zada_find.hip)
 // ... its stored entries for the archive writer: entry k's len [k] > 0 bytes at device address src [k] copied to dst [k] and summed in one pass, in
 // pieces of 16 KiB (k_uz_store / k_uz_fold); crc [k] is in/out, the running register
 int unzip_store_entries(Ctx *c, uint32_t ns, const uint64_t *src, const uint64_t *dst, const uint64_t *len, uint32_t *crc);
+// ... the same kernels over bytes that are in place already (UzStoreEnt.flags bit 0: sum only) for the batched parallel Inflate: len [k] > 0 bytes at
+// device address at [k], any alignment; crc [k] is in/out.  One synchronisation for all of them
+int unzip_sum_entries(Ctx *c, uint32_t ns, const uint64_t *at, const uint64_t *len, uint32_t *crc);
 // The readers' runners (inf_run, bzd_run, ulz_run) on jobs whose streams and outputs are device addresses, for zada_unzip_device: one call takes
 // every entry of a method through the launches of the method's batch call.  res [k].crc is in/out (the running register), rc ZADA_OK or ZADA_E_DATA;
 // the first entry that fails is described in the context's error text under its number `index`, unless *described says one already is.

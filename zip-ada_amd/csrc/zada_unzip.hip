@@ -23,6 +23,7 @@
 #include "../../include/zada.h"
 #include "zada_internal.h"
 #include "zada_unzip_plan.h"
+#include "zada_inflate_par_batch_plan.h"
 
 struct zada_ctx { zada::Ctx c; };
 
@@ -342,6 +343,19 @@ int unzip_store_entries(Ctx *c, uint32_t ns, const uint64_t *src, const uint64_t
   for (uint32_t s = 0; s < ns; s++) crc[s] = out[s];
   return 0;
 }
+int unzip_sum_entries(Ctx *c, uint32_t ns, const uint64_t *at, const uint64_t *len, uint32_t *crc) {
+  if (!ns) return 0;
+  UzState *S = uz_state(c);
+  if (!S) { c->err = "unzip: no memory for the tables"; return ZADA_E_NOMEM; }
+  std::vector<UzStoreEnt> se(ns);
+  std::vector<uint64_t> slen(len, len + ns);
+  for (uint32_t s = 0; s < ns; s++) se[s] = UzStoreEnt{at[s], at[s], len[s], crc[s], 0, 0, 1u};      // (bit 0: the bytes are in place)
+  std::vector<uint32_t> out;
+  const int rc = uz_store_run(c, S, se, slen, out, UZ_PIECE_DEFAULT, false);
+  if (rc) return rc;
+  for (uint32_t s = 0; s < ns; s++) crc[s] = out[s];
+  return 0;
+}
 
 // entries idx [0 .. n) of the table, entry idx [k]'s output at device address out [k]
 static int uz_group(Ctx *c, UzState *S, const uint8_t *archive, const zada_unzip_entry *ent, zada_unzip_result *res, const std::vector<int> &idx,
@@ -418,13 +432,36 @@ static int uz_group(Ctx *c, UzState *S, const uint8_t *archive, const zada_unzip
   std::vector<ReaderJob> rj;
   std::vector<ReaderRes> rr;
   std::vector<uint32_t> rk;
-  // "inflate_par_min_kib": the large Deflate entries (with "inflate_par_deflate64" the Deflate64 ones too) one after the other on many waves each (zada_inflate_par.hip); an entry that path does not
-  // take, a damaged one among them, is left to the batch below, whose verdict and error text are the answer
-  if (c->knob_infp_min_kib > 0) {
+  // "inflate_par_min_kib": the large Deflate entries (with "inflate_par_deflate64" the Deflate64 ones too) on many waves each (zada_inflate_par.hip): one
+  // after the other, or with "inflate_par_batch" all of the group in the same launches.  An entry that path does not take, a damaged one among them, is
+  // left to the batch below, whose verdict and error text are the answer
+  auto infp_selects = [&](uint32_t k) {
+    const zada_unzip_entry &e = ent[idx[k]];
+    return !done[k] && (e.method == 8 || (e.method == 9 && c->knob_infp_deflate64)) && uz_payload(e) >= ((uint64_t)c->knob_infp_min_kib << 10);
+  };
+  if (c->knob_infp_min_kib > 0 && c->knob_infp_batch) {
+    std::vector<InfpbIn> bi;
+    std::vector<uint32_t> bk;
+    for (uint32_t k = 0; k < n; k++) {
+      if (!infp_selects(k)) continue;
+      const zada_unzip_entry &e = ent[idx[k]];
+      bi.push_back(InfpbIn{src[k], uz_payload(e), out[k], e.cap, e.method, res[idx[k]].crc});
+      bk.push_back(k);
+    }
+    std::vector<InfpbRes> br(bi.size());
+    const int rc = inflate_par_batch(c, (uint32_t)bi.size(), bi.data(), br.data());
+    if (rc < 0) return rc;
+    for (size_t j = 0; j < bk.size(); j++) {
+      if (!br[j].taken) continue;
+      const uint32_t k = bk[j];
+      zada_unzip_result &R = res[idx[k]];
+      done[k] = 1; R.crc = br[j].crc; R.out_len = br[j].out_len; R.in_used = br[j].in_used + (uz_encrypted(ent[idx[k]]) ? 12 : 0);
+    }
+  } else if (c->knob_infp_min_kib > 0) {
     zada_inflate_par_info sum{}, one{};
     for (uint32_t k = 0; k < n; k++) {
+      if (!infp_selects(k)) continue;
       const zada_unzip_entry &e = ent[idx[k]];
-      if (done[k] || !(e.method == 8 || (e.method == 9 && c->knob_infp_deflate64)) || uz_payload(e) < ((uint64_t)c->knob_infp_min_kib << 10)) continue;
       zada_unzip_result &R = res[idx[k]];
       uint64_t ol = 0, iu = 0;
       uint32_t reg = R.crc;
