@@ -59,6 +59,9 @@ void Ctx::tend() {
   timing.push_back({"#bt4_pool_grown", (float)bt4_pool_grown});
   timing.push_back({"#atoms_grown", (float)atoms_grown});
   timing.push_back({"#fix_grown", (float)fix_grown});
+  timing.push_back({"#descr_l3_points", (float)descr_l3});
+  timing.push_back({"#descr_excluded", (float)descr_excluded});
+  timing.push_back({"#descr_late", (float)descr_late});
 }
 
 #ifndef ZADA_COPY_LANES
@@ -212,6 +215,7 @@ int ensure_entropy_workspace(Ctx *c, uint64_t atoms, uint64_t flushes, uint64_t 
   hipStreamSynchronize(c->stream); hipStreamSynchronize(c->stream2);
   free_group(W.en_allocs);
   W.cap_atoms = 0; W.cap_flush = 0;
+  c->trace_stale = false;                                        // (the atoms of the range analysed last are gone: zada_last_trace has nothing to run over)
   const uint64_t cap = room.cap_atoms;
   // flushes: one per 65 536 atoms of a stream; a batch of small entries has (at least) one per entry
   const uint64_t nflush = (cap / FLUSH > flushes ? cap / FLUSH : flushes + flushes / 4) + 3;
@@ -221,6 +225,7 @@ int ensure_entropy_workspace(Ctx *c, uint64_t atoms, uint64_t flushes, uint64_t 
   A(descr, nflush * SLOTS * 320);
   A(seg_nblk, nflush); A(seg_cut, nflush * MAXBLK_PER_SEG); A(seg_blk_off, nflush);
   A(cut_trace, nflush * SLOTS * 2);
+  A(pmask, nflush * (SLOTS + 5) * 10); A(descr_cnt, 4);
   W.cap_blocks = nflush * MAXBLK_PER_SEG;
   A(blocks, W.cap_blocks);
   A(binfo, W.cap_blocks);
@@ -535,7 +540,7 @@ int range_open(Ctx *c, int method, const uint8_t *rin, uint64_t stream_size, uin
   R.open = true; R.rin = rin; R.lo = lo; R.pre = pre; R.n = n; R.post = post;
   R.first = lo == 0; R.last = behind == 0; R.method = method; R.level = level;
   c->last_nblocks = 0;
-  c->demand_rounds = 0; c->parse_rounds = 0; c->atoms_grown = 0; c->fix_grown = 0;
+  c->demand_rounds = 0; c->parse_rounds = 0; c->descr_l3 = c->descr_excluded = c->descr_late = 0; c->atoms_grown = 0; c->fix_grown = 0;
   // the output bit stream is OR-ed together: zero it meanwhile, on the second stream
   Workspace &W = c->ws;
   const uint64_t zbytes = n + n / 8 + (1u << 20) < W.cap_out ? n + n / 8 + (1u << 20) : W.cap_out;
@@ -751,6 +756,7 @@ static int deflate_spans(Ctx *c, int method, const uint8_t *d_src, const uint8_t
   cc.last_type = BT_RESERVED; cc.cur_eob = 7u << 16;
   bool inefficient = false;
   int total_demand = 0, total_splice = 0, total_atoms_grown = 0, total_fix_grown = 0;
+  uint64_t total_l3 = 0, total_excluded = 0, total_late = 0;
   for (uint64_t lo = 0; lo < n; lo += span) {
     const uint64_t hi = lo + span < n ? lo + span : n;
     const bool last = hi == n;
@@ -782,6 +788,7 @@ static int deflate_spans(Ctx *c, int method, const uint8_t *d_src, const uint8_t
     if (R.nflush > 0 || last) {
       rc = entropy_analyze(c);
       if (rc) return rc;
+      total_l3 += c->descr_l3; total_excluded += c->descr_excluded; total_late += c->descr_late;
       hipStreamWaitEvent(st, c->ev_out, 0);
       if (cc.pos & 7) hipMemcpyAsync(W.out, &shared, 1, hipMemcpyHostToDevice, st);       // the byte this span shares with the one before
       R.carry_in = cc;
@@ -833,6 +840,7 @@ static int deflate_spans(Ctx *c, int method, const uint8_t *d_src, const uint8_t
     if (fb && fb((int)(100 * hi / n), user)) return ZADA_ABORTED;
   }
   c->demand_rounds = total_demand; c->parse_rounds = total_splice; c->atoms_grown = total_atoms_grown; c->fix_grown = total_fix_grown;      // (of all spans: range_open starts them at 0)
+  c->descr_l3 = total_l3; c->descr_excluded = total_excluded; c->descr_late = total_late;
   c->tmark("end"); c->tend();
   *out_len = inefficient ? base_bytes : (cc.pos + 7) / 8;
   if (crc_inout) *crc_inout = crc;
@@ -977,7 +985,7 @@ int batch_launch(Ctx *c, int method, const BatchLayout &L, uint64_t *obytes, uin
   Range &R = c->rg;
   R = Range();
   R.open = true; R.batch = true; R.n_entries = E; R.rin = W.in; R.n = total; R.method = method; R.level = level;
-  c->last_nblocks = 0; c->demand_rounds = 0; c->parse_rounds = 0;
+  c->last_nblocks = 0; c->demand_rounds = 0; c->parse_rounds = 0; c->descr_l3 = c->descr_excluded = c->descr_late = 0;
   hipLaunchKernelGGL(k_batch_crc, dim3(E), dim3(64), 0, st, E, W.in, W.ent_start, W.ent_len, W.ent_crc);
   ShardJob job;
   job.nbuf = total; job.tok_lo = 0; job.tok_hi = (uint32_t)total; job.final = true; job.entry_known = true; job.entry = ExitState{0, SYNC_F};
@@ -1104,6 +1112,7 @@ zada_ctx *zada_create(int device) {
   if (const char *e = getenv("ZADA_INNER_BUDGET")) z->c.knob_inner_budget = atoi(e);
   if (const char *e = getenv("ZADA_LINK_RUN")) { const int v = atoi(e); if (v >= 0 && v <= 64 && !(v & (v - 1))) z->c.knob_link_run = v; }
   if (const char *e = getenv("ZADA_ATOMS_PCT")) { if (atoi(e) >= 1 && atoi(e) <= 100) z->c.knob_atoms_pct = atoi(e); }
+  if (const char *e = getenv("ZADA_DESCR_LAZY")) z->c.knob_descr_lazy = atoi(e) != 0;
   if (const char *e = getenv("ZADA_CD_FILTER")) z->c.knob_cd_filter = atoi(e) != 0;
   if (const char *e = getenv("ZADA_EXACT_RESPEC")) { if (atoi(e) >= 0) z->c.knob_exact_respec = atoi(e); }
   if (const char *e = getenv("ZADA_MAX_DEMAND_ROUNDS")) { if (atoi(e) > 0) z->c.knob_max_demand_rounds = atoi(e); }
@@ -1150,6 +1159,7 @@ int zada_set_knob(zada_ctx *z, const char *name, int value) {
   else if (!strcmp(name, "atoms_pct")) { if (value < 1 || value > 100) return ZADA_E_INVALID; z->c.knob_atoms_pct = value; z->c.ws.cap_atoms = 0; }   // (the next call books the entropy workspace anew)
   else if (!strcmp(name, "fix_stride")) { if (value < 0 || value > (int)PTOK_STRIDE) return ZADA_E_INVALID; z->c.knob_fix_stride = value; z->c.ws.cap_n = 0; }
   else if (!strcmp(name, "cd_list_cap")) { if (value < 0) return ZADA_E_INVALID; z->c.knob_cd_list_cap = value; }
+  else if (!strcmp(name, "descr_lazy")) { if (value < 0 || value > 1) return ZADA_E_INVALID; z->c.knob_descr_lazy = value; }
   else if (!strcmp(name, "cd_filter")) { if (value < 0 || value > 1) return ZADA_E_INVALID; z->c.knob_cd_filter = value; }
   else if (!strcmp(name, "exact_respec")) { if (value < 0) return ZADA_E_INVALID; z->c.knob_exact_respec = value; }
   else if (!strcmp(name, "max_demand_rounds")) z->c.knob_max_demand_rounds = value > 0 ? value : 12;
@@ -2278,7 +2288,7 @@ int lzma_batch_launch(Ctx *c, int method, DevBatch &D) {
       hipLaunchKernelGGL(k_pad_init, dim3(1), dim3(256), 0, st, pa);
     }
     c->rg = Range();
-    c->last_nblocks = 0; c->demand_rounds = 0; c->parse_rounds = 0;
+    c->last_nblocks = 0; c->demand_rounds = 0; c->parse_rounds = 0; c->descr_l3 = c->descr_excluded = c->descr_late = 0;
     hipLaunchKernelGGL(k_batch_crc, dim3(E), dim3(64), 0, st, E, W.in, W.ent_start, W.ent_len, W.ent_crc);
     ShardJob job;
     job.nbuf = total; job.tok_lo = 0; job.tok_hi = (uint32_t)total; job.final = true; job.entry_known = true; job.entry = ExitState{0, SYNC_F};
@@ -2716,6 +2726,7 @@ int zada_last_trace(zada_ctx *z, uint64_t *rec, uint64_t cap, uint64_t *count) {
   *count = 0;
   if (!R.analyzed || R.method == ZADA_DEFLATE_FIXED || R.nflush == 0) return ZADA_OK;
   if (hipSetDevice(c->device) != hipSuccess) return ZADA_E_HIP;
+  if (entropy_trace(c)) return ZADA_E_HIP;                     // (a call that took the lazy path kept no trace: the full path over its atoms now)
   std::vector<uint32_t> h((size_t)R.nflush * SLOTS * 2);
   hipMemcpyAsync(h.data(), c->ws.cut_trace, h.size() * 4, hipMemcpyDeviceToHost, c->stream);
   if (hip_check(c, hipStreamSynchronize(c->stream), "trace")) return ZADA_E_HIP;

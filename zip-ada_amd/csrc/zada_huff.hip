@@ -7,6 +7,8 @@
 //                    histogram (Get_statistics :953-976) + length-limited code lengths
 //   k_cut_scan       Scan_and_send_from_main_buffer's similarity walk (:1363-1401), one wave
 //                    per flush; emits the cut positions = candidate blocks
+//   k_piece_masks / k_cut_scan_lazy   Deflate_3 (knob "descr_lazy"): the descriptors of the windows tested at step level 3 only are built
+//                    where a bound on the distance (zada_descr_bound.h) does not already say "similar", inside the scan
 //   k_block_analyze  per candidate block: statistics, both descriptor variants (:1213-1219),
 //                    header costs (:549-704) and data costs (:1147-1209)
 //   k_choose         the one inherently sequential step: the format decision chain of
@@ -16,8 +18,10 @@
 //                    parallel emission: per-atom (code, length) -> prefix sums -> bit packing
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
+#include <stdio.h>
 #include <stdint.h>
 #include "zada_logic.h"
+#include "zada_descr_bound.h"
 #include "zada_internal.h"
 #include "zada_llhc_wave.h"
 
@@ -178,6 +182,153 @@ __global__ void __launch_bounds__(64) k_cut_scan(EntropyView v, uint32_t kstep, 
   if (lane == 0) seg_nblk[j] = nb;
 }
 
+// --------------------------------------------------------------------------------------------
+// The lazy path of Deflate_3 (kstep 1; knob "descr_lazy").  Three slots in four are tested at step level 3 only, where a cut needs a
+// distance of 205 000 -- far more than neighbouring windows of one kind of data are apart.  A sliding descriptor is only ever compared
+// with the reference descriptor and, if that cuts, installed as the new one (:1363-1401): where a bound on the distance taken from the
+// reference's lengths and the SET of symbols the window uses (zada_descr_bound.h) stays below the threshold, the window's two codings are
+// never read and are not made.
+//   k_piece_masks     which symbols occur in every 750-atom piece, pieces laid out from F - 2048 per flush: sliding window k is the
+//                     pieces k .. k + 4 whole and the first 347 atoms of piece k + 5
+//   k_window_descr    with kstep 4: slot 0 and the slots tested at levels 1 and 2, each counted whole
+//   k_cut_scan_lazy   the walk of k_cut_scan; at a level-3-only slot the bound, and only where it does not decide the window's
+//                     descriptor, built on the spot by the same wave (and left in `descr`, as k_window_descr would have)
+// Same cuts as k_window_descr (kstep 1) + k_cut_scan; no trace (zada_last_trace runs those two when asked).
+// --------------------------------------------------------------------------------------------
+constexpr uint32_t PM_PIECES = SLOTS + 5, PM_GROUPS = (PM_PIECES + 3) / 4, PM_LOADS = (MIN_STEP + 63) / 64;
+// one wave per piece: its 750 atoms in flight at once, every lane's symbols into ten words of its own, the words OR-ed across the wave
+__global__ void __launch_bounds__(256) k_piece_masks(EntropyView v, uint32_t *__restrict__ pmask) {
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint32_t p = (blockIdx.x % PM_GROUPS) * 4 + (uint32_t)w, j = blockIdx.x / PM_GROUPS;
+  uint64_t gj; uint32_t F, to, fl;
+  if (!flush_geom(v, j, F, to, gj, fl)) return;
+  if (to - F < SLIDER - 1 || p >= PM_PIECES) return;
+  int64_t a = (int64_t)F - HALF_SLIDER + (int64_t)MIN_STEP * p, b = a + MIN_STEP - 1;
+  if (a < 0) a = 0;
+  if (b > (int64_t)to) b = to;
+  uint32_t at[PM_LOADS];
+#pragma unroll
+  for (uint32_t u = 0; u < PM_LOADS; u++) { const int64_t x = a + lane + 64 * u; at[u] = x <= b ? v.atoms[x] : 0xFFFFFFFFu; }
+  uint32_t m[DB_WORDS];
+#pragma unroll
+  for (int k = 0; k < DB_WORDS; k++) m[k] = 0;
+#pragma unroll
+  for (uint32_t u = 0; u < PM_LOADS; u++) {
+    if (a + lane + 64 * u <= b) {
+      int ls, ds; atom_symbols(at[u], ls, ds);
+      const uint32_t bit = 1u << (ls & 31);
+#pragma unroll
+      for (int k = 0; k < 9; k++) m[k] |= (ls >> 5) == k ? bit : 0u;
+      if (ds >= 0) m[9] |= 1u << ds;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < DB_WORDS; k++)
+    for (int off = 32; off >= 1; off >>= 1) m[k] |= __shfl_xor(m[k], off);
+  uint32_t mine = 0;
+#pragma unroll
+  for (int k = 0; k < DB_WORDS; k++) if (lane == k) mine = m[k];
+  if (lane < DB_WORDS) pmask[((uint64_t)j * PM_PIECES + p) * DB_WORDS + lane] = mine;
+}
+
+__global__ void __launch_bounds__(64) k_cut_scan_lazy(EntropyView v, uint8_t *__restrict__ descr, const uint32_t *__restrict__ pmask,
+                                                      uint32_t *__restrict__ seg_nblk, uint32_t *__restrict__ seg_cut, uint32_t *__restrict__ counters) {
+  __shared__ uint32_t hist[320];
+  __shared__ uint8_t bl[320];
+  __shared__ __attribute__((aligned(16))) uint8_t S[LLHC_WAVE_SCRATCH];
+  __shared__ uint32_t Um[DB_WORDS], Dm[DB_WORDS], bins[2][DB_BINS];
+  const uint32_t *__restrict__ atoms = v.atoms;
+  const uint32_t j = blockIdx.x;
+  const int lane = threadIdx.x;
+  uint64_t gj; uint32_t F, to, fl;
+  if (!flush_geom(v, j, F, to, gj, fl)) { if (lane == 0) seg_nblk[j] = 0; return; }
+  uint32_t *cuts = seg_cut + (uint64_t)j * MAXBLK_PER_SEG;
+  uint32_t nb = 1, n_l3 = 0, n_excl = 0, n_late = 0;
+  if (lane == 0) cuts[0] = F;
+  if (to - F >= SLIDER - 1) {
+    uint8_t *d0 = descr + (uint64_t)j * SLOTS * 320;
+    const uint32_t *pm = pmask + (uint64_t)j * PM_PIECES * DB_WORDS;
+    int init[5], ibl[5];                                                          // the reference descriptor: tweaked, and its lengths
+    for (int r = 0; r < 5; r++) { ibl[r] = d0[lane + 64 * r]; init[r] = tweak_value(ibl[r]); }
+    for (uint32_t k = 1; (uint64_t)F + MIN_STEP * k + HALF_SLIDER < to; k++) {
+      const int thr = (k % 8 == 0) ? 420 : (k % 4 == 0) ? 430 : 2050;          // step_choice :1304-1308
+      uint8_t *dk = d0 + (uint64_t)k * 320;
+      if (k % 4) {
+        n_l3++;
+        const int64_t lo = (int64_t)F + MIN_STEP * k - HALF_SLIDER;
+        const bool empty = (gj & 1) == 0 && MIN_STEP * k < HALF_SLIDER;           // the null slice (:1372): built, not bounded
+        bool decided = false;
+        if (!empty) {
+          __syncthreads();
+          if (lane < DB_WORDS) {
+            uint32_t d = 0;
+            for (uint32_t q = 0; q < 5; q++) d |= pm[(k + q) * DB_WORDS + lane];
+            uint32_t u = d | pm[(k + 5) * DB_WORDS + lane];
+            if (lane == 8) { d |= 1u; u |= 1u; }                                   // end of block, counted once in every window :946
+            Dm[lane] = d; Um[lane] = u;
+          }
+          bins[lane >> 5][lane & 31] = 0;
+          __syncthreads();
+          if (lane == 0) db_patch_dist(Um, Dm);
+          __syncthreads();
+          uint32_t bound = 0;
+          for (int r = 0; r < 5; r++) {
+            const int s = lane + 64 * r;
+            const bool in_u = db_has(Um, s);
+            int bin;
+            bound += db_sym(ibl[r], in_u, in_u && db_has(Dm, s), bin);
+            if (bin >= 0) atomicAdd(&bins[s >= 288][bin], 1u);
+          }
+          __syncthreads();
+          bound += db_bin_extra(bins[lane >> 5], lane & 31);
+          bound = wave_sum_u32(bound);
+          decided = bound < DB_L3_CUT;                                             // the distance is below the bound: Similar
+        }
+        if (decided) { n_excl++; continue; }
+        n_late++;
+        // the window's descriptor after all, as k_window_descr makes it
+        __syncthreads();
+        for (int i = lane; i < 320; i += 64) hist[i] = (i == 256) ? 1u : 0u;
+        __syncthreads();
+        if (!empty)
+          for (int64_t a0 = lo + lane; a0 <= lo + SLIDER; a0 += 64 * 8) {
+            uint32_t at[8];
+#pragma unroll
+            for (int u = 0; u < 8; u++) { const int64_t x = a0 + 64 * u; at[u] = atoms[x <= lo + SLIDER ? x : lo + SLIDER]; }
+#pragma unroll
+            for (int u = 0; u < 8; u++) {
+              if (a0 + 64 * u <= lo + SLIDER) {
+                int ls, ds; atom_symbols(at[u], ls, ds);
+                atomicAdd(&hist[ls], 1u);
+                if (ds >= 0) atomicAdd(&hist[288 + ds], 1u);
+              }
+            }
+          }
+        __syncthreads();
+        if (lane == 0) patch_dist_stats(hist + 288);
+        __syncthreads();
+#pragma unroll 1
+        for (int t = 0; t < 2; t++) llhc_wave<15>(hist + 288 * t, t ? 32 : 288, bl + 288 * t, S, lane);
+        __syncthreads();
+        for (int i = lane; i < 320; i += 64) dk[i] = bl[i];
+        __syncthreads();
+      }
+      int sb[5], sl[5]; uint32_t dist = 0;
+      for (int r = 0; r < 5; r++) { sb[r] = (k % 4) ? bl[lane + 64 * r] : dk[lane + 64 * r]; sl[r] = tweak_value(sb[r]); int d = init[r] - sl[r]; dist += (uint32_t)(d < 0 ? -d : d); }
+      dist = wave_sum_u32(dist);
+      if (!(dist < (uint32_t)thr * 100u)) {                                      // not Similar => cut (:1375-1395)
+        if (lane == 0) cuts[nb] = F + MIN_STEP * k;
+        nb++;
+        for (int r = 0; r < 5; r++) { init[r] = sl[r]; ibl[r] = sb[r]; }
+      }
+    }
+  }
+  if (lane == 0) {
+    seg_nblk[j] = nb;
+    if (n_l3) { atomicAdd(&counters[0], n_l3); atomicAdd(&counters[1], n_excl); atomicAdd(&counters[2], n_late); }
+  }
+}
+
 __global__ void k_fill_blocks(EntropyView v, const uint32_t *__restrict__ seg_nblk, const uint32_t *__restrict__ seg_cut,
                               const uint32_t *__restrict__ seg_off, BlockRange *__restrict__ blocks, uint32_t *__restrict__ blk_entry, int fixed_only) {
   uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -218,10 +369,156 @@ __global__ void k_apos_sentinel(const uint32_t *__restrict__ atoms, uint32_t *__
 // --------------------------------------------------------------------------------------------
 // k_block_analyze : one workgroup (256 threads) per candidate block
 // --------------------------------------------------------------------------------------------
+// ---- the single-lane stretches of round 1-7's kernel on a whole wave (Round 8; cycle split in profiles/r8/NOTES.md: the two tweaks were 38 % and the
+// header plan 29 % of a block's cycles, one lane walking LDS arrays element by element while 255 waited at the barrier) ----
+// A set of positions 0 .. 319 as five 64-bit words in LDS (uniform content, per-lane look-ups): first member above i (320: none)
+__device__ __forceinline__ int posmap_next(const uint64_t *m, int i) {
+  int r = (i + 1) >> 6;
+  if (r >= 5) return 320;
+  uint64_t w = m[r] & (~0ull << ((i + 1) & 63));
+  while (!w) { if (++r >= 5) return 320; w = m[r]; }
+  return 64 * r + __builtin_ctzll(w);
+}
+// ... last member at or below i (-1: none)
+__device__ __forceinline__ int posmap_prev(const uint64_t *m, int i) {
+  int r = i >> 6;
+  uint64_t w = m[r] & (~0ull >> (63 - (i & 63)));
+  while (!w) { if (--r < 0) return -1; w = m[r]; }
+  return 64 * r + 63 - __builtin_clzll(w);
+}
+
+// Tweak_for_better_RLE (zip-compress-deflate.adb:238-318) on one wave, the same result as tweak_for_better_rle (zada_logic.h): `orig` are the counts
+// (n <= 64 * R of them, not written), `out` a copy of them that is tweaked in place; scratch: 2 * (n + 1) words and five 64-bit words.
+//   * the stretches of equal counts that are good for RLE already (:254-276) are runs: their starts come from ballots, a position's run from the
+//     neighbouring starts;
+//   * the second loop (:278-316) goes from break to break.  Where it breaks depends on the counts not yet rewritten -- a stretch is rewritten
+//     when the break behind it is reached, and `limit` is taken from the four counts from the break on -- so the next break is the first position
+//     that is good, follows a good one, or differs from the limit by four or more: one ballot per 64 positions instead of one step per position;
+//     the stretch's sum is a difference of prefix sums, and its new count is written by all lanes at once.
+template <int R>
+__device__ void tweak_rle_wave(const uint32_t *orig, uint32_t *out, int n, uint8_t *scratch, int lane) {
+  uint32_t *P = (uint32_t *)scratch, *LIM = P + 328;
+  uint64_t *map = (uint64_t *)(LIM + 328);
+  uint32_t c[R];
+#pragma unroll
+  for (int r = 0; r < R; r++) { const int i = lane + 64 * r; c[r] = i < n ? orig[i] : 0u; }
+  int length = 0;
+#pragma unroll
+  for (int r = 0; r < R; r++) { const unsigned long long m = __ballot(c[r] != 0); if (m) length = 64 * r + 64 - __builtin_clzll(m); }
+  if (length == 0) return;                                                         // :249-252
+  // starts of the runs of equal counts in [0, length), and `length` itself as the end of the last one
+#pragma unroll
+  for (int r = 0; r < 5; r++) {
+    unsigned long long m = 0;
+    if (r < R) { const int i = lane + 64 * r; m = __ballot(i <= length && (i == 0 || i == length || c[r] != orig[i - 1])); }
+    if (lane == 0) map[r] = m;
+  }
+  // prefix sums P [i] = orig [0] + .. + orig [i - 1], and the limit a break at i sets (:306-312)
+  uint32_t carry = 0;
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const int i = lane + 64 * r;
+    uint32_t x = i < length ? c[r] : 0u;
+    for (int off = 1; off < 64; off <<= 1) { const uint32_t y = __shfl_up(x, off); if (lane >= off) x += y; }
+    if (i < length) {
+      P[i + 1] = carry + x;
+      LIM[i] = i < length - 3 ? (c[r] + orig[i + 1] + orig[i + 2] + orig[i + 3] + 2) / 4 : c[r];
+    }
+    carry += __shfl(x, 63);
+  }
+  if (lane == 0) { P[0] = 0; LIM[length] = 0; }
+  wave_sync();
+  // good [i] (:254-276), then G: positions where the second loop breaks whatever the limit is
+  uint64_t G[R];
+  unsigned long long below = 0;                                                  // good [64 r - 1]
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const int i = lane + 64 * r;
+    bool good = false;
+    if (i < length) { const int len = posmap_next(map, i) - posmap_prev(map, i); good = c[r] == 0 ? len >= 5 : len >= 7; }
+    const unsigned long long gm = __ballot(good);
+    G[r] = gm | (gm << 1) | below;
+    below = gm >> 63;
+    if ((length >> 6) == r) G[r] |= 1ull << (length & 63);
+  }
+  int b = 0;
+  uint32_t limit = (G[0] & 1) ? LIM[0] : orig[0];                                  // (no break at 0 unless good [0]: limit = counts [0], :279)
+  for (;;) {
+    int next = -1;
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      if (next < 0 && r >= (b >> 6)) {
+        const int64_t d = (int64_t)c[r] - (int64_t)limit;
+        unsigned long long m = __ballot(d >= 4 || d <= -4) | G[r];
+        if (r == (b >> 6)) m &= ~((2ull << (b & 63)) - 1);                          // positions above b
+        if ((length >> 6) == r) m &= (2ull << (length & 63)) - 1;                   // ... up to `length`
+        if (m) next = 64 * r + __builtin_ctzll(m);
+      }
+    }
+    const uint32_t stride = (uint32_t)(next - b), sum = P[next] - P[b];
+    if (stride >= 4 || (stride >= 3 && sum == 0)) {                                 // :283-296
+      uint32_t nc = (sum + stride / 2) / stride;
+      if (nc < 1) nc = 1;
+      if (sum == 0) nc = 0;
+#pragma unroll
+      for (int r = 0; r < R; r++) { const int i = lane + 64 * r; if (i >= b && i < next) out[i] = nc; }
+    }
+    if (next >= length) break;
+    // positions of G that follow one another (a stretch that is good for RLE: typically the long runs of unused symbols) break one by one into
+    // stretches of one count, which are never rewritten: go on from the last of them
+    uint64_t g = 0;
+#pragma unroll
+    for (int r = 0; r < R; r++) if (r == (next >> 6)) g = G[r];
+    const uint64_t inv = ~(g >> (next & 63));
+    const int ones = inv ? __builtin_ctzll(inv) : 64;
+    b = ones > 1 ? next + ones - 1 : next;
+    if (b >= length) break;
+    limit = LIM[b];
+  }
+  wave_sync();
+}
+
+// The tokens of Put_Compression_Structure's run-length walk (header_rle_walk, :597-650) over a run of `len` equal code lengths v that starts where the
+// walk stands at its first element (a run's start always is such a place: no token crosses into a run of another value): counted into tf [0 .. 18].
+__device__ __forceinline__ void header_run_tokens(uint32_t *tf, int v, int len) {
+  if (v != 0) {
+    // the first element as itself, then "repeat previous" for 3 .. 6 at a time while three or more are left, the rest as themselves
+    const int rem = len - 1, m = rem % 6;
+    const int n16 = rem / 6 + (m >= 3 ? 1 : 0), lits = 1 + (m >= 3 ? 0 : m);
+    atomicAdd(&tf[v], (uint32_t)lits);
+    if (n16) atomicAdd(&tf[16], (uint32_t)n16);
+  } else {
+    int rem = len, done = 0, n16 = 0, n17 = 0, n18 = 0, lits = 0;
+    while (rem > 0) {
+      if (done > 0 && rem >= 3 && rem <= 6) { n16++; rem = 0; }                     // zeros behind zeros: "repeat previous" only for 3 .. 6 (:613)
+      else if (rem >= 3) { if (rem <= 10) { n17++; rem = 0; } else { const int t = rem < 138 ? rem : 138; n18++; rem -= t; done += t; } }
+      else { lits += rem; rem = 0; }
+    }
+    if (lits) atomicAdd(&tf[0], (uint32_t)lits);
+    if (n16) atomicAdd(&tf[16], (uint32_t)n16);
+    if (n17) atomicAdd(&tf[17], (uint32_t)n17);
+    if (n18) atomicAdd(&tf[18], (uint32_t)n18);
+  }
+}
+
+#ifdef ZADA_BA_STATS   /* cycles of a block's phases by thread 0's clock (entropy_analyze prints them): 0 histogram, 1 tweaks, 2 patches, 3 the four codings,
+                          4 header plan (cs_bl, RLE walk), 5 coding of the header's code, 6 a_non_zero and header bits, 7 costs and output; 8 blocks, 9 atoms.
+                          The stamps 0 .. 3 stand behind a barrier of their own; 4 .. 6 are wave 0's (wave 1 does the other variant meanwhile) */
+__device__ unsigned long long g_ba_dbg[16];
+#define BA_STAMP(k) do { if (threadIdx.x == 0) { const unsigned long long t_ = clock64(); atomicAdd(&g_ba_dbg[k], t_ - ba_t); ba_t = t_; } } while (0)
+#define BA_STAMP_SYNC(k) do { __syncthreads(); BA_STAMP(k); } while (0)
+#else
+#define BA_STAMP(k) do { } while (0)
+#define BA_STAMP_SYNC(k) do { } while (0)
+#endif
 __global__ void __launch_bounds__(256) k_block_analyze(const uint32_t *__restrict__ atoms, const uint32_t *__restrict__ apos,
                                                        const BlockRange *__restrict__ blocks, BlockInfo *__restrict__ binfo) {
+#ifdef ZADA_BA_STATS
+  unsigned long long ba_t = clock64();
+#endif
   __shared__ uint32_t st1[320], st2[320], dtmp[2][32];
-  __shared__ uint8_t bl1[320], bl2[320], good[320];
+  __shared__ uint8_t bl1[320], bl2[320];
+  __shared__ uint32_t sp_s;
   __shared__ __attribute__((aligned(16))) uint8_t S[4][LLHC_WAVE_SCRATCH];
   __shared__ HeaderPlan hp[2];
   __shared__ uint64_t red[3][4];
@@ -243,44 +540,72 @@ __global__ void __launch_bounds__(256) k_block_analyze(const uint32_t *__restric
     }
   }
   __syncthreads();
+  BA_STAMP(0);
   for (int i = tid; i < 320; i += 256) st2[i] = st1[i];
   __syncthreads();
-  if (tid == 0) tweak_for_better_rle(st2, 288, good);                       // :1217
-  if (tid == 64) tweak_for_better_rle(st2 + 288, 32, good + 288);           // :1218
+  if (w == 0) tweak_rle_wave<5>(st1, st2, 288, S[0], lane);                 // :1217
+  if (w == 1) tweak_rle_wave<1>(st1 + 288, st2 + 288, 32, S[1], lane);      // :1218
+  if (w == 3) {                                                             // :1222 (Long_length_codes :1093-1095)
+    const unsigned long long m = __ballot(lane < 21 && st1[267 + lane] != 0);
+    if (lane == 0) sp_s = m ? 0u : 1u;
+  }
   __syncthreads();
+  BA_STAMP(1);
   if (w >= 2 && lane == 0) {
     uint32_t *dt = dtmp[w - 2]; const uint32_t *src = (w == 2 ? st1 : st2) + 288;
     for (int i = 0; i < 32; i++) dt[i] = src[i];
     patch_dist_stats(dt);                                                     // :340-365, on a copy
   }
   wave_sync();
+  BA_STAMP_SYNC(2);
   llhc_wave<15>(w == 0 ? st1 : w == 1 ? st2 : dtmp[w - 2], w < 2 ? 288 : 32,      // one wave per code set
                 ((w & 1) ? bl2 : bl1) + (w < 2 ? 0 : 288), S[w], lane);
   __syncthreads();
+  BA_STAMP(3);
   if (w < 2) {                                                                // Put_Compression_Structure, cost analysis
     HeaderPlan *h = &hp[w];
     const uint8_t *ll = w == 0 ? bl1 : bl2;
-    if (lane == 0) {
-      int max_ll = 0, max_d = 0, idx = 0;
-      for (int a = 287; a >= 0; a--) if (ll[a] > 0) { max_ll = a; break; }
-      for (int a = 31; a >= 0; a--) if (ll[288 + a] > 0) { max_d = a; break; }
-      for (int a = 0; a <= max_ll; a++) h->cs_bl[idx++] = ll[a];
-      for (int a = 0; a <= max_d; a++) h->cs_bl[idx++] = ll[288 + a];
-      h->last_cs_bl = (uint16_t)idx; h->hlit_m257 = (uint8_t)(max_ll - 256); h->hdist_m1 = (uint8_t)max_d;
-      for (int a = 0; a < 19; a++) h->truc_freq[a] = 0;
-      uint32_t *tf = h->truc_freq;
-      header_rle_walk(h->cs_bl, idx, [tf](int x, uint32_t) { tf[x]++; });
+    uint64_t *map = (uint64_t *)S[w];
+    // the last used code of either alphabet (0 if none), the concatenated lengths, the starts of their runs
+    int max_ll = 0;
+    for (int r = 0; r < 5; r++) { const int a = lane + 64 * r; if (a < 288 && ll[a] > 0) max_ll = a; }
+    for (int off = 32; off >= 1; off >>= 1) { const int o = __shfl_xor(max_ll, off); max_ll = o > max_ll ? o : max_ll; }
+    const unsigned long long dm = __ballot(lane < 32 && ll[288 + (lane & 31)] > 0);
+    const int max_d = dm ? 63 - __builtin_clzll(dm) : 0;
+    const int n = max_ll + 1 + max_d + 1;
+    int cv[5];
+    for (int r = 0; r < 5; r++) {
+      const int i = lane + 64 * r;
+      cv[r] = i < n ? (int)(i <= max_ll ? ll[i] : ll[288 + i - max_ll - 1]) : -1;
+      if (i < n) h->cs_bl[i] = (uint8_t)cv[r];
+    }
+    if (lane < 19) h->truc_freq[lane] = 0;
+    if (lane == 0) { h->last_cs_bl = (uint16_t)n; h->hlit_m257 = (uint8_t)(max_ll - 256); h->hdist_m1 = (uint8_t)max_d; }
+    wave_sync();
+    bool start[5];
+    for (int r = 0; r < 5; r++) {
+      const int i = lane + 64 * r;
+      start[r] = i < n && (i == 0 || cv[r] != (int)h->cs_bl[i - 1]);
+      const unsigned long long m = __ballot(start[r] || i == n);
+      if (lane == 0) map[r] = m;
     }
     wave_sync();
+    for (int r = 0; r < 5; r++)
+      if (start[r]) { const int i = lane + 64 * r; header_run_tokens(h->truc_freq, cv[r], posmap_next(map, i) - i); }
+    wave_sync();
+    BA_STAMP(4);
     llhc_wave<7>(h->truc_freq, 19, h->truc_bl, S[w], lane);
-    if (lane == 0) {
-      int anz = 3;
-      for (int a = 0; a <= 18; a++) if (a > anz && h->truc_bl[header_perm(a)] > 0) anz = a;
-      h->a_non_zero = (uint8_t)anz;
-      uint32_t bits = 14 + (uint32_t)(1 + anz) * 3;
-      for (int a = 0; a <= 18; a++) bits += h->truc_freq[a] * (uint32_t)(h->truc_bl[a] + header_extra_bits(a));
-      h->bits = bits;
+    wave_sync();
+    BA_STAMP(5);
+    {
+      const unsigned long long nz = __ballot(lane < 19 && h->truc_bl[header_perm(lane < 19 ? lane : 0)] > 0);
+      int anz = nz ? 63 - __builtin_clzll(nz) : 0;
+      if (anz < 3) anz = 3;
+      uint32_t bits = lane < 19 ? h->truc_freq[lane] * (uint32_t)(h->truc_bl[lane] + header_extra_bits(lane)) : 0u;
+      bits = wave_sum_u32(bits) + 14 + (uint32_t)(1 + anz) * 3;
+      if (lane == 0) { h->a_non_zero = (uint8_t)anz; h->bits = bits; }
     }
+    BA_STAMP(6);
   }
   // data costs, Compute_sizes_of_variants :1152-1190 (EOB, symbol 256, is never counted there)
   uint64_t cf = 0, c1 = 0, c2 = 0;
@@ -304,10 +629,12 @@ __global__ void __launch_bounds__(256) k_block_analyze(const uint32_t *__restric
     bi->dyn1_data = red[1][0] + red[1][1] + red[1][2] + red[1][3];
     bi->dyn2_data = red[2][0] + red[2][1] + red[2][2] + red[2][3];
     bi->bytes = (br.pad ? br.pad : apos[br.first + br.count]) - apos[br.first];     // (pad: the entry ends here, in a batch)
-    uint32_t sp = 1;
-    for (int i = 267; i <= 287; i++) if (st1[i] != 0) sp = 0;                // :1222 (Long_length_codes :1093-1095)
-    bi->stored_possible = sp;
+    bi->stored_possible = sp_s;
   }
+  BA_STAMP(7);
+#ifdef ZADA_BA_STATS
+  if (tid == 0) { atomicAdd(&g_ba_dbg[8], 1ull); atomicAdd(&g_ba_dbg[9], (unsigned long long)br.count); }
+#endif
 }
 
 // --------------------------------------------------------------------------------------------
@@ -1085,23 +1412,58 @@ int entropy_analyze(Ctx *c) {
       hipLaunchKernelGGL(k_fill_blocks_fixed, dim3((nblocks + 255) / 256), dim3(256), 0, st, v.foff, v.lvalid - v.foff, nblocks, W.blocks);
     } else {
       const uint32_t kstep = fixed_only ? (1u << 30) : R.method == 8 ? 8 : R.method == 9 ? 4 : 1;   // max_choice :1310-1311 (Deflate_Fixed in a batch: no scanning, one block per flush)
-      if (!fixed_only) hipLaunchKernelGGL(k_window_descr, dim3(v.nflush * WD_NGROUPS), dim3(64), 0, st, v, kstep, W.descr);
+      const bool lazy = kstep == 1 && c->knob_descr_lazy;                          // (Deflate_2 / _1 have no slot tested at level 3 only)
+      uint32_t cnt[3] = {0, 0, 0};
+      if (lazy) {
+        hipMemsetAsync(W.descr_cnt, 0, 3 * 4, st);
+        hipLaunchKernelGGL(k_piece_masks, dim3(v.nflush * PM_GROUPS), dim3(256), 0, st, v, W.pmask);
+        hipLaunchKernelGGL(k_window_descr, dim3(v.nflush * WD_NGROUPS), dim3(64), 0, st, v, 4u, W.descr);
+      } else if (!fixed_only) hipLaunchKernelGGL(k_window_descr, dim3(v.nflush * WD_NGROUPS), dim3(64), 0, st, v, kstep, W.descr);
       c->tmark("window_descr");
-      hipLaunchKernelGGL(k_cut_scan, dim3(v.nflush), dim3(64), 0, st, v, kstep, W.descr, W.seg_nblk, W.seg_cut, W.cut_trace);
+      if (lazy) hipLaunchKernelGGL(k_cut_scan_lazy, dim3(v.nflush), dim3(64), 0, st, v, W.descr, W.pmask, W.seg_nblk, W.seg_cut, W.descr_cnt);
+      else hipLaunchKernelGGL(k_cut_scan, dim3(v.nflush), dim3(64), 0, st, v, kstep, W.descr, W.seg_nblk, W.seg_cut, W.cut_trace);
+      c->trace_stale = lazy;
       exclusive_scan_u32(st, W.seg_nblk, W.seg_blk_off, W.scan2, W.total2, v.nflush);
       hipMemcpyAsync(&nblocks, W.total2, 4, hipMemcpyDeviceToHost, st);
+      if (lazy) hipMemcpyAsync(cnt, W.descr_cnt, 3 * 4, hipMemcpyDeviceToHost, st);
       hipLaunchKernelGGL(k_fill_blocks, dim3((v.nflush + 255) / 256), dim3(256), 0, st, v, W.seg_nblk, W.seg_cut, W.seg_blk_off, W.blocks, W.blk_entry, fixed_only ? 1 : 0);
       if (hip_check(c, hipStreamSynchronize(st), "cut_scan")) return ZADA_E_HIP_;
       c->tmark("cut_scan");
+      c->descr_l3 += cnt[0]; c->descr_excluded += cnt[1]; c->descr_late += cnt[2];
     }
     if (nblocks > W.cap_blocks) { c->err = "block table overflow"; return -1; }
     if (nblocks > 0) hipLaunchKernelGGL(k_block_analyze, dim3(nblocks), dim3(256), 0, st, v.atoms, v.apos, W.blocks, W.binfo);
     c->tmark("block_analyze");
+#ifdef ZADA_BA_STATS
+    { unsigned long long h[16]; hipDeviceSynchronize(); hipMemcpyFromSymbol(h, HIP_SYMBOL(g_ba_dbg), sizeof h);
+      const double nb = h[8] ? (double)h[8] : 1.0;
+      fprintf(stderr, "[k_block_analyze] %llu blocks, %.0f atoms per block; cycles per block: histogram %.0f, tweaks %.0f, patches %.0f, codings %.0f, header plan %.0f, header code %.0f, "
+              "a_non_zero + bits %.0f, costs + output %.0f\n", h[8], (double)h[9] / nb, (double)h[0] / nb, (double)h[1] / nb, (double)h[2] / nb, (double)h[3] / nb, (double)h[4] / nb, (double)h[5] / nb,
+              (double)h[6] / nb, (double)h[7] / nb);
+      for (int q = 0; q < 16; q++) h[q] = 0;
+      hipMemcpyToSymbol(HIP_SYMBOL(g_ba_dbg), h, sizeof h); }
+#endif
     if ((!fixed_only || R.batch) && nblocks > 0) hipLaunchKernelGGL(k_block_relate, dim3(nblocks), dim3(64), 0, st, nblocks, W.binfo, W.blocks, (ChRec *)W.chrec);
   }
   R.nblocks = nblocks;
   R.analyzed = true;
   return hip_check(c, hipGetLastError(), "entropy_analyze");
+}
+
+// The trace of the range analysed last, when its cuts came from the lazy path (which keeps none): the full path over the same atoms
+// (they stay in the workspace until the next call) -- every window's descriptor, the distance at every test point.  Same cuts.
+int entropy_trace(Ctx *c) {
+  if (!c->trace_stale) return 0;
+  const Range &R = c->rg;
+  Workspace &W = c->ws;
+  if (!R.analyzed || R.method == 6 || R.nflush == 0) return 0;
+  const EntropyView v = range_view(c);
+  const uint32_t kstep = R.method == 8 ? 8 : R.method == 9 ? 4 : 1;
+  hipLaunchKernelGGL(k_window_descr, dim3(v.nflush * WD_NGROUPS), dim3(64), 0, c->stream, v, kstep, W.descr);
+  hipLaunchKernelGGL(k_cut_scan, dim3(v.nflush), dim3(64), 0, c->stream, v, kstep, W.descr, W.seg_nblk, W.seg_cut, W.cut_trace);
+  if (hip_check(c, hipGetLastError(), "trace")) return ZADA_E_HIP_;
+  c->trace_stale = false;
+  return 0;
 }
 
 int entropy_choose(Ctx *c) {

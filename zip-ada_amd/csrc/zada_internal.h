@@ -175,6 +175,8 @@ struct Workspace {
   uint32_t *ea_atoms = nullptr, *ea_apos = nullptr;   // local atom array: LB_CAP slots, the range's atoms, LA_CAP slots (+ sentinel)
   uint8_t *descr = nullptr;                  // [nflush][SLOTS][320]
   uint32_t *seg_nblk = nullptr, *seg_cut = nullptr, *seg_blk_off = nullptr;   // cuts [nflush][MAXBLK_PER_SEG]
+  uint32_t *pmask = nullptr;                 // [nflush][SLOTS + 5][10]: symbols present in every 750-atom piece (lazy descriptors, zada_huff.hip)
+  uint32_t *descr_cnt = nullptr;             // [3]: level-3-only test points, decided by the bound, descriptors built inside the scan
   uint32_t *cut_trace = nullptr;             // [nflush][SLOTS][2]: similarity distance and cut level at every test point
   BlockRange *blocks = nullptr;
   BlockInfo *binfo = nullptr;
@@ -312,8 +314,14 @@ struct Ctx {
   bool timing_on = true;
   // last-call block trace: fetched from the workspace when zada_last_blocks asks for it
   uint32_t last_nblocks = 0;
+  bool trace_stale = false;                          // the range analysed last took the lazy path: cut_trace is not its trace (entropy_trace makes it).
+                                                     // INVARIANT: while it is set, rg describes atoms that still lie in ws.ea_atoms (and ws.ftab for a batch): whatever
+                                                     // writes those arrays for another purpose either starts a new Range (range_open, batch_launch, lzma_batch_launch: rg =
+                                                     // Range (), analyzed false, so entropy_trace does nothing) or goes through ensure_entropy_workspace, which clears the flag
+  uint64_t descr_l3 = 0, descr_excluded = 0, descr_late = 0;   // last call, lazy path (last_timing: #descr_l3_points, #descr_excluded, #descr_late)
   // knobs read from the environment once, when the context is created (tests set them before zada_create, or call
   // zada_set_knob)
+  int knob_descr_lazy = 1;          // "descr_lazy" / ZADA_DESCR_LAZY: Deflate_3 builds the descriptors of the windows tested at step level 3 only where a bound on the distance does not decide (zada_descr_bound.h); 0: every window's descriptor, as rounds 1-7.  Same bytes
   int knob_budget = -1;             // ZADA_BUDGET: rounds of chain steps per position in the first match pass (0 = unbounded, -1 = default)
   int knob_max_demand_rounds = 12;  // ZADA_MAX_DEMAND_ROUNDS
   int knob_atoms_pct = 50;          // "atoms_pct": the atom arrays of a stream start with room for this many atoms per 100 input bytes (they grow when a shard has more: one atom per byte is the worst case, the benchmark stream has 0.3)
@@ -529,6 +537,7 @@ bool lzma_batch_refused(Ctx *c, const DevBatch &D);                             
 int batch_geometry(Ctx *c, uint32_t E, const uint32_t *d_total_atoms);
 int entropy_analyze(Ctx *c);
 int entropy_choose(Ctx *c);
+int entropy_trace(Ctx *c);
 int entropy_emit(Ctx *c, uint8_t *d_out);
 int crc_launch(Ctx *c, const uint8_t *d_in, uint64_t n);
 int crc_finish(Ctx *c, uint64_t n, uint32_t *crc_inout);
