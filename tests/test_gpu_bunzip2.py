@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import _bunzip2
+import _readers
 from _bunzip2 import E_DATA, model_bunzip2
 from _common import product, silesia_mix
 
@@ -357,3 +358,12 @@ def test_archive_of_zipfile_and_what_the_reader_refuses(encoder, mix2):
         assert isinstance(t[name], za.ZadaError) and all(x is None for k, x in t.items() if k not in (name, "lzma.bin"))
     with pytest.raises(za.UnsupportedMethod):
         za.UnZip(encoder).extract(za.ZipInfo.load(arc), what="one")
+
+
+def test_argument_checks_come_first(encoder):
+    _readers.argument_checks(encoder, "bunzip2")
+
+
+def test_several_launch_groups(encoder):
+    """bunzip_batch_mib = 16 (8 MiB of streams and outputs per group): the entries go through several groups; bz2 says what every entry holds."""
+    _readers.several_launch_groups(encoder, "bunzip2")

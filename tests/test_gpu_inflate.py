@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import _inflate
+import _readers
 from _inflate import E_DATA, model_inflate
 from _common import product, silesia_mix
 from test_inflate_model import deflate64_cases, deflate64_fixed
@@ -394,3 +395,12 @@ def test_crypt_decode_batch_undoes_encode(encoder, mix):
         M.im_crypt_decode(kk, buf.ctypes.data, len(c))
         assert buf[:len(c)].tobytes() == d and tuple(kk) == kc
     assert encoder.crypt_decode_batch([], []) == []
+
+
+def test_argument_checks_come_first(encoder):
+    _readers.argument_checks(encoder, "inflate")
+
+
+def test_several_launch_groups(encoder):
+    """batch_mib = 1: the entries go through several groups; zlib says what every entry holds."""
+    _readers.several_launch_groups(encoder, "inflate")

@@ -11,6 +11,7 @@ import zlib
 import numpy as np
 import pytest
 
+import _readers
 import _unlzma
 from _unlzma import E_DATA, model_unlzma
 from _common import product, silesia_mix
@@ -392,3 +393,12 @@ def test_archive_of_zipfile_and_one_flipped_byte(encoder, mix2):
     p, size, crc, sha = _unlzma.reference_payload()
     rc, out, ol, used, reg = encoder.unlzma_batch([p], [size], [False])[0]
     assert (rc, ol, used, reg ^ 0xFFFFFFFF) == (0, size, len(p), crc) and hashlib.sha256(out).hexdigest() == sha
+
+
+def test_argument_checks_come_first(encoder):
+    _readers.argument_checks(encoder, "unlzma")
+
+
+def test_several_launch_groups(encoder):
+    """batch_mib = 1: the entries go through several groups; liblzma says what every entry holds."""
+    _readers.several_launch_groups(encoder, "unlzma")

@@ -818,23 +818,71 @@ class Encoder:
         mv = memoryview(arena)
         return [(bytes(mv[int(offs[i]):int(offs[i]) + int(lens[i])]), tuple(int(x) for x in ks[i])) for i in range(cnt)]
 
+    # ---- what the methods of the four readers share: fn is the entry point of the C ABI, `lead` its arguments in front of the stream, `mid` those
+    # between cap and out_len; `who` its name in the error texts ----
+    def _reader_single(self, fn, who, payload, cap, crc, grow, lead=(), mid=()):
+        """One stream on host buffers.  grow: the cap doubles while the only complaint is "output beyond cap"."""
+        n = len(payload)
+        while True:
+            out = ctypes.create_string_buffer(max(cap, 1))
+            ol, iu, c = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(crc)
+            rc = fn(self.ctx, *lead, _addr(payload) if n else None, n, ctypes.addressof(out), cap, *mid, ctypes.byref(ol), ctypes.byref(iu), ctypes.byref(c))
+            if rc == 0:
+                return out.raw[:ol.value], iu.value, c.value
+            if rc == E_DATA and grow and b"output beyond cap" in self.lib.zada_last_error(self.ctx):
+                cap *= 2
+                continue
+            self._err(rc, who)
+
+    def _reader_device(self, fn, who, d_in_ptr, n_in, d_out_ptr, cap, crc, lead=(), mid=()):
+        ol, iu, c = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(crc)
+        rc = fn(self.ctx, *lead, d_in_ptr, n_in, d_out_ptr, cap, *mid, ctypes.byref(ol), ctypes.byref(iu), ctypes.byref(c))
+        if rc != 0:
+            self._err(rc, who)
+        return ol.value, iu.value, c.value
+
+    def _reader_batch(self, who, payloads, caps, crc, deliver, call):
+        """caps: one per payload, as a contiguous numpy array of 64-bit values.  call (count, in pointers, lengths, out pointers or None, caps, out_len,
+        in_used, crc, rc): the batch call of the C ABI on the addresses of these arrays, with the format's own arrays spliced in."""
+        import numpy as np
+        cnt = len(payloads)
+        lens = np.fromiter((len(d) for d in payloads), dtype=np.uint64, count=cnt)
+        keep = [d if len(d) else b"\0" for d in payloads]
+        ins = np.fromiter((_addr(d) for d in keep), dtype=np.uint64, count=cnt)
+        total = sum(int(x) for x in caps)                  # (Python integers: the sizes may come from a directory that lies)
+        try:
+            if total >= 1 << 40:
+                raise MemoryError
+            arena = np.empty(total + 1 if deliver else 1, dtype=np.uint8)
+        except (MemoryError, ValueError):
+            raise ZadaError("%s: %d bytes of output are promised -- more than this machine holds" % (who, total))
+        offs = np.concatenate(([0], np.cumsum(caps)[:-1])).astype(np.uint64)
+        outp = (arena.ctypes.data + offs).astype(np.uint64)
+        ols, ius = np.zeros(cnt, dtype=np.uint64), np.zeros(cnt, dtype=np.uint64)
+        crcs = np.full(cnt, crc, dtype=np.uint32)
+        rcs = np.zeros(cnt, dtype=np.int32)
+        worst = call(cnt, ins.ctypes.data, lens.ctypes.data, outp.ctypes.data if deliver else None, caps.ctypes.data, ols.ctypes.data, ius.ctypes.data,
+                     crcs.ctypes.data, rcs.ctypes.data)
+        if worst < 0 and worst != E_DATA:
+            self._err(worst, "zada_" + who)
+        mv = memoryview(arena)
+        return [(int(rcs[i]), bytes(mv[int(offs[i]):int(offs[i]) + int(ols[i])]) if deliver and rcs[i] == 0 else None, int(ols[i]), int(ius[i]), int(crcs[i]))
+                for i in range(cnt)]
+
+    def _reader_last_records(self, fn, width, *lead):
+        import numpy as np
+        n = fn(self.ctx, *lead, None, 0)
+        a = np.zeros(max(int(n), 1), dtype=np.uint64)
+        fn(self.ctx, *lead, a.ctypes.data, int(n))
+        return a[:int(n)].reshape(-1, width)
+
     # ---- the reader: UnZip.Decompress.Inflate (unzip-decompress.adb:1463-1889; include/zada.h "Inflate") ----
     def inflate(self, payload, size=None, format=8, crc=0xFFFFFFFF):
         """One raw Deflate (format 8) or Deflate64 (9) stream.  size: the uncompressed size the directory promises (a stream that writes more is a
         DataError); None = unknown: the output buffer starts at four times the payload and doubles while the only complaint is "output beyond cap".
         Returns (bytes, input bytes used, running CRC register).  Raises DataError."""
-        n = len(payload)
-        cap = max(4 * n, 256) if size is None else int(size)
-        while True:
-            out = ctypes.create_string_buffer(max(cap, 1))
-            ol, iu, c = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(crc)
-            rc = self.lib.zada_inflate(self.ctx, format, _addr(payload) if n else None, n, ctypes.addressof(out), cap, ctypes.byref(ol), ctypes.byref(iu), ctypes.byref(c))
-            if rc == 0:
-                return out.raw[:ol.value], iu.value, c.value
-            if rc == E_DATA and size is None and b"output beyond cap" in self.lib.zada_last_error(self.ctx):
-                cap *= 2
-                continue
-            self._err(rc, "zada_inflate")
+        cap = max(4 * len(payload), 256) if size is None else int(size)
+        return self._reader_single(self.lib.zada_inflate, "zada_inflate", payload, cap, crc, size is None, lead=(format,))
 
     def inflate_batch(self, payloads, sizes, formats=8, crc=0xFFFFFFFF, deliver=True):
         """Independent streams (one per Zip entry), one wave each, in one launch per group of "batch_mib".  sizes [i] = cap of entry i; formats: one
@@ -845,39 +893,15 @@ class Encoder:
         if cnt == 0:
             return []
         fm = np.full(cnt, formats, dtype=np.int32) if np.isscalar(formats) else np.ascontiguousarray(np.array(formats, dtype=np.int32))
-        lens = np.fromiter((len(d) for d in payloads), dtype=np.uint64, count=cnt)
         caps = np.ascontiguousarray(np.array(sizes, dtype=np.uint64))
         if len(caps) != cnt or len(fm) != cnt:
             raise ZadaError("inflate_batch: one size and one format per payload")
-        keep = [d if len(d) else b"\0" for d in payloads]
-        ins = np.fromiter((_addr(d) for d in keep), dtype=np.uint64, count=cnt)
-        offs = np.concatenate(([0], np.cumsum(caps)[:-1])).astype(np.uint64)
-        total = sum(int(x) for x in caps)                  # (Python integers: the sizes may come from a directory that lies)
-        try:
-            if total >= 1 << 40:
-                raise MemoryError
-            arena = np.empty(total + 1 if deliver else 1, dtype=np.uint8)
-        except (MemoryError, ValueError):
-            raise ZadaError("inflate_batch: %d bytes of output are promised -- more than this machine holds" % total)
-        outp = (arena.ctypes.data + offs).astype(np.uint64)
-        ols, ius = np.zeros(cnt, dtype=np.uint64), np.zeros(cnt, dtype=np.uint64)
-        crcs = np.full(cnt, crc, dtype=np.uint32)
-        rcs = np.zeros(cnt, dtype=np.int32)
-        worst = self.lib.zada_inflate_batch(self.ctx, cnt, fm.ctypes.data, ins.ctypes.data, lens.ctypes.data, outp.ctypes.data if deliver else None, caps.ctypes.data,
-                                            ols.ctypes.data, ius.ctypes.data, crcs.ctypes.data, rcs.ctypes.data)
-        if worst < 0 and worst != E_DATA:
-            self._err(worst, "zada_inflate_batch")
-        mv = memoryview(arena)
-        return [(int(rcs[i]), bytes(mv[int(offs[i]):int(offs[i]) + int(ols[i])]) if deliver and rcs[i] == 0 else None, int(ols[i]), int(ius[i]), int(crcs[i]))
-                for i in range(cnt)]
+        return self._reader_batch("inflate_batch", payloads, caps, crc, deliver,
+                                  lambda cnt, ins, lens, *rest: self.lib.zada_inflate_batch(self.ctx, cnt, fm.ctypes.data, ins, lens, *rest))
 
     def inflate_device(self, d_in_ptr, n_in, d_out_ptr, cap, format=8, crc=0xFFFFFFFF):
         """Device-resident variant (HBM addresses of any alignment).  Returns (bytes written, input bytes used, running CRC register); raises DataError."""
-        ol, iu, c = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(crc)
-        rc = self.lib.zada_inflate_device(self.ctx, format, d_in_ptr, n_in, d_out_ptr, cap, ctypes.byref(ol), ctypes.byref(iu), ctypes.byref(c))
-        if rc != 0:
-            self._err(rc, "zada_inflate_device")
-        return ol.value, iu.value, c.value
+        return self._reader_device(self.lib.zada_inflate_device, "zada_inflate_device", d_in_ptr, n_in, d_out_ptr, cap, crc, lead=(format,))
 
     # ---- one large Deflate stream on many waves (include/zada.h "One large Deflate stream"; experimental) ----
     INFLATE_PAR_REASONS = ("none", "damaged", "repairs", "single chunk", "format", "memory")
@@ -920,18 +944,8 @@ class Encoder:
         """One BZip2 stream (Zip format 12), its blocks in parallel.  size: the uncompressed size the directory promises (a stream that writes more
         is a DataError); None = unknown: the output buffer starts at eight times the payload and doubles while the only complaint is "output beyond
         cap".  Returns (bytes, input bytes used, running CRC register).  Raises DataError."""
-        n = len(payload)
-        cap = max(8 * n, 4096) if size is None else int(size)
-        while True:
-            out = ctypes.create_string_buffer(max(cap, 1))
-            ol, iu, c = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(crc)
-            rc = self.lib.zada_bunzip2(self.ctx, _addr(payload) if n else None, n, ctypes.addressof(out), cap, ctypes.byref(ol), ctypes.byref(iu), ctypes.byref(c))
-            if rc == 0:
-                return out.raw[:ol.value], iu.value, c.value
-            if rc == E_DATA and size is None and b"output beyond cap" in self.lib.zada_last_error(self.ctx):
-                cap *= 2
-                continue
-            self._err(rc, "zada_bunzip2")
+        cap = max(8 * len(payload), 4096) if size is None else int(size)
+        return self._reader_single(self.lib.zada_bunzip2, "zada_bunzip2", payload, cap, crc, size is None)
 
     def bunzip2_batch(self, payloads, sizes, crc=0xFFFFFFFF, deliver=True):
         """Independent BZip2 streams (one per Zip entry): the blocks of all of them through the same launches, in groups bounded by
@@ -941,48 +955,19 @@ class Encoder:
         cnt = len(payloads)
         if cnt == 0:
             return []
-        lens = np.fromiter((len(d) for d in payloads), dtype=np.uint64, count=cnt)
         caps = np.ascontiguousarray(np.array(sizes, dtype=np.uint64))
         if len(caps) != cnt:
             raise ZadaError("bunzip2_batch: one size per payload")
-        keep = [d if len(d) else b"\0" for d in payloads]
-        ins = np.fromiter((_addr(d) for d in keep), dtype=np.uint64, count=cnt)
-        offs = np.concatenate(([0], np.cumsum(caps)[:-1])).astype(np.uint64)
-        total = sum(int(x) for x in caps)                  # (Python integers: the sizes may come from a directory that lies)
-        try:
-            if total >= 1 << 40:
-                raise MemoryError
-            arena = np.empty(total + 1 if deliver else 1, dtype=np.uint8)
-        except (MemoryError, ValueError):
-            raise ZadaError("bunzip2_batch: %d bytes of output are promised -- more than this machine holds" % total)
-        outp = (arena.ctypes.data + offs).astype(np.uint64)
-        ols, ius = np.zeros(cnt, dtype=np.uint64), np.zeros(cnt, dtype=np.uint64)
-        crcs = np.full(cnt, crc, dtype=np.uint32)
-        rcs = np.zeros(cnt, dtype=np.int32)
-        worst = self.lib.zada_bunzip2_batch(self.ctx, cnt, ins.ctypes.data, lens.ctypes.data, outp.ctypes.data if deliver else None, caps.ctypes.data,
-                                            ols.ctypes.data, ius.ctypes.data, crcs.ctypes.data, rcs.ctypes.data)
-        if worst < 0 and worst != E_DATA:
-            self._err(worst, "zada_bunzip2_batch")
-        mv = memoryview(arena)
-        return [(int(rcs[i]), bytes(mv[int(offs[i]):int(offs[i]) + int(ols[i])]) if deliver and rcs[i] == 0 else None, int(ols[i]), int(ius[i]), int(crcs[i]))
-                for i in range(cnt)]
+        return self._reader_batch("bunzip2_batch", payloads, caps, crc, deliver, lambda *a: self.lib.zada_bunzip2_batch(self.ctx, *a))
 
     def bunzip2_last_records(self, blocks=False):
         """The last bunzip2* call: per entry (rule, block, bit, 0) -- or, blocks = True, per block of the chains (entry, symbols, origin, stored CRC,
         end bit) -- as a numpy array of 64-bit values."""
-        import numpy as np
-        n = self.lib.zada_bunzip2_last_records(self.ctx, int(blocks), None, 0)
-        a = np.zeros(max(int(n), 1), dtype=np.uint64)
-        self.lib.zada_bunzip2_last_records(self.ctx, int(blocks), a.ctypes.data, int(n))
-        return a[:int(n)].reshape(-1, 5 if blocks else 4)
+        return self._reader_last_records(self.lib.zada_bunzip2_last_records, 5 if blocks else 4, int(blocks))
 
     def bunzip2_device(self, d_in_ptr, n_in, d_out_ptr, cap, crc=0xFFFFFFFF):
         """Device-resident variant (HBM addresses of any alignment).  Returns (bytes written, input bytes used, running CRC register); raises DataError."""
-        ol, iu, c = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(crc)
-        rc = self.lib.zada_bunzip2_device(self.ctx, d_in_ptr, n_in, d_out_ptr, cap, ctypes.byref(ol), ctypes.byref(iu), ctypes.byref(c))
-        if rc != 0:
-            self._err(rc, "zada_bunzip2_device")
-        return ol.value, iu.value, c.value
+        return self._reader_device(self.lib.zada_bunzip2_device, "zada_bunzip2_device", d_in_ptr, n_in, d_out_ptr, cap, crc)
 
     # ---- the reader: LZMA.Decoding.Decode (lzma-decoding.adb; include/zada.h "LZMA.Decoding") ----
     def unlzma(self, payload, cap=None, eos=True, crc=0xFFFFFFFF):
@@ -990,21 +975,10 @@ class Encoder:
         promises (a stream that writes more is a DataError; one without marker, eos = False, ends there); None = unknown (eos = True only): the
         output buffer starts at eight times the payload and doubles while the only complaint is "output beyond cap".  eos: bit 1 of the entry's
         general-purpose flags -- the stream ends on a marker.  Returns (bytes, input bytes used, running CRC register).  Raises DataError."""
-        n = len(payload)
         if cap is None and not eos:
             raise ZadaError("unlzma: a stream without marker needs its size")
-        size, cap = cap, (max(8 * n, 4096) if cap is None else int(cap))
-        while True:
-            out = ctypes.create_string_buffer(max(cap, 1))
-            ol, iu, c = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(crc)
-            rc = self.lib.zada_unlzma(self.ctx, _addr(payload) if n else None, n, ctypes.addressof(out), cap, int(bool(eos)), ctypes.byref(ol), ctypes.byref(iu),
-                                      ctypes.byref(c))
-            if rc == 0:
-                return out.raw[:ol.value], iu.value, c.value
-            if rc == E_DATA and size is None and b"output beyond cap" in self.lib.zada_last_error(self.ctx):
-                cap *= 2
-                continue
-            self._err(rc, "zada_unlzma")
+        size, cap = cap, (max(8 * len(payload), 4096) if cap is None else int(cap))
+        return self._reader_single(self.lib.zada_unlzma, "zada_unlzma", payload, cap, crc, size is None, mid=(int(bool(eos)),))
 
     def unlzma_batch(self, payloads, caps, eos=True, crc=0xFFFFFFFF, deliver=True):
         """Independent LZMA payloads (one per Zip entry), one wave per entry, in groups bounded by "batch_mib" (and, for literal tables in HBM,
@@ -1014,65 +988,30 @@ class Encoder:
         cnt = len(payloads)
         if cnt == 0:
             return []
-        lens = np.fromiter((len(d) for d in payloads), dtype=np.uint64, count=cnt)
         caps = np.ascontiguousarray(np.array(caps, dtype=np.uint64))
         if len(caps) != cnt:
             raise ZadaError("unlzma_batch: one cap per payload")
         flags = np.full(cnt, int(bool(eos)), dtype=np.int32) if isinstance(eos, (bool, int)) else np.ascontiguousarray(np.array([int(bool(x)) for x in eos], dtype=np.int32))
         if len(flags) != cnt:
             raise ZadaError("unlzma_batch: one eos flag per payload")
-        keep = [d if len(d) else b"\0" for d in payloads]
-        ins = np.fromiter((_addr(d) for d in keep), dtype=np.uint64, count=cnt)
-        offs = np.concatenate(([0], np.cumsum(caps)[:-1])).astype(np.uint64)
-        total = sum(int(x) for x in caps)                  # (Python integers: the sizes may come from a directory that lies)
-        try:
-            if total >= 1 << 40:
-                raise MemoryError
-            arena = np.empty(total + 1 if deliver else 1, dtype=np.uint8)
-        except (MemoryError, ValueError):
-            raise ZadaError("unlzma_batch: %d bytes of output are promised -- more than this machine holds" % total)
-        outp = (arena.ctypes.data + offs).astype(np.uint64)
-        ols, ius = np.zeros(cnt, dtype=np.uint64), np.zeros(cnt, dtype=np.uint64)
-        crcs = np.full(cnt, crc, dtype=np.uint32)
-        rcs = np.zeros(cnt, dtype=np.int32)
-        worst = self.lib.zada_unlzma_batch(self.ctx, cnt, ins.ctypes.data, lens.ctypes.data, outp.ctypes.data if deliver else None, caps.ctypes.data,
-                                           flags.ctypes.data, ols.ctypes.data, ius.ctypes.data, crcs.ctypes.data, rcs.ctypes.data)
-        if worst < 0 and worst != E_DATA:
-            self._err(worst, "zada_unlzma_batch")
-        mv = memoryview(arena)
-        return [(int(rcs[i]), bytes(mv[int(offs[i]):int(offs[i]) + int(ols[i])]) if deliver and rcs[i] == 0 else None, int(ols[i]), int(ius[i]), int(crcs[i]))
-                for i in range(cnt)]
+        return self._reader_batch("unlzma_batch", payloads, caps, crc, deliver,
+                                  lambda cnt, ins, lens, outp, caps, *rest: self.lib.zada_unlzma_batch(self.ctx, cnt, ins, lens, outp, caps, flags.ctypes.data, *rest))
 
     def unlzma_last_records(self):
         """The last unlzma* call: per entry (rule broken or 0, input byte, output position, how the stream ended -- 1: on a marker, 2: without, 0: it did
         not) as a numpy array of 64-bit values."""
-        import numpy as np
-        n = self.lib.zada_unlzma_last_records(self.ctx, None, 0)
-        a = np.zeros(max(int(n), 1), dtype=np.uint64)
-        self.lib.zada_unlzma_last_records(self.ctx, a.ctypes.data, int(n))
-        return a[:int(n)].reshape(-1, 4)
+        return self._reader_last_records(self.lib.zada_unlzma_last_records, 4)
 
     def unlzma_device(self, d_in_ptr, n_in, d_out_ptr, cap, eos=True, crc=0xFFFFFFFF):
         """Device-resident variant (HBM addresses of any alignment).  Returns (bytes written, input bytes used, running CRC register); raises DataError."""
-        ol, iu, c = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(crc)
-        rc = self.lib.zada_unlzma_device(self.ctx, d_in_ptr, n_in, d_out_ptr, cap, int(bool(eos)), ctypes.byref(ol), ctypes.byref(iu), ctypes.byref(c))
-        if rc != 0:
-            self._err(rc, "zada_unlzma_device")
-        return ol.value, iu.value, c.value
+        return self._reader_device(self.lib.zada_unlzma_device, "zada_unlzma_device", d_in_ptr, n_in, d_out_ptr, cap, crc, mid=(int(bool(eos)),))
 
     # ---- the reader: Unshrink, Unreduce, Explode (unzip-decompress.adb:590-1418; include/zada.h "Unshrink, Unreduce and Explode") ----
     def unlegacy(self, payload, cap, method, flags=0, crc=0xFFFFFFFF):
         """One Shrink (method 1), Reduce (2 .. 5) or Implode (6) payload.  cap: the uncompressed size the directory promises -- the stream ends when cap
         bytes are out, none of the formats has an end code.  flags: the entry's general-purpose flags (Implode: bit 1 = 8 KiB dictionary, bit 2 = three
         trees).  Returns (bytes, input bytes used, running CRC register).  Raises DataError."""
-        n, cap = len(payload), int(cap)
-        out = ctypes.create_string_buffer(max(cap, 1))
-        ol, iu, c = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(crc)
-        rc = self.lib.zada_unlegacy(self.ctx, int(method), int(flags), _addr(payload) if n else None, n, ctypes.addressof(out), cap, ctypes.byref(ol), ctypes.byref(iu),
-                                    ctypes.byref(c))
-        if rc != 0:
-            self._err(rc, "zada_unlegacy")
-        return out.raw[:ol.value], iu.value, c.value
+        return self._reader_single(self.lib.zada_unlegacy, "zada_unlegacy", payload, int(cap), crc, False, lead=(int(method), int(flags)))
 
     def unlegacy_batch(self, streams, caps, methods, flags=None, crc=0xFFFFFFFF, deliver=True):
         """Independent Shrink / Reduce / Implode payloads (one per Zip entry), one wave per entry, in groups bounded by "batch_mib"; one batch may mix
@@ -1083,7 +1022,6 @@ class Encoder:
         cnt = len(streams)
         if cnt == 0:
             return []
-        lens = np.fromiter((len(d) for d in streams), dtype=np.uint64, count=cnt)
         caps = np.ascontiguousarray(np.array(caps, dtype=np.uint64))
         if len(caps) != cnt:
             raise ZadaError("unlegacy_batch: one cap per stream")
@@ -1092,43 +1030,17 @@ class Encoder:
                else np.ascontiguousarray(np.array([int(f) & 0xFF for f in flags], dtype=np.uint8)))
         if len(meth) != cnt or len(flg) != cnt:
             raise ZadaError("unlegacy_batch: one method and one flags value per stream")
-        total = sum(int(x) for x in caps)                  # (Python integers: the sizes may come from a directory that lies)
-        if total >= 1 << 40:
-            raise ZadaError("unlegacy_batch: %d bytes of output are promised -- more than this machine holds" % total)
-        keep = [d if len(d) else b"\0" for d in streams]
-        ins = np.fromiter((_addr(d) for d in keep), dtype=np.uint64, count=cnt)
-        offs = np.concatenate(([0], np.cumsum(caps)[:-1])).astype(np.uint64)
-        try:
-            arena = np.empty(total + 1 if deliver else 1, dtype=np.uint8)
-        except (MemoryError, ValueError):
-            raise ZadaError("unlegacy_batch: %d bytes of output are promised -- more than this machine holds" % total)
-        outp = (arena.ctypes.data + offs).astype(np.uint64)
-        ols, ius = np.zeros(cnt, dtype=np.uint64), np.zeros(cnt, dtype=np.uint64)
-        crcs = np.full(cnt, crc, dtype=np.uint32)
-        rcs = np.zeros(cnt, dtype=np.int32)
-        worst = self.lib.zada_unlegacy_batch(self.ctx, cnt, ins.ctypes.data, lens.ctypes.data, outp.ctypes.data if deliver else None, caps.ctypes.data,
-                                             meth.ctypes.data, flg.ctypes.data, ols.ctypes.data, ius.ctypes.data, crcs.ctypes.data, rcs.ctypes.data)
-        if worst < 0 and worst != E_DATA:
-            self._err(worst, "zada_unlegacy_batch")
-        mv = memoryview(arena)
-        return [(int(rcs[i]), bytes(mv[int(offs[i]):int(offs[i]) + int(ols[i])]) if deliver and rcs[i] == 0 else None, int(ols[i]), int(ius[i]), int(crcs[i]))
-                for i in range(cnt)]
+        return self._reader_batch("unlegacy_batch", streams, caps, crc, deliver,
+                                  lambda cnt, ins, lens, outp, caps, *rest: self.lib.zada_unlegacy_batch(self.ctx, cnt, ins, lens, outp, caps, meth.ctypes.data,
+                                                                                                     flg.ctypes.data, *rest))
 
     def unlegacy_last_records(self):
         """The last unlegacy* call: per entry (rule broken or 0, input byte, output position, 0) as a numpy array of 64-bit values."""
-        import numpy as np
-        n = self.lib.zada_unlegacy_last_records(self.ctx, None, 0)
-        a = np.zeros(max(int(n), 1), dtype=np.uint64)
-        self.lib.zada_unlegacy_last_records(self.ctx, a.ctypes.data, int(n))
-        return a[:int(n)].reshape(-1, 4)
+        return self._reader_last_records(self.lib.zada_unlegacy_last_records, 4)
 
     def unlegacy_device(self, d_in_ptr, n_in, d_out_ptr, cap, method, flags=0, crc=0xFFFFFFFF):
         """Device-resident variant (HBM addresses of any alignment).  Returns (bytes written, input bytes used, running CRC register); raises DataError."""
-        ol, iu, c = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(crc)
-        rc = self.lib.zada_unlegacy_device(self.ctx, int(method), int(flags), d_in_ptr, n_in, d_out_ptr, cap, ctypes.byref(ol), ctypes.byref(iu), ctypes.byref(c))
-        if rc != 0:
-            self._err(rc, "zada_unlegacy_device")
-        return ol.value, iu.value, c.value
+        return self._reader_device(self.lib.zada_unlegacy_device, "zada_unlegacy_device", d_in_ptr, n_in, d_out_ptr, cap, crc, lead=(int(method), int(flags)))
 
     # ---- the archive reader on device memory (include/zada.h "an archive that lies in device memory") ----
     @staticmethod

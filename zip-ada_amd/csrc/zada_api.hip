@@ -32,6 +32,20 @@ int hip_check(Ctx *c, hipError_t e, const char *what) {
   return ZADA_E_HIP_;
 }
 
+int dev_grow(Ctx *c, DevBuf &b, uint64_t bytes, const char *what) {
+  if (b.p && b.cap >= bytes) return 0;
+  hipStreamSynchronize(c->stream);
+  dev_free(b);
+  const uint64_t want = ((bytes < (1u << 20) ? (1u << 20) : bytes) + 65535) & ~65535ull;
+  if (hipMalloc((void **)&b.p, want) != hipSuccess) { (void)hipGetLastError(); if (what) c->err = what; return ZADA_E_NOMEM; }
+  b.cap = want;
+  return 0;
+}
+void dev_free(DevBuf &b) {
+  if (b.p) hipFree(b.p);
+  b.p = nullptr; b.cap = 0;
+}
+
 void Ctx::tbegin() {
   marks.clear();
   timing.clear();

@@ -20,6 +20,7 @@
 #include <vector>
 #include "../../include/zada.h"
 #include "zada_internal.h"
+#include "zada_reader_host.h"
 #include "zada_bunzip2_logic.h"
 
 struct zada_ctx { zada::Ctx c; };
@@ -410,13 +411,10 @@ __global__ void __launch_bounds__(BZD_WAVE) k_bzd_crc(BzdBlk *blk, const BzdCrcO
 }
 
 // ---- host side ----
-struct BzdBuf { uint8_t *p = nullptr; uint64_t cap = 0; };
-struct BzdState {
+struct BzdState : ReaderState {           // (tabs: jobs and offsets; last_entries: rule, block, bit, blocks of its chain)
   BzdCrcOps *d_ops = nullptr;
-  uint32_t *d_counter = nullptr;
-  BzdBuf tabs, cands, wa, wb, arena;      // jobs and offsets; candidates; a round's slots and records; a round's later stages; a group's inputs and outputs
-  std::vector<uint64_t> last_entries;     // the last call, per entry: rule, block, bit, blocks of its chain (zada_bunzip2_last_records)
-  std::vector<uint64_t> last_blocks;      // ... per block of a chain, in order: entry, symbols, origin, stored CRC, end bit
+  DevBuf cands, wa, wb;                   // candidates; a round's slots and records; a round's later stages
+  std::vector<uint64_t> last_blocks;      // the last call, per block of a chain, in order: entry, symbols, origin, stored CRC, end bit (zada_bunzip2_last_records)
 };
 
 static BzdState *bzd_state(Ctx *c) {
@@ -445,20 +443,10 @@ static BzdState *bzd_state(Ctx *c) {
 void bunzip2_destroy(Ctx *c) {
   BzdState *S = (BzdState *)c->bzd;
   if (!S) return;
-  for (BzdBuf *b : {&S->tabs, &S->cands, &S->wa, &S->wb, &S->arena}) if (b->p) hipFree(b->p);
+  for (DevBuf *b : {&S->tabs, &S->cands, &S->wa, &S->wb, &S->arena}) dev_free(*b);
   hipFree(S->d_ops); hipFree(S->d_counter);
   delete S;
   c->bzd = nullptr;
-}
-static int bzd_grow(Ctx *c, BzdBuf &b, uint64_t bytes, const char *what) {
-  if (b.p && b.cap >= bytes) return 0;
-  hipStreamSynchronize(c->stream);
-  if (b.p) hipFree(b.p);
-  b.p = nullptr; b.cap = 0;
-  const uint64_t want = ((bytes < (1u << 20) ? (1u << 20) : bytes) + 65535) & ~65535ull;
-  if (hipMalloc((void **)&b.p, want) != hipSuccess) { (void)hipGetLastError(); c->err = what; return ZADA_E_NOMEM; }
-  b.cap = want;
-  return 0;
 }
 // pieces of one device buffer, each at a multiple of 256
 struct BzdCarve {
@@ -491,7 +479,7 @@ static void bzd_no_magic(BzdEnt &e, const BzdJob &J) {
 #define BZD_HIP(call, what) do { if (hip_check(c, (call), what)) return ZADA_E_HIP_; } while (0)
 
 // E jobs (device addresses) through the launches; res [E] receives the records
-static int bzd_run(Ctx *c, BzdState *S, const std::vector<BzdJob> &jobs, const uint32_t *crc_in, std::vector<BzdResult> &res, uint32_t entry0 = 0) {
+static int bzd_run(Ctx *c, BzdState *S, const std::vector<BzdJob> &jobs, const uint32_t *crc_in, std::vector<BzdResult> &res, uint32_t entry0) {
   const uint32_t E = (uint32_t)jobs.size();
   res.assign(E, BzdResult{});
   if (E == 0) return 0;
@@ -504,7 +492,7 @@ static int bzd_run(Ctx *c, BzdState *S, const std::vector<BzdJob> &jobs, const u
   std::vector<uint32_t> hdr(E, 0);
   BzdCarve tc;
   const uint64_t o_jobs = tc.take((uint64_t)E * sizeof(BzdJob)), o_boff = tc.take((uint64_t)(E + 1) * 8), o_hdr = tc.take((uint64_t)E * 4);
-  int rc = bzd_grow(c, S->tabs, tc.at, "hipMalloc (bunzip2 tables)");
+  int rc = dev_grow(c, S->tabs, tc.at, "hipMalloc (bunzip2 tables)");
   if (rc) return rc;
   const BzdJob *d_jobs = (const BzdJob *)(S->tabs.p + o_jobs);
   hipMemcpyAsync(S->tabs.p + o_jobs, jobs.data(), (size_t)E * sizeof(BzdJob), hipMemcpyHostToDevice, st);
@@ -515,7 +503,7 @@ static int bzd_run(Ctx *c, BzdState *S, const std::vector<BzdJob> &jobs, const u
     uint64_t cap = total / 32 + 4ull * E + 1024;
     for (int attempt = 0; attempt < 2; attempt++) {
       if (cap >= (1ull << 32)) { c->err = "bunzip2: too many block candidates"; return ZADA_E_TOO_LARGE; }
-      rc = bzd_grow(c, S->cands, cap * sizeof(BzdCand), "hipMalloc (bunzip2 candidates)");
+      rc = dev_grow(c, S->cands, cap * sizeof(BzdCand), "hipMalloc (bunzip2 candidates)");
       if (rc) return rc;
       hipMemsetAsync(S->d_counter, 0, 4, st);
       const uint64_t wgs = (total + 255) / 256;
@@ -574,7 +562,7 @@ static int bzd_run(Ctx *c, BzdState *S, const std::vector<BzdJob> &jobs, const u
     BzdCarve wa;
     const uint64_t a_cand = wa.take((uint64_t)R * sizeof(BzdCand)), a_order = wa.take((uint64_t)R * 4), a_soff = wa.take((uint64_t)R * 8), a_scap = wa.take((uint64_t)R * 4),
                    a_rec = wa.take((uint64_t)R * sizeof(BzdRec)), a_counts = wa.take((uint64_t)R * 1024), a_slots = wa.take(slots + 256);
-    rc = bzd_grow(c, S->wa, wa.at, "hipMalloc (bunzip2 slots)");
+    rc = dev_grow(c, S->wa, wa.at, "hipMalloc (bunzip2 slots)");
     if (rc) return rc;
     uint8_t *A = S->wa.p;
     hipMemcpyAsync(A + a_cand, rc_cands.data(), (size_t)R * sizeof(BzdCand), hipMemcpyHostToDevice, st);
@@ -623,7 +611,7 @@ static int bzd_run(Ctx *c, BzdState *S, const std::vector<BzdJob> &jobs, const u
       const uint64_t b_blk = wb.take((uint64_t)NB * sizeof(BzdBlk)), b_hist = wb.take((uint64_t)nchunk * 1024), b_tt = wb.take(sym * 4 + 16), b_T = wb.take(sym + 16),
                      b_len = wb.take((uint64_t)nsplit * 4), b_succ = wb.take((uint64_t)nsplit * 4), b_rank = wb.take((uint64_t)nsplit * 4),
                      b_rlen = wb.take((uint64_t)nrc * 20), b_rexit = wb.take((uint64_t)nrc * 5), b_rentry = wb.take(nrc), b_roff = wb.take((uint64_t)nrc * 4);
-      rc = bzd_grow(c, S->wb, wb.at, "hipMalloc (bunzip2 inverse BWT)");
+      rc = dev_grow(c, S->wb, wb.at, "hipMalloc (bunzip2 inverse BWT)");
       if (rc) return rc;
       uint8_t *W = S->wb.p;
       BzdBlk *d_blk = (BzdBlk *)(W + b_blk);
@@ -710,23 +698,19 @@ static void bzd_describe(Ctx *c, const BzdResult &R, int entry) {
   c->err = buf;
 }
 
+struct BzdReader : ReaderTraits<BzdJob, BzdResult, BzdState> {
+  static constexpr const char *word = "bunzip2";
+  static BzdState *state(Ctx *c) { return bzd_state(c); }
+  static void begin(BzdState *S) { S->last_entries.clear(); S->last_blocks.clear(); }
+  // streams and outputs of a group: half of the knob; the rounds' work arrays: the rest
+  static uint64_t limit(const Ctx *c) { return ((uint64_t)c->knob_bunzip_batch_mib << 20) / 2; }
+  static int run(Ctx *c, BzdState *S, std::vector<BzdJob> &jobs, const uint32_t *crc_in, std::vector<BzdResult> &res, uint32_t entry0) { return bzd_run(c, S, jobs, crc_in, res, entry0); }
+  static void describe(Ctx *c, const BzdResult &R, int entry) { bzd_describe(c, R, entry); }
+};
+
 // bzd_run for zada_unzip_device (zada_internal.h)
 int bunzip2_run_jobs(Ctx *c, uint32_t E, const ReaderJob *rj, ReaderRes *rr, bool *described) {
-  if (E == 0) return 0;
-  BzdState *S = bzd_state(c);
-  if (!S) { c->err = "bunzip2: no memory for the tables"; return ZADA_E_NOMEM; }
-  std::vector<BzdJob> jobs(E);
-  std::vector<uint32_t> regs(E);
-  std::vector<BzdResult> res;
-  for (uint32_t k = 0; k < E; k++) { jobs[k] = BzdJob{rj[k].in, rj[k].out, rj[k].n_in, rj[k].cap}; regs[k] = rr[k].crc; }
-  S->last_entries.clear(); S->last_blocks.clear();
-  const int rc = bzd_run(c, S, jobs, regs.data(), res);
-  if (rc) return rc;
-  for (uint32_t k = 0; k < E; k++) {
-    if (res[k].rc) { rr[k] = ReaderRes{ZADA_E_DATA, regs[k], 0, 0}; if (!*described) { bzd_describe(c, res[k], rj[k].index); *described = true; } }
-    else rr[k] = ReaderRes{ZADA_OK, res[k].crc, res[k].out_len, res[k].in_used};
-  }
-  return 0;
+  return reader_run_jobs<BzdReader>(c, E, rj, rr, described, [](const ReaderJob &J) { return BzdJob{J.in, J.out, J.n_in, J.cap}; });
 }
 
 }  // namespace zada
@@ -741,25 +725,10 @@ int zada_bunzip2_device(zada_ctx *z, const void *d_in, uint64_t n_in, void *d_ou
   c->lz_stopped = false;
   if ((n_in && !d_in) || (cap && !d_out)) { c->err = "zada_bunzip2_device: null buffer"; return ZADA_E_INVALID; }
   if (n_in >= BZD_MAX_BYTES || cap >= BZD_MAX_BYTES) { c->err = "zada_bunzip2_device: a stream or an output of 1 TiB or more"; return ZADA_E_TOO_LARGE; }
-  if (out_len) *out_len = 0;
-  if (in_used) *in_used = 0;
-  if (hipSetDevice(c->device) != hipSuccess) return ZADA_E_HIP;
-  BzdState *S = bzd_state(c);
-  if (!S) { c->err = "bunzip2: no memory for the tables"; return ZADA_E_NOMEM; }
-  std::vector<BzdJob> jobs(1);
-  jobs[0] = BzdJob{(uint64_t)(uintptr_t)d_in, (uint64_t)(uintptr_t)d_out, n_in, cap};
-  std::vector<BzdResult> res;
-  const uint32_t reg = crc_inout ? *crc_inout : 0u;
-  S->last_entries.clear(); S->last_blocks.clear();
-  c->tbegin();
-  int rc = bzd_run(c, S, jobs, &reg, res);
-  c->tend();
-  if (rc) { hipStreamSynchronize(c->stream); (void)hipGetLastError(); return rc; }
-  if (res[0].rc) { bzd_describe(c, res[0], 0); return ZADA_E_DATA; }
-  if (out_len) *out_len = res[0].out_len;
-  if (in_used) *in_used = res[0].in_used;
-  if (crc_inout) *crc_inout = res[0].crc;
-  return ZADA_OK;
+  return reader_device_one<BzdReader>(c, out_len, in_used, crc_inout, [&](BzdJob &J) {
+    J = BzdJob{(uint64_t)(uintptr_t)d_in, (uint64_t)(uintptr_t)d_out, n_in, cap};
+    return 0;
+  });
 }
 
 int zada_bunzip2_batch(zada_ctx *z, int count, const uint8_t *const *in, const uint64_t *n_in, uint8_t *const *out, const uint64_t *cap, uint64_t *out_len,
@@ -773,87 +742,21 @@ int zada_bunzip2_batch(zada_ctx *z, int count, const uint8_t *const *in, const u
     if (n_in[i] >= BZD_MAX_BYTES || cap[i] >= BZD_MAX_BYTES) { c->err = "zada_bunzip2_batch: a stream or an output of 1 TiB or more"; return ZADA_E_TOO_LARGE; }
   }
   if (count == 0) return ZADA_OK;
-  if (hipSetDevice(c->device) != hipSuccess) return ZADA_E_HIP;
-  BzdState *S = bzd_state(c);
-  if (!S) { c->err = "bunzip2: no memory for the tables"; return ZADA_E_NOMEM; }
-  int worst = 0, worst_entry = -1;
-  BzdResult worst_rec{};
-  const uint64_t limit = ((uint64_t)c->knob_bunzip_batch_mib << 20) / 2;        // streams and outputs of a group: half of the knob; the rounds' work arrays: the rest
-  std::vector<uint8_t> host;
-  std::vector<BzdJob> jobs;
-  std::vector<BzdResult> res;
-  std::vector<uint32_t> regs;
-  std::vector<uint64_t> ooff;
-  S->last_entries.clear(); S->last_blocks.clear();
-  c->tbegin();
-  for (int g0 = 0; g0 < count;) {
-    uint64_t in_bytes = 0, out_bytes = 0;
-    int g1 = g0;
-    while (g1 < count) {
-      const uint64_t a = (n_in[g1] + 15) & ~15ull, b = (cap[g1] + 15) & ~15ull;
-      if (g1 > g0 && in_bytes + out_bytes + a + b > limit) break;
-      in_bytes += a; out_bytes += b; g1++;
-    }
-    const uint32_t E = (uint32_t)(g1 - g0);
-    int rc = bzd_grow(c, S->arena, in_bytes + out_bytes + 16, "hipMalloc (bunzip2 arena)");
-    if (rc) { c->tend(); return rc; }
-    host.resize(in_bytes ? in_bytes : 1);
-    jobs.resize(E); regs.resize(E); ooff.resize(E);
-    uint64_t io = 0, oo = in_bytes;
-    for (uint32_t k = 0; k < E; k++) {
-      const int i = g0 + (int)k;
-      if (n_in[i]) memcpy(host.data() + io, in[i], n_in[i]);
-      jobs[k] = BzdJob{(uint64_t)(uintptr_t)(S->arena.p + io), (uint64_t)(uintptr_t)(S->arena.p + oo), n_in[i], cap[i]};
-      regs[k] = crc ? crc[i] : 0u;
-      ooff[k] = oo;
-      io += (n_in[i] + 15) & ~15ull; oo += (cap[i] + 15) & ~15ull;
-    }
-    if (in_bytes) hipMemcpyAsync(S->arena.p, host.data(), in_bytes, hipMemcpyHostToDevice, c->stream);
-    rc = bzd_run(c, S, jobs, regs.data(), res, (uint32_t)g0);
-    if (rc) { hipStreamSynchronize(c->stream); (void)hipGetLastError(); c->tend(); return rc; }
-    uint64_t hi = 0;
-    if (out) for (uint32_t k = 0; k < E; k++) if (res[k].rc == 0 && res[k].out_len) hi = ooff[k] + res[k].out_len - in_bytes;
-    host.resize(hi ? hi : 1);
-    if (hi && (hip_check(c, hipMemcpyAsync(host.data(), S->arena.p + in_bytes, hi, hipMemcpyDeviceToHost, c->stream), "bunzip2 copy out") ||
-               hip_check(c, hipStreamSynchronize(c->stream), "bunzip2 copy out"))) { c->tend(); return ZADA_E_HIP; }
-    for (uint32_t k = 0; k < E; k++) {
-      const int i = g0 + (int)k;
-      rc_out[i] = res[k].rc ? ZADA_E_DATA : ZADA_OK;
-      if (out_len) out_len[i] = res[k].out_len;
-      if (in_used) in_used[i] = res[k].in_used;
-      if (res[k].rc) { if (worst == 0) { worst = ZADA_E_DATA; worst_entry = i; worst_rec = res[k]; } continue; }
-      if (crc) crc[i] = res[k].crc;
-      if (out && res[k].out_len) memcpy(out[i], host.data() + (ooff[k] - in_bytes), res[k].out_len);
-    }
-    g0 = g1;
-  }
-  c->tend();
-  if (worst) bzd_describe(c, worst_rec, worst_entry);
-  return worst;
+  return reader_batch<BzdReader>(c, count, in, n_in, out, cap, out_len, in_used, crc, rc_out,
+                                 [&](int i, uint64_t d_in, uint64_t d_out) { return BzdJob{d_in, d_out, n_in[i], cap[i]}; });
 }
 
 int zada_bunzip2(zada_ctx *z, const uint8_t *in, uint64_t n_in, uint8_t *out, uint64_t cap, uint64_t *out_len, uint64_t *in_used, uint32_t *crc_inout) {
   if (!z) return ZADA_E_INVALID;
   z->c.lz_stopped = false;
   if ((n_in && !in) || (cap && !out)) { z->c.err = "zada_bunzip2: null buffer"; return ZADA_E_INVALID; }
-  if (out_len) *out_len = 0;
-  if (in_used) *in_used = 0;
-  uint64_t ol = 0, iu = 0;
-  uint32_t reg = crc_inout ? *crc_inout : 0u;
-  int erc = 0;
-  int rc = zada_bunzip2_batch(z, 1, &in, &n_in, &out, &cap, &ol, &iu, &reg, &erc);
-  if (rc) return rc;
-  if (out_len) *out_len = ol;
-  if (in_used) *in_used = iu;
-  if (crc_inout) *crc_inout = reg;
-  return ZADA_OK;
+  return reader_single(out_len, in_used, crc_inout, [&](uint64_t *ol, uint64_t *iu, uint32_t *reg, int *erc) {
+    return zada_bunzip2_batch(z, 1, &in, &n_in, &out, &cap, ol, iu, reg, erc);
+  });
 }
 
 uint64_t zada_bunzip2_last_records(zada_ctx *z, int what, uint64_t *dst, uint64_t cap_items) {
   if (!z || !z->c.bzd || (cap_items && !dst)) return 0;
   const BzdState *S = (const BzdState *)z->c.bzd;
-  const std::vector<uint64_t> &v = what == 0 ? S->last_entries : S->last_blocks;
-  const uint64_t n = v.size() < cap_items ? v.size() : cap_items;
-  if (n) memcpy(dst, v.data(), n * 8);
-  return v.size();
+  return reader_last_records(what == 0 ? S->last_entries : S->last_blocks, dst, cap_items);
 }

@@ -140,8 +140,7 @@ __global__ void __launch_bounds__(FZ_WAVE * FZ_WAVES) k_fz_search(const FzEntry 
 }
 
 // ---- host side ----
-struct FzBuf { uint8_t *p = nullptr; uint64_t cap = 0; };
-struct FzState { FzBuf tabs, arena; };
+struct FzState { DevBuf tabs, arena; };
 
 static FzState *fz_state(Ctx *c) {
   if (!c->fz) c->fz = new (std::nothrow) FzState();
@@ -150,19 +149,9 @@ static FzState *fz_state(Ctx *c) {
 void find_destroy(Ctx *c) {
   FzState *S = (FzState *)c->fz;
   if (!S) return;
-  for (FzBuf *b : {&S->tabs, &S->arena}) if (b->p) hipFree(b->p);
+  for (DevBuf *b : {&S->tabs, &S->arena}) dev_free(*b);
   delete S;
   c->fz = nullptr;
-}
-static int fz_grow(Ctx *c, FzBuf &b, uint64_t bytes, const char *what) {
-  if (b.p && b.cap >= bytes) return 0;
-  hipStreamSynchronize(c->stream);
-  if (b.p) hipFree(b.p);
-  b.p = nullptr; b.cap = 0;
-  const uint64_t want = ((bytes < (1u << 20) ? (1u << 20) : bytes) + 65535) & ~65535ull;
-  if (hipMalloc((void **)&b.p, want) != hipSuccess) { (void)hipGetLastError(); c->err = what; return ZADA_E_NOMEM; }
-  b.cap = want;
-  return 0;
 }
 
 #define FZ_HIP(call, what) do { if (hip_check(c, (call), what)) return ZADA_E_HIP_; } while (0)
@@ -180,7 +169,7 @@ static int fz_run(Ctx *c, FzState *S, const std::vector<FzEntry> &ents, const st
   if (!NP) return 0;
   const uint64_t o_needle = 0, o_ents = FZ_MAX, o_occ = (o_ents + (uint64_t)ne * sizeof(FzEntry) + 255) & ~255ull, o_first = (o_occ + (uint64_t)ne * 8 + 255) & ~255ull,
                  o_pieces = (o_first + (uint64_t)ne * 8 + 255) & ~255ull;
-  const int rc = fz_grow(c, S->tabs, o_pieces + pieces.size() * sizeof(UzPiece) + 256, "hipMalloc (find tables)");
+  const int rc = dev_grow(c, S->tabs, o_pieces + pieces.size() * sizeof(UzPiece) + 256, "hipMalloc (find tables)");
   if (rc) return rc;
   uint8_t *T = S->tabs.p;
   hipMemcpyAsync(T + o_needle, N.buf, FZ_MAX, hipMemcpyHostToDevice, st);
@@ -286,7 +275,7 @@ int zada_findzip_device(zada_ctx *z, const void *d_archive, uint64_t archive_len
     const int n = g1 - g0;
     uint64_t bytes = 0;
     for (int i = g0; i < g1; i++) { rows[i].out_off = bytes; bytes += uz_slot(rows[i].cap); }
-    rc = fz_grow(c, S->arena, bytes + 16, "hipMalloc (findzip arena)");
+    rc = dev_grow(c, S->arena, bytes + 16, "hipMalloc (findzip arena)");
     if (rc) return rc;
     ur.assign(n, zada_unzip_result{0, 0xFFFFFFFFu, 0, 0});
     // through the reader's launches; a return value that no entry carries is what stopped the call

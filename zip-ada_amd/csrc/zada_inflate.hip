@@ -24,6 +24,7 @@
 #include <vector>
 #include "../../include/zada.h"
 #include "zada_internal.h"
+#include "zada_reader_host.h"
 #include "zada_inflate_logic.h"
 #include "zada_inflate_wave.h"
 
@@ -235,11 +236,8 @@ __global__ void __launch_bounds__(INF_WAVE) k_crypt_decode(const uint64_t *__res
 }
 
 // ---- host side ----
-struct InfState {
+struct InfState : ReaderState {
   InfCrcOps *d_ops = nullptr;
-  uint32_t *d_counter = nullptr;
-  uint8_t *tabs = nullptr; uint64_t cap_tabs = 0;      // jobs, order, crc_in, results of a launch
-  uint8_t *arena = nullptr; uint64_t cap_arena = 0;    // a group's inputs and outputs (the host-buffer entry points)
   int waves = 0;                                       // waves a launch keeps in flight
 };
 
@@ -273,21 +271,10 @@ static InfState *inf_state(Ctx *c) {
 void inflate_destroy(Ctx *c) {
   InfState *S = (InfState *)c->inf;
   if (!S) return;
-  if (S->tabs) hipFree(S->tabs);
-  if (S->arena) hipFree(S->arena);
+  dev_free(S->tabs); dev_free(S->arena);
   hipFree(S->d_ops); hipFree(S->d_counter);
   delete S;
   c->inf = nullptr;
-}
-static int inf_grow(Ctx *c, uint8_t **p, uint64_t *cap, uint64_t bytes, const char *what) {
-  if (*p && *cap >= bytes) return 0;
-  hipStreamSynchronize(c->stream);
-  if (*p) hipFree(*p);
-  *p = nullptr; *cap = 0;
-  const uint64_t want = ((bytes < (1u << 20) ? (1u << 20) : bytes) + 65535) & ~65535ull;
-  if (hipMalloc((void **)p, want) != hipSuccess) { (void)hipGetLastError(); c->err = what; return ZADA_E_NOMEM; }
-  *cap = want;
-  return 0;
 }
 
 // E jobs (device addresses) through one launch of k_inflate and one of k_inf_crc; res [E] receives the records
@@ -298,26 +285,17 @@ static int inf_run(Ctx *c, InfState *S, const std::vector<InfJob> &jobs, const u
   std::vector<uint32_t> order(E);
   for (uint32_t i = 0; i < E; i++) order[i] = i;
   std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return jobs[a].n_in > jobs[b].n_in; });      // longest first
-  const uint64_t o_jobs = 0, o_order = o_jobs + (uint64_t)E * sizeof(InfJob), o_crc = o_order + (uint64_t)E * 4, o_res = (o_crc + (uint64_t)E * 4 + 15) & ~15ull,
-                 total = o_res + (uint64_t)E * sizeof(InfResult);
-  int rc = inf_grow(c, &S->tabs, &S->cap_tabs, total, "hipMalloc (inflate tables)");
+  ReaderTables<InfJob, InfResult> T;
+  const int rc = reader_tables_send(c, S, "inflate", jobs, order, crc_in, 1, T);
   if (rc) return rc;
   hipStream_t st = c->stream;
-  hipMemcpyAsync(S->tabs + o_jobs, jobs.data(), (size_t)E * sizeof(InfJob), hipMemcpyHostToDevice, st);
-  hipMemcpyAsync(S->tabs + o_order, order.data(), (size_t)E * 4, hipMemcpyHostToDevice, st);
-  hipMemcpyAsync(S->tabs + o_crc, crc_in, (size_t)E * 4, hipMemcpyHostToDevice, st);
-  hipMemsetAsync(S->d_counter, 0, 4, st);
   const uint32_t grid = E < (uint32_t)S->waves ? E : (uint32_t)S->waves;
   c->tmark("inflate:begin");
-  hipLaunchKernelGGL(k_inflate, dim3(grid), dim3(INF_WAVE), 0, st, (const InfJob *)(S->tabs + o_jobs), (const uint32_t *)(S->tabs + o_order), E, S->d_counter,
-                     (InfResult *)(S->tabs + o_res));
+  hipLaunchKernelGGL(k_inflate, dim3(grid), dim3(INF_WAVE), 0, st, T.jobs, T.order, E, S->d_counter, T.res);
   c->tmark("inflate:k_inflate");
-  hipLaunchKernelGGL(k_inf_crc, dim3(E), dim3(INF_WAVE), 0, st, (const InfJob *)(S->tabs + o_jobs), (InfResult *)(S->tabs + o_res), (const uint32_t *)(S->tabs + o_crc),
-                     (const InfCrcOps *)S->d_ops, E);
+  hipLaunchKernelGGL(k_inf_crc, dim3(E), dim3(INF_WAVE), 0, st, T.jobs, T.res, T.crc, (const InfCrcOps *)S->d_ops, E);
   c->tmark("inflate:k_inf_crc");
-  hipMemcpyAsync(res.data(), S->tabs + o_res, (size_t)E * sizeof(InfResult), hipMemcpyDeviceToHost, st);
-  if (hip_check(c, hipGetLastError(), "inflate launch") || hip_check(c, hipStreamSynchronize(st), "inflate")) return ZADA_E_HIP_;
-  return 0;
+  return reader_tables_fetch(c, "inflate", T, res);
 }
 
 // The Zip CRC-32 of E outputs in device memory through k_inf_crc, for the BZip2 reader (zada_bunzip2.hip): regs [i] is the register before
@@ -333,15 +311,15 @@ int inflate_crc_entries(Ctx *c, uint32_t E, const uint64_t *out, const uint64_t 
     res[i] = InfResult{0, 0, out_len[i], 0, 0, 0, 0};
   }
   const uint64_t o_jobs = 0, o_crc = o_jobs + (uint64_t)E * sizeof(InfJob), o_res = (o_crc + (uint64_t)E * 4 + 15) & ~15ull, total = o_res + (uint64_t)E * sizeof(InfResult);
-  int rc = inf_grow(c, &S->tabs, &S->cap_tabs, total, "hipMalloc (inflate tables)");
+  int rc = dev_grow(c, S->tabs, total, "hipMalloc (inflate tables)");
   if (rc) return rc;
   hipStream_t st = c->stream;
-  hipMemcpyAsync(S->tabs + o_jobs, jobs.data(), (size_t)E * sizeof(InfJob), hipMemcpyHostToDevice, st);
-  hipMemcpyAsync(S->tabs + o_crc, regs, (size_t)E * 4, hipMemcpyHostToDevice, st);
-  hipMemcpyAsync(S->tabs + o_res, res.data(), (size_t)E * sizeof(InfResult), hipMemcpyHostToDevice, st);
-  hipLaunchKernelGGL(k_inf_crc, dim3(E), dim3(INF_WAVE), 0, st, (const InfJob *)(S->tabs + o_jobs), (InfResult *)(S->tabs + o_res), (const uint32_t *)(S->tabs + o_crc),
+  hipMemcpyAsync(S->tabs.p + o_jobs, jobs.data(), (size_t)E * sizeof(InfJob), hipMemcpyHostToDevice, st);
+  hipMemcpyAsync(S->tabs.p + o_crc, regs, (size_t)E * 4, hipMemcpyHostToDevice, st);
+  hipMemcpyAsync(S->tabs.p + o_res, res.data(), (size_t)E * sizeof(InfResult), hipMemcpyHostToDevice, st);
+  hipLaunchKernelGGL(k_inf_crc, dim3(E), dim3(INF_WAVE), 0, st, (const InfJob *)(S->tabs.p + o_jobs), (InfResult *)(S->tabs.p + o_res), (const uint32_t *)(S->tabs.p + o_crc),
                      (const InfCrcOps *)S->d_ops, E);
-  hipMemcpyAsync(res.data(), S->tabs + o_res, (size_t)E * sizeof(InfResult), hipMemcpyDeviceToHost, st);
+  hipMemcpyAsync(res.data(), S->tabs.p + o_res, (size_t)E * sizeof(InfResult), hipMemcpyDeviceToHost, st);
   if (hip_check(c, hipGetLastError(), "crc launch") || hip_check(c, hipStreamSynchronize(st), "crc")) return ZADA_E_HIP_;
   for (uint32_t i = 0; i < E; i++) regs[i] = res[i].crc;
   return 0;
@@ -353,22 +331,16 @@ static void inf_describe(Ctx *c, const InfResult &R, int entry) {
   c->err = buf;
 }
 
+struct InfReader : ReaderTraits<InfJob, InfResult, InfState> {
+  static constexpr const char *word = "inflate";
+  static InfState *state(Ctx *c) { return inf_state(c); }
+  static int run(Ctx *c, InfState *S, std::vector<InfJob> &jobs, const uint32_t *crc_in, std::vector<InfResult> &res, uint32_t) { return inf_run(c, S, jobs, crc_in, res); }
+  static void describe(Ctx *c, const InfResult &R, int entry) { inf_describe(c, R, entry); }
+};
+
 // inf_run for zada_unzip_device (zada_internal.h)
 int inflate_run_jobs(Ctx *c, uint32_t E, const ReaderJob *rj, ReaderRes *rr, bool *described) {
-  if (E == 0) return 0;
-  InfState *S = inf_state(c);
-  if (!S) { c->err = "inflate: no memory for the tables"; return ZADA_E_NOMEM; }
-  std::vector<InfJob> jobs(E);
-  std::vector<uint32_t> regs(E);
-  std::vector<InfResult> res;
-  for (uint32_t k = 0; k < E; k++) { jobs[k] = InfJob{rj[k].in, rj[k].out, rj[k].n_in, rj[k].cap, rj[k].format, 0}; regs[k] = rr[k].crc; }
-  const int rc = inf_run(c, S, jobs, regs.data(), res);
-  if (rc) return rc;
-  for (uint32_t k = 0; k < E; k++) {
-    if (res[k].rc) { rr[k] = ReaderRes{ZADA_E_DATA, regs[k], 0, 0}; if (!*described) { inf_describe(c, res[k], rj[k].index); *described = true; } }
-    else rr[k] = ReaderRes{ZADA_OK, res[k].crc, res[k].out_len, res[k].in_used};
-  }
-  return 0;
+  return reader_run_jobs<InfReader>(c, E, rj, rr, described, [](const ReaderJob &J) { return InfJob{J.in, J.out, J.n_in, J.cap, J.format, 0}; });
 }
 
 }  // namespace zada
@@ -392,24 +364,10 @@ int zada_inflate_device(zada_ctx *z, int format, const void *d_in, uint64_t n_in
   Ctx *c = &z->c;
   if ((n_in && !d_in) || (cap && !d_out)) { c->err = "zada_inflate_device: null buffer"; return ZADA_E_INVALID; }
   if (n_in >= INF_MAX_BYTES || cap >= INF_MAX_BYTES) { c->err = "zada_inflate_device: a stream or an output of 1 TiB or more"; return ZADA_E_TOO_LARGE; }
-  if (out_len) *out_len = 0;
-  if (in_used) *in_used = 0;
-  if (hipSetDevice(c->device) != hipSuccess) return ZADA_E_HIP;
-  InfState *S = inf_state(c);
-  if (!S) { c->err = "inflate: no memory for the tables"; return ZADA_E_NOMEM; }
-  std::vector<InfJob> jobs(1);
-  jobs[0] = InfJob{(uint64_t)(uintptr_t)d_in, (uint64_t)(uintptr_t)d_out, n_in, cap, format, 0};
-  std::vector<InfResult> res;
-  const uint32_t reg = crc_inout ? *crc_inout : 0u;
-  c->tbegin();
-  rc = inf_run(c, S, jobs, &reg, res);
-  c->tend();
-  if (rc) { hipStreamSynchronize(c->stream); (void)hipGetLastError(); return rc; }
-  if (res[0].rc) { inf_describe(c, res[0], 0); return ZADA_E_DATA; }
-  if (out_len) *out_len = res[0].out_len;
-  if (in_used) *in_used = res[0].in_used;
-  if (crc_inout) *crc_inout = res[0].crc;
-  return ZADA_OK;
+  return reader_device_one<InfReader>(c, out_len, in_used, crc_inout, [&](InfJob &J) {
+    J = InfJob{(uint64_t)(uintptr_t)d_in, (uint64_t)(uintptr_t)d_out, n_in, cap, format, 0};
+    return 0;
+  });
 }
 
 int zada_inflate_batch(zada_ctx *z, int count, const int *format, const uint8_t *const *in, const uint64_t *n_in, uint8_t *const *out, const uint64_t *cap,
@@ -424,81 +382,17 @@ int zada_inflate_batch(zada_ctx *z, int count, const int *format, const uint8_t 
     if (n_in[i] >= INF_MAX_BYTES || cap[i] >= INF_MAX_BYTES) { c->err = "zada_inflate_batch: a stream or an output of 1 TiB or more"; return ZADA_E_TOO_LARGE; }
   }
   if (count == 0) return ZADA_OK;
-  if (hipSetDevice(c->device) != hipSuccess) return ZADA_E_HIP;
-  InfState *S = inf_state(c);
-  if (!S) { c->err = "inflate: no memory for the tables"; return ZADA_E_NOMEM; }
-  int worst = 0, worst_entry = -1;
-  InfResult worst_rec{};
-  const uint64_t limit = (uint64_t)c->knob_batch_mib << 20;
-  std::vector<uint8_t> host;
-  std::vector<InfJob> jobs;
-  std::vector<InfResult> res;
-  std::vector<uint32_t> regs;
-  std::vector<uint64_t> ooff;
-  c->tbegin();
-  for (int g0 = 0; g0 < count;) {
-    // a group: entries g0 .. g1 - 1, inputs then outputs in one arena, every buffer at a multiple of 16
-    uint64_t in_bytes = 0, out_bytes = 0;
-    int g1 = g0;
-    while (g1 < count) {
-      const uint64_t a = (n_in[g1] + 15) & ~15ull, b = (cap[g1] + 15) & ~15ull;
-      if (g1 > g0 && in_bytes + out_bytes + a + b > limit) break;
-      in_bytes += a; out_bytes += b; g1++;
-    }
-    const uint32_t E = (uint32_t)(g1 - g0);
-    int rc = inf_grow(c, &S->arena, &S->cap_arena, in_bytes + out_bytes + 16, "hipMalloc (inflate arena)");
-    if (rc) { c->tend(); return rc; }
-    host.resize(in_bytes ? in_bytes : 1);
-    jobs.resize(E); regs.resize(E); ooff.resize(E);
-    uint64_t io = 0, oo = in_bytes;
-    for (uint32_t k = 0; k < E; k++) {
-      const int i = g0 + (int)k;
-      if (n_in[i]) memcpy(host.data() + io, in[i], n_in[i]);
-      jobs[k] = InfJob{(uint64_t)(uintptr_t)(S->arena + io), (uint64_t)(uintptr_t)(S->arena + oo), n_in[i], cap[i], format[i], 0};
-      regs[k] = crc ? crc[i] : 0u;
-      ooff[k] = oo;
-      io += (n_in[i] + 15) & ~15ull; oo += (cap[i] + 15) & ~15ull;
-    }
-    if (in_bytes) hipMemcpyAsync(S->arena, host.data(), in_bytes, hipMemcpyHostToDevice, c->stream);
-    rc = inf_run(c, S, jobs, regs.data(), res);
-    if (rc) { hipStreamSynchronize(c->stream); (void)hipGetLastError(); c->tend(); return rc; }
-    // the outputs come back in one piece up to the last byte any entry wrote
-    uint64_t hi = 0;
-    if (out) for (uint32_t k = 0; k < E; k++) if (res[k].rc == 0 && res[k].out_len) hi = ooff[k] + res[k].out_len - in_bytes;
-    host.resize(hi ? hi : 1);
-    if (hi && (hip_check(c, hipMemcpyAsync(host.data(), S->arena + in_bytes, hi, hipMemcpyDeviceToHost, c->stream), "inflate copy out") ||
-               hip_check(c, hipStreamSynchronize(c->stream), "inflate copy out"))) { c->tend(); return ZADA_E_HIP; }
-    for (uint32_t k = 0; k < E; k++) {
-      const int i = g0 + (int)k;
-      rc_out[i] = res[k].rc ? ZADA_E_DATA : ZADA_OK;
-      if (out_len) out_len[i] = res[k].out_len;
-      if (in_used) in_used[i] = res[k].in_used;
-      if (res[k].rc) { if (worst == 0) { worst = ZADA_E_DATA; worst_entry = i; worst_rec = res[k]; } continue; }
-      if (crc) crc[i] = res[k].crc;
-      if (out && res[k].out_len) memcpy(out[i], host.data() + (ooff[k] - in_bytes), res[k].out_len);
-    }
-    g0 = g1;
-  }
-  c->tend();
-  if (worst) inf_describe(c, worst_rec, worst_entry);
-  return worst;
+  return reader_batch<InfReader>(c, count, in, n_in, out, cap, out_len, in_used, crc, rc_out,
+                                 [&](int i, uint64_t d_in, uint64_t d_out) { return InfJob{d_in, d_out, n_in[i], cap[i], format[i], 0}; });
 }
 
 int zada_inflate(zada_ctx *z, int format, const uint8_t *in, uint64_t n_in, uint8_t *out, uint64_t cap, uint64_t *out_len, uint64_t *in_used, uint32_t *crc_inout) {
   int rc = inf_prepare(z, format, "zada_inflate");
   if (rc) return rc;
   if ((n_in && !in) || (cap && !out)) { z->c.err = "zada_inflate: null buffer"; return ZADA_E_INVALID; }
-  if (out_len) *out_len = 0;
-  if (in_used) *in_used = 0;
-  uint64_t ol = 0, iu = 0;
-  uint32_t reg = crc_inout ? *crc_inout : 0u;
-  int erc = 0;
-  rc = zada_inflate_batch(z, 1, &format, &in, &n_in, &out, &cap, &ol, &iu, &reg, &erc);
-  if (rc) return rc;
-  if (out_len) *out_len = ol;
-  if (in_used) *in_used = iu;
-  if (crc_inout) *crc_inout = reg;
-  return ZADA_OK;
+  return reader_single(out_len, in_used, crc_inout, [&](uint64_t *ol, uint64_t *iu, uint32_t *reg, int *erc) {
+    return zada_inflate_batch(z, 1, &format, &in, &n_in, &out, &cap, ol, iu, reg, erc);
+  });
 }
 
 int zada_crypt_decode_batch(zada_ctx *z, int count, uint32_t (*keys)[3], uint8_t *const *buf, const uint64_t *n) {
@@ -520,8 +414,8 @@ int zada_crypt_decode_batch(zada_ctx *z, int count, uint32_t (*keys)[3], uint8_t
     while (g1 < count && (g1 == g0 || bytes + n[g1] <= limit)) bytes += n[g1++];
     const uint32_t E = (uint32_t)(g1 - g0);
     const uint64_t o_ptr = 0, o_len = (uint64_t)E * 8, o_key = (uint64_t)E * 16, tbytes = o_key + (uint64_t)E * 12;
-    int rc = inf_grow(c, &S->arena, &S->cap_arena, bytes + 16, "hipMalloc (crypt arena)");
-    if (!rc) rc = inf_grow(c, &S->tabs, &S->cap_tabs, tbytes, "hipMalloc (crypt tables)");
+    int rc = dev_grow(c, S->arena, bytes + 16, "hipMalloc (crypt arena)");
+    if (!rc) rc = dev_grow(c, S->tabs, tbytes, "hipMalloc (crypt tables)");
     if (rc) return rc;
     host.resize(bytes ? bytes : 1);
     tab.assign((size_t)(tbytes + 7) / 8, 0);
@@ -529,17 +423,17 @@ int zada_crypt_decode_batch(zada_ctx *z, int count, uint32_t (*keys)[3], uint8_t
     for (uint32_t k = 0; k < E; k++) {
       const int i = g0 + (int)k;
       if (n[i]) memcpy(host.data() + o, buf[i], n[i]);
-      tab[k] = (uint64_t)(uintptr_t)(S->arena + o); tab[E + k] = n[i];
+      tab[k] = (uint64_t)(uintptr_t)(S->arena.p + o); tab[E + k] = n[i];
       memcpy((uint8_t *)tab.data() + o_key + 12 * (uint64_t)k, keys[i], 12);
       o += n[i];
     }
     hipStream_t st = c->stream;
-    if (bytes) hipMemcpyAsync(S->arena, host.data(), bytes, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(S->tabs, tab.data(), tbytes, hipMemcpyHostToDevice, st);
-    hipLaunchKernelGGL(k_crypt_decode, dim3((E + INF_WAVE - 1) / INF_WAVE), dim3(INF_WAVE), 0, st, (const uint64_t *)(S->tabs + o_ptr), (const uint64_t *)(S->tabs + o_len),
-                       (uint32_t *)(S->tabs + o_key), E);
-    if (bytes) hipMemcpyAsync(host.data(), S->arena, bytes, hipMemcpyDeviceToHost, st);
-    hipMemcpyAsync((uint8_t *)tab.data() + o_key, S->tabs + o_key, (size_t)E * 12, hipMemcpyDeviceToHost, st);
+    if (bytes) hipMemcpyAsync(S->arena.p, host.data(), bytes, hipMemcpyHostToDevice, st);
+    hipMemcpyAsync(S->tabs.p, tab.data(), tbytes, hipMemcpyHostToDevice, st);
+    hipLaunchKernelGGL(k_crypt_decode, dim3((E + INF_WAVE - 1) / INF_WAVE), dim3(INF_WAVE), 0, st, (const uint64_t *)(S->tabs.p + o_ptr), (const uint64_t *)(S->tabs.p + o_len),
+                       (uint32_t *)(S->tabs.p + o_key), E);
+    if (bytes) hipMemcpyAsync(host.data(), S->arena.p, bytes, hipMemcpyDeviceToHost, st);
+    hipMemcpyAsync((uint8_t *)tab.data() + o_key, S->tabs.p + o_key, (size_t)E * 12, hipMemcpyDeviceToHost, st);
     if (hip_check(c, hipGetLastError(), "crypt decode") || hip_check(c, hipStreamSynchronize(st), "crypt decode")) { (void)hipGetLastError(); return ZADA_E_HIP; }
     o = 0;
     for (uint32_t k = 0; k < E; k++) {

@@ -308,8 +308,8 @@ template <int FORMAT> static void infp_launch_resolve(Ctx *c, hipStream_t st, co
 }
 
 struct InfpState {
-  uint8_t *tabs = nullptr; uint64_t cap_tabs = 0;      // jobs, records, live chunks, the marker counter
-  void *sym = nullptr; uint64_t cap_sym = 0;           // the symbols: 2 bytes per output byte, Deflate64 4
+  DevBuf tabs;                                         // jobs, records, live chunks, the marker counter
+  DevBuf sym;                                          // the symbols: 2 bytes per output byte, Deflate64 4
   zada_inflate_par_info last{};
 };
 static InfpState *infp_state(Ctx *c) {
@@ -319,20 +319,9 @@ static InfpState *infp_state(Ctx *c) {
 void inflate_par_destroy(Ctx *c) {
   InfpState *S = (InfpState *)c->infp;
   if (!S) return;
-  if (S->tabs) hipFree(S->tabs);
-  if (S->sym) hipFree(S->sym);
+  dev_free(S->tabs); dev_free(S->sym);
   delete S;
   c->infp = nullptr;
-}
-static bool infp_grow(Ctx *c, void **p, uint64_t *cap, uint64_t bytes) {
-  if (*p && *cap >= bytes) return true;
-  hipStreamSynchronize(c->stream);
-  if (*p) hipFree(*p);
-  *p = nullptr; *cap = 0;
-  const uint64_t want = ((bytes < (1u << 20) ? (1u << 20) : bytes) + 65535) & ~65535ull;
-  if (hipMalloc(p, want) != hipSuccess) { (void)hipGetLastError(); return false; }
-  *cap = want;
-  return true;
 }
 
 static uint32_t infp_crc_bytes(uint32_t r, const uint8_t *p, uint32_t n) {
@@ -360,21 +349,21 @@ int inflate_par_try(Ctx *c, int format, const void *d_in, uint64_t n_in, void *d
   // the tables: jobs [nch], records [nch], live chunks [nch], the marker counter
   const uint64_t o_jobs = 0, o_recs = o_jobs + (uint64_t)nch * sizeof(InfpJob), o_live = o_recs + (uint64_t)nch * sizeof(InfpRec),
                  o_mark = o_live + (uint64_t)nch * sizeof(InfpLive), total_tabs = o_mark + 16;
-  if (!infp_grow(c, (void **)&S->tabs, &S->cap_tabs, total_tabs)) return fall(INFP_MEMORY);
+  if (dev_grow(c, S->tabs, total_tabs, nullptr)) return fall(INFP_MEMORY);
   hipStream_t st = c->stream;
   const uint8_t *in = (const uint8_t *)d_in;
   std::vector<InfpJob> jobs(nch);
   std::vector<InfpRec> recs(nch);
   for (uint32_t k = 0; k < nch; k++) jobs[k] = InfpJob{k ? INFP_SEARCH : 0ull, k, 0};
-  hipMemcpyAsync(S->tabs + o_jobs, jobs.data(), (size_t)nch * sizeof(InfpJob), hipMemcpyHostToDevice, st);
+  hipMemcpyAsync(S->tabs.p + o_jobs, jobs.data(), (size_t)nch * sizeof(InfpJob), hipMemcpyHostToDevice, st);
   c->tmark("inflate_par:begin");
   auto scout = [&](uint32_t njobs) {
-    hipLaunchKernelGGL(d64 ? k_infp_scout<true> : k_infp_scout<false>, dim3(njobs), dim3(INF_WAVE), 0, st, in, n_in, chunk_bytes, (const InfpJob *)(S->tabs + o_jobs), njobs,
-                       (InfpRec *)(S->tabs + o_recs));
+    hipLaunchKernelGGL(d64 ? k_infp_scout<true> : k_infp_scout<false>, dim3(njobs), dim3(INF_WAVE), 0, st, in, n_in, chunk_bytes, (const InfpJob *)(S->tabs.p + o_jobs), njobs,
+                       (InfpRec *)(S->tabs.p + o_recs));
   };
   scout(nch);
   c->tmark("inflate_par:k_infp_scout");
-  hipMemcpyAsync(recs.data(), S->tabs + o_recs, (size_t)nch * sizeof(InfpRec), hipMemcpyDeviceToHost, st);
+  hipMemcpyAsync(recs.data(), S->tabs.p + o_recs, (size_t)nch * sizeof(InfpRec), hipMemcpyDeviceToHost, st);
   if (hip_check(c, hipGetLastError(), "inflate_par scout launch") || hip_check(c, hipStreamSynchronize(st), "inflate_par scout")) return ZADA_E_HIP_;
   I.scout_rounds = 1;
   // the chain
@@ -389,9 +378,9 @@ int inflate_par_try(Ctx *c, int format, const void *d_in, uint64_t n_in, void *d
     if (w == INFP_W_DONE) break;
     if (W.repairs > bound) return fall(INFP_REPAIRS);
     const InfpJob J{W.expect, W.cur, 0};
-    hipMemcpyAsync(S->tabs + o_jobs, &J, sizeof J, hipMemcpyHostToDevice, st);
+    hipMemcpyAsync(S->tabs.p + o_jobs, &J, sizeof J, hipMemcpyHostToDevice, st);
     scout(1u);
-    hipMemcpyAsync(&recs[W.cur], S->tabs + o_recs + (uint64_t)W.cur * sizeof(InfpRec), sizeof(InfpRec), hipMemcpyDeviceToHost, st);
+    hipMemcpyAsync(&recs[W.cur], S->tabs.p + o_recs + (uint64_t)W.cur * sizeof(InfpRec), sizeof(InfpRec), hipMemcpyDeviceToHost, st);
     if (hip_check(c, hipGetLastError(), "inflate_par repair launch") || hip_check(c, hipStreamSynchronize(st), "inflate_par repair")) return ZADA_E_HIP_;
     I.scout_rounds++;
   }
@@ -399,19 +388,19 @@ int inflate_par_try(Ctx *c, int format, const void *d_in, uint64_t n_in, void *d
   if (W.total > cap) return fall(INFP_DAMAGED);
   if (W.live < 2) return fall(INFP_SINGLE_CHUNK);
   const uint64_t total = W.total;
-  if (total && !infp_grow(c, &S->sym, &S->cap_sym, total * (d64 ? sizeof(InfpFmt<9>::sym_t) : sizeof(InfpFmt<8>::sym_t)))) return fall(INFP_MEMORY);
+  if (total && dev_grow(c, S->sym, total * (d64 ? sizeof(InfpFmt<9>::sym_t) : sizeof(InfpFmt<8>::sym_t)), nullptr)) return fall(INFP_MEMORY);
   // the live chunks, in order
   std::vector<InfpLive> live;
   live.reserve(W.live);
   for (uint32_t k = 0; k < nch; k++)
     if (is_live[k]) live.push_back(InfpLive{recs[k].start_bit, ((uint64_t)k + 1) * chunk_bytes * 8, off[k], recs[k].bytes, 0, 0, 0});
   const uint32_t nl = (uint32_t)live.size();
-  hipMemcpyAsync(S->tabs + o_live, live.data(), (size_t)nl * sizeof(InfpLive), hipMemcpyHostToDevice, st);
-  hipMemsetAsync(S->tabs + o_mark, 0, 16, st);
-  InfpLive *d_live = (InfpLive *)(S->tabs + o_live);
-  uint64_t *d_mark = (uint64_t *)(S->tabs + o_mark);
+  hipMemcpyAsync(S->tabs.p + o_live, live.data(), (size_t)nl * sizeof(InfpLive), hipMemcpyHostToDevice, st);
+  hipMemsetAsync(S->tabs.p + o_mark, 0, 16, st);
+  InfpLive *d_live = (InfpLive *)(S->tabs.p + o_live);
+  uint64_t *d_mark = (uint64_t *)(S->tabs.p + o_mark);
   std::vector<InfpLive> back(nl);
-  if (d64) infp_launch_decode<9>(st, in, n_in, d_live, nl, S->sym); else infp_launch_decode<8>(st, in, n_in, d_live, nl, S->sym);
+  if (d64) infp_launch_decode<9>(st, in, n_in, d_live, nl, S->sym.p); else infp_launch_decode<8>(st, in, n_in, d_live, nl, S->sym.p);
   c->tmark("inflate_par:k_infp_decode");
   hipMemcpyAsync(back.data(), d_live, (size_t)nl * sizeof(InfpLive), hipMemcpyDeviceToHost, st);
   if (hip_check(c, hipGetLastError(), "inflate_par decode launch") || hip_check(c, hipStreamSynchronize(st), "inflate_par decode")) return ZADA_E_HIP_;
@@ -425,7 +414,7 @@ int inflate_par_try(Ctx *c, int format, const void *d_in, uint64_t n_in, void *d
     }
   }
   if (total) {
-    if (d64) infp_launch_resolve<9>(c, st, d_live, nl, S->sym, (uint8_t *)d_out, d_mark); else infp_launch_resolve<8>(c, st, d_live, nl, S->sym, (uint8_t *)d_out, d_mark);
+    if (d64) infp_launch_resolve<9>(c, st, d_live, nl, S->sym.p, (uint8_t *)d_out, d_mark); else infp_launch_resolve<8>(c, st, d_live, nl, S->sym.p, (uint8_t *)d_out, d_mark);
   }
   uint64_t marks = 0;
   uint8_t head[16];
@@ -482,21 +471,21 @@ static int infpb_sub(Ctx *c, InfpState *S, const InfpbIn *rows, InfpbRes *res, c
   const uint64_t o_str = 0, o_jobs = o_str + up((uint64_t)ns * sizeof(InfpbStream)), o_recs = o_jobs + up((uint64_t)nch * sizeof(InfpbJob)),
                  o_back = o_recs + up((uint64_t)nch * sizeof(InfpRec)), o_live = o_back + up((uint64_t)ns * sizeof(InfpRec)), o_mark = o_live + up((uint64_t)nch * sizeof(InfpbLive)),
                  total_tabs = o_mark + 16;
-  if (!infp_grow(c, (void **)&S->tabs, &S->cap_tabs, total_tabs)) { infpb_drop(B, INFP_MEMORY); return leave(); }
-  const InfpbStream *d_str = (const InfpbStream *)(S->tabs + o_str);
-  InfpbLive *d_live = (InfpbLive *)(S->tabs + o_live);
-  uint64_t *d_mark = (uint64_t *)(S->tabs + o_mark);
+  if (dev_grow(c, S->tabs, total_tabs, nullptr)) { infpb_drop(B, INFP_MEMORY); return leave(); }
+  const InfpbStream *d_str = (const InfpbStream *)(S->tabs.p + o_str);
+  InfpbLive *d_live = (InfpbLive *)(S->tabs.p + o_live);
+  uint64_t *d_mark = (uint64_t *)(S->tabs.p + o_mark);
   streams.resize(ns);
   for (uint32_t s = 0; s < ns; s++) { const InfpbIn &R = rows[B.st[s].row]; streams[s] = InfpbStream{R.in, R.n_in, R.out, 0, B.st[s].first, 0, 0, 0}; }
-  hipMemcpyAsync(S->tabs + o_str, streams.data(), (size_t)ns * sizeof(InfpbStream), hipMemcpyHostToDevice, st);
-  hipMemcpyAsync(S->tabs + o_jobs, jobs.data(), (size_t)nch * sizeof(InfpbJob), hipMemcpyHostToDevice, st);
+  hipMemcpyAsync(S->tabs.p + o_str, streams.data(), (size_t)ns * sizeof(InfpbStream), hipMemcpyHostToDevice, st);
+  hipMemcpyAsync(S->tabs.p + o_jobs, jobs.data(), (size_t)nch * sizeof(InfpbJob), hipMemcpyHostToDevice, st);
   auto scout = [&](uint32_t njobs, InfpRec *d_back) {
-    hipLaunchKernelGGL(d64 ? k_infpb_scout<true> : k_infpb_scout<false>, dim3(njobs), dim3(INF_WAVE), 0, st, d_str, chunk_bytes, (const InfpbJob *)(S->tabs + o_jobs), njobs,
-                       (InfpRec *)(S->tabs + o_recs), d_back);
+    hipLaunchKernelGGL(d64 ? k_infpb_scout<true> : k_infpb_scout<false>, dim3(njobs), dim3(INF_WAVE), 0, st, d_str, chunk_bytes, (const InfpbJob *)(S->tabs.p + o_jobs), njobs,
+                       (InfpRec *)(S->tabs.p + o_recs), d_back);
   };
   scout(nch, nullptr);
   c->tmark("inflate_par_batch:k_infpb_scout");
-  hipMemcpyAsync(B.recs.data(), S->tabs + o_recs, (size_t)nch * sizeof(InfpRec), hipMemcpyDeviceToHost, st);
+  hipMemcpyAsync(B.recs.data(), S->tabs.p + o_recs, (size_t)nch * sizeof(InfpRec), hipMemcpyDeviceToHost, st);
   if (hip_check(c, hipGetLastError(), "inflate_par_batch scout launch") || hip_check(c, hipStreamSynchronize(st), "inflate_par_batch scout")) return ZADA_E_HIP_;
   B.launches = 1;
   // the chain in rounds: the one pending repair of every stream that asked for one in the same launch, exactly those records back
@@ -505,9 +494,9 @@ static int infpb_sub(Ctx *c, InfpState *S, const InfpbIn *rows, InfpbRes *res, c
     infpb_round(B, rows, jobs);
     const uint32_t nj = (uint32_t)jobs.size();
     if (!nj) break;
-    hipMemcpyAsync(S->tabs + o_jobs, jobs.data(), (size_t)nj * sizeof(InfpbJob), hipMemcpyHostToDevice, st);
-    scout(nj, (InfpRec *)(S->tabs + o_back));
-    hipMemcpyAsync(back.data(), S->tabs + o_back, (size_t)nj * sizeof(InfpRec), hipMemcpyDeviceToHost, st);
+    hipMemcpyAsync(S->tabs.p + o_jobs, jobs.data(), (size_t)nj * sizeof(InfpbJob), hipMemcpyHostToDevice, st);
+    scout(nj, (InfpRec *)(S->tabs.p + o_back));
+    hipMemcpyAsync(back.data(), S->tabs.p + o_back, (size_t)nj * sizeof(InfpRec), hipMemcpyDeviceToHost, st);
     if (hip_check(c, hipGetLastError(), "inflate_par_batch repair launch") || hip_check(c, hipStreamSynchronize(st), "inflate_par_batch repair")) return ZADA_E_HIP_;
     B.launches++;
     for (uint32_t j = 0; j < nj; j++) B.recs[jobs[j].chunk] = back[j];
@@ -516,22 +505,22 @@ static int infpb_sub(Ctx *c, InfpState *S, const InfpbIn *rows, InfpbRes *res, c
   const uint64_t nsym = infpb_tables(B, rows, streams, lives);
   const uint32_t nsl = (uint32_t)streams.size(), nl = (uint32_t)lives.size();
   if (!nsl) return leave();
-  if (nsym && !infp_grow(c, &S->sym, &S->cap_sym, nsym * infpb_sym_bytes(format))) { infpb_drop(B, INFP_MEMORY); return leave(); }
+  if (nsym && dev_grow(c, S->sym, nsym * infpb_sym_bytes(format), nullptr)) { infpb_drop(B, INFP_MEMORY); return leave(); }
   // (from here on the stream table holds the chained streams alone, in order: a live row's `stream` is its row of this table, InfpbState::slot)
-  hipMemcpyAsync(S->tabs + o_str, streams.data(), (size_t)nsl * sizeof(InfpbStream), hipMemcpyHostToDevice, st);
+  hipMemcpyAsync(S->tabs.p + o_str, streams.data(), (size_t)nsl * sizeof(InfpbStream), hipMemcpyHostToDevice, st);
   hipMemcpyAsync(d_live, lives.data(), (size_t)nl * sizeof(InfpbLive), hipMemcpyHostToDevice, st);
   hipMemsetAsync(d_mark, 0, 16, st);
   std::vector<InfpbLive> got(nl);
-  if (d64) infpb_launch_decode<9>(st, d_str, d_live, nl, S->sym); else infpb_launch_decode<8>(st, d_str, d_live, nl, S->sym);
+  if (d64) infpb_launch_decode<9>(st, d_str, d_live, nl, S->sym.p); else infpb_launch_decode<8>(st, d_str, d_live, nl, S->sym.p);
   c->tmark("inflate_par_batch:k_infpb_decode");
   hipMemcpyAsync(got.data(), d_live, (size_t)nl * sizeof(InfpbLive), hipMemcpyDeviceToHost, st);
   if (hip_check(c, hipGetLastError(), "inflate_par_batch decode launch") || hip_check(c, hipStreamSynchronize(st), "inflate_par_batch decode")) return ZADA_E_HIP_;
   // a stream with a row that is not what the count saw leaves before a byte of it is written
   const uint32_t left = infpb_compare(B, got, streams);
   if (left == nsl) return leave();
-  if (left) hipMemcpyAsync(S->tabs + o_str, streams.data(), (size_t)nsl * sizeof(InfpbStream), hipMemcpyHostToDevice, st);
+  if (left) hipMemcpyAsync(S->tabs.p + o_str, streams.data(), (size_t)nsl * sizeof(InfpbStream), hipMemcpyHostToDevice, st);
   if (nsym) {
-    if (d64) infpb_launch_resolve<9>(c, st, d_str, nsl, d_live, nl, S->sym, d_mark); else infpb_launch_resolve<8>(c, st, d_str, nsl, d_live, nl, S->sym, d_mark);
+    if (d64) infpb_launch_resolve<9>(c, st, d_str, nsl, d_live, nl, S->sym.p, d_mark); else infpb_launch_resolve<8>(c, st, d_str, nsl, d_live, nl, S->sym.p, d_mark);
   }
   uint64_t marks = 0;
   hipMemcpyAsync(&marks, d_mark, 8, hipMemcpyDeviceToHost, st);

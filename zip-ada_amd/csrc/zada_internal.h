@@ -359,6 +359,12 @@ struct Ctx {
 
 extern thread_local std::string *tls_err;          // error text of a worker thread (see hip_check)
 int hip_check(Ctx *c, hipError_t e, const char *what);
+// A device buffer that only grows: the tables and arenas of the readers and of the archive calls (zada_api.hip).  dev_grow leaves at least `bytes`
+// in it: a buffer that is too small is freed behind a synchronisation of the context's stream and allocated anew, 1 MiB at least and a multiple of
+// 64 KiB.  0, or ZADA_E_NOMEM with `what` as the error text (null: the text stays as it is).
+struct DevBuf { uint8_t *p = nullptr; uint64_t cap = 0; };
+int dev_grow(Ctx *c, DevBuf &b, uint64_t bytes, const char *what);
+void dev_free(DevBuf &b);
 // the text of deflate_spans and deflate_device_one when the stream is longer than the capacity they got (zada_zip_device tells this refusal from
 // every other ZADA_E_INVALID by it)
 constexpr const char *ERR_OUTPUT_TOO_SMALL = "output buffer too small";

@@ -125,8 +125,7 @@ __global__ void __launch_bounds__(CZ_WAVE * CZ_WAVES) k_cz_compare(const CzPair 
 }
 
 // ---- host side ----
-struct RzBuf { uint8_t *p = nullptr; uint64_t cap = 0; };
-struct RzState { RzBuf tabs, arena_a, arena_b, hold; };      // hold: the streams of a ReZip group, method after method, until the group is placed
+struct RzState { DevBuf tabs, arena_a, arena_b, hold; };      // hold: the streams of a ReZip group, method after method, until the group is placed
 
 static RzState *rz_state(Ctx *c) {
   if (!c->rz) c->rz = new (std::nothrow) RzState();
@@ -135,19 +134,9 @@ static RzState *rz_state(Ctx *c) {
 void rezip_destroy(Ctx *c) {
   RzState *S = (RzState *)c->rz;
   if (!S) return;
-  for (RzBuf *b : {&S->tabs, &S->arena_a, &S->arena_b, &S->hold}) if (b->p) hipFree(b->p);
+  for (DevBuf *b : {&S->tabs, &S->arena_a, &S->arena_b, &S->hold}) dev_free(*b);
   delete S;
   c->rz = nullptr;
-}
-static int rz_grow(Ctx *c, RzBuf &b, uint64_t bytes, const char *what) {
-  if (b.p && b.cap >= bytes) return 0;
-  hipStreamSynchronize(c->stream);
-  if (b.p) hipFree(b.p);
-  b.p = nullptr; b.cap = 0;
-  const uint64_t want = ((bytes < (1u << 20) ? (1u << 20) : bytes) + 65535) & ~65535ull;
-  if (hipMalloc((void **)&b.p, want) != hipSuccess) { (void)hipGetLastError(); c->err = what; return ZADA_E_NOMEM; }
-  b.cap = want;
-  return 0;
 }
 
 #define RZ_HIP(call, what) do { if (hip_check(c, (call), what)) return ZADA_E_HIP_; } while (0)
@@ -162,7 +151,7 @@ static int cz_run(Ctx *c, RzState *S, const std::vector<CzPair> &pairs, const st
   for (uint32_t k = 0; k < np; k++) first[k] = pairs[k].n;
   if (!NP) return 0;
   const uint64_t o_pairs = 0, o_first = (o_pairs + (uint64_t)np * sizeof(CzPair) + 255) & ~255ull, o_pieces = (o_first + (uint64_t)np * 8 + 255) & ~255ull;
-  const int rc = rz_grow(c, S->tabs, o_pieces + pieces.size() * sizeof(UzPiece) + 256, "hipMalloc (compare tables)");
+  const int rc = dev_grow(c, S->tabs, o_pieces + pieces.size() * sizeof(UzPiece) + 256, "hipMalloc (compare tables)");
   if (rc) return rc;
   uint8_t *T = S->tabs.p;
   hipMemcpyAsync(T + o_pairs, pairs.data(), (size_t)np * sizeof(CzPair), hipMemcpyHostToDevice, st);
@@ -261,8 +250,8 @@ int zada_compzip_device(zada_ctx *z, const void *d_archive_a, uint64_t len_a, co
     g0 = g1;
     const int n = (int)idx.size();
     if (!n) continue;
-    rc = rz_grow(c, S->arena_a, bytes + 16, "hipMalloc (compzip arena 1)");
-    if (!rc) rc = rz_grow(c, S->arena_b, bytes + 16, "hipMalloc (compzip arena 2)");
+    rc = dev_grow(c, S->arena_a, bytes + 16, "hipMalloc (compzip arena 1)");
+    if (!rc) rc = dev_grow(c, S->arena_b, bytes + 16, "hipMalloc (compzip arena 2)");
     if (rc) return rc;
     ra.assign(n, zada_unzip_result{0, 0xFFFFFFFFu, 0, 0}); rb = ra;
     // both sides through the reader's launches; a return value that no entry carries is what stopped the call
@@ -342,7 +331,7 @@ int rz_group(RzRun &R, const std::vector<int> &idx) {
     ue[k] = zada_unzip_entry{e.in_off, e.n_in, bytes, e.method == 0 ? e.n_in : e.usize, e.method, (uint8_t)(e.flags & (e.method == 6 ? 6u : 2u)), 0, 0};   // (Implode: bits 1 and 2 say how it is read)
     bytes += uz_slot(ue[k].cap);
   }
-  int rc = rz_grow(c, R.S->arena_a, bytes + 16, "hipMalloc (rezip extraction arena)");
+  int rc = dev_grow(c, R.S->arena_a, bytes + 16, "hipMalloc (rezip extraction arena)");
   if (rc) return rc;
   uint8_t *arena = R.S->arena_a.p;
   rc = zada_unzip_device(R.z, R.src, R.src_len, arena, bytes, n, ue.data(), nullptr, ur.data());
@@ -384,7 +373,7 @@ int rz_group(RzRun &R, const std::vector<int> &idx) {
       }
     hold_at[m + 1] = hold_at[m] + ((zada_zip_bound_ex((int)tabs[m].size(), tabs[m].data(), 0, 0) + 255) & ~255ull);
   }
-  if ((rc = rz_grow(c, R.S->hold, hold_at.back() + 16, "hipMalloc (rezip holding buffer)"))) return rc;
+  if ((rc = dev_grow(c, R.S->hold, hold_at.back() + 16, "hipMalloc (rezip holding buffer)"))) return rc;
   // 3. every distinct method once, ascending; the (size, rank) leaders of an entry are read off when all have run (nothing in the buffer moves)
   for (size_t m = 0; m < methods.size(); m++) {
     const int cnt = (int)tabs[m].size();

@@ -50,7 +50,7 @@ struct zada_trained {
   uint8_t *d_text = nullptr;                        // decoder: the trainer's text up to the snapshot
   uint8_t *d_prefix = nullptr; uint64_t prefix_len = 0;   // decoder: stub [dec_fork_in .. skip)
   uint8_t *d_stub = nullptr;                        // decoder: stub [0 .. skip), for entries that decode their whole stream
-  uint8_t *d_tabs = nullptr, *d_arena = nullptr; uint64_t cap_tabs = 0, cap_arena = 0;
+  zada::DevBuf tabs, arena;
   zada_trained_info_t info{};
 };
 
@@ -88,16 +88,6 @@ __global__ void __launch_bounds__(TR_THREADS) k_tr_gather(const TrGather *__rest
 }
 }  // namespace
 
-static int tr_grow(Ctx *c, uint8_t **p, uint64_t *cap, uint64_t bytes, const char *what) {
-  if (*p && *cap >= bytes) return 0;
-  hipStreamSynchronize(c->stream);
-  if (*p) hipFree(*p);
-  *p = nullptr; *cap = 0;
-  const uint64_t want = ((bytes < (1u << 20) ? (1u << 20) : bytes) + 65535) & ~65535ull;
-  if (hipMalloc((void **)p, want) != hipSuccess) { (void)hipGetLastError(); c->err = what; return ZADA_E_NOMEM; }
-  *cap = want;
-  return 0;
-}
 static int tr_gather(Ctx *c, const std::vector<TrGather> &g, uint8_t *d_list) {
   if (g.empty()) return 0;
   hipMemcpyAsync(d_list, g.data(), g.size() * sizeof(TrGather), hipMemcpyHostToDevice, c->stream);
@@ -105,7 +95,7 @@ static int tr_gather(Ctx *c, const std::vector<TrGather> &g, uint8_t *d_list) {
   return hip_check(c, hipGetLastError(), "k_tr_gather") ? ZADA_E_HIP : 0;
 }
 static void tr_free(zada_trained *h) {
-  for (uint8_t *p : {h->d_trainer, h->d_fsnap, h->d_fout, h->d_stub, h->d_snap, h->d_text, h->d_prefix, h->d_tabs, h->d_arena}) if (p) hipFree(p);
+  for (uint8_t *p : {h->d_trainer, h->d_fsnap, h->d_fout, h->d_stub, h->d_snap, h->d_text, h->d_prefix, h->tabs.p, h->arena.p}) if (p) hipFree(p);
   delete h;
 }
 // the checks every call on a handle makes before it touches the device
@@ -133,11 +123,11 @@ static int tr_decode_group(Ctx *c, zada_trained *h, int g0, int g1, const zada_t
   const uint8_t *d_head = fork ? h->d_prefix : h->d_stub;
   uint64_t in_bytes = 0, out_bytes = 0;
   for (int i = g0; i < g1; i++) { in_bytes += a16(PL + ent[i].n); out_bytes += a16(T + ent[i].cap); }
-  int rc = tr_grow(c, &h->d_arena, &h->cap_arena, in_bytes + out_bytes + 16, "hipMalloc (trained arena)");
+  int rc = dev_grow(c, h->arena, in_bytes + out_bytes + 16, "hipMalloc (trained arena)");
   if (rc) return rc;
   const uint64_t o_gather = 0, o_jobs = o_gather + (uint64_t)E * sizeof(TrGather), o_order = o_jobs + (uint64_t)E * sizeof(UlzTrainedJob),
                  o_res = (o_order + (uint64_t)E * 4 + 15) & ~15ull, total = o_res + (uint64_t)E * sizeof(UlzResult);
-  rc = tr_grow(c, &h->d_tabs, &h->cap_tabs, total, "hipMalloc (trained tables)");
+  rc = dev_grow(c, h->tabs, total, "hipMalloc (trained tables)");
   if (rc) return rc;
   std::vector<TrGather> g(E);
   std::vector<UlzTrainedJob> jobs(E);
@@ -145,7 +135,7 @@ static int tr_decode_group(Ctx *c, zada_trained *h, int g0, int g1, const zada_t
   uint64_t io = 0, oo = in_bytes;
   for (uint32_t k = 0; k < E; k++) {
     const zada_trained_entry &e = ent[g0 + (int)k];
-    uint8_t *in_slot = h->d_arena + io, *out_slot = h->d_arena + oo;
+    uint8_t *in_slot = h->arena.p + io, *out_slot = h->arena.p + oo;
     g[k].c[0] = TrCopy{(uint64_t)(uintptr_t)d_head, (uint64_t)(uintptr_t)in_slot, PL};
     g[k].c[1] = TrCopy{(uint64_t)(uintptr_t)e.d_data, (uint64_t)(uintptr_t)(in_slot + PL), e.n};
     g[k].c[2] = TrCopy{(uint64_t)(uintptr_t)h->d_text, (uint64_t)(uintptr_t)out_slot, F};
@@ -155,7 +145,7 @@ static int tr_decode_group(Ctx *c, zada_trained *h, int g0, int g1, const zada_t
   }
   std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return jobs[a].n_in > jobs[b].n_in; });     // the longest first
   hipStream_t st = c->stream;
-  uint8_t *tb = h->d_tabs;
+  uint8_t *tb = h->tabs.p;
   c->tmark("trained:begin");
   if ((rc = tr_gather(c, g, tb + o_gather))) return rc;
   c->tmark("trained:k_tr_gather");
@@ -196,7 +186,7 @@ static int tr_encode_group(Ctx *c, zada_trained *h, const std::vector<int> &grou
   int rc = lzma_batch_layout(c, ZADA_LZMA_3, E, ln.data(), nullptr, D);
   if (rc) return rc;
   const uint64_t o_forked = (uint64_t)E * sizeof(TrGather);
-  rc = tr_grow(c, &h->d_tabs, &h->cap_tabs, o_forked + E, "hipMalloc (trained tables)");
+  rc = dev_grow(c, h->tabs, o_forked + E, "hipMalloc (trained tables)");
   if (rc) return rc;
   // an entry forks when ONE window fill holds its whole stream (String_buffer_size bytes at most): then the window's bookkeeping at the fork is
   // a function of the stream's length alone (k_lzma_fork_fill)
@@ -213,10 +203,10 @@ static int tr_encode_group(Ctx *c, zada_trained *h, const std::vector<int> &grou
     g[k].c[2] = TrCopy{0, 0, 0};
   }
   c->tbegin(); c->tmark("lzma:begin");
-  if ((rc = tr_gather(c, g, h->d_tabs))) return rc;
-  const LzFork fk{h->d_fsnap, h->d_fout, h->fout_len, h->d_tabs + o_forked};
+  if ((rc = tr_gather(c, g, h->tabs.p))) return rc;
+  const LzFork fk{h->d_fsnap, h->d_fout, h->fout_len, h->tabs.p + o_forked};
   if (h->d_fsnap && c->knob_trained_fork) {
-    hipMemcpyAsync(h->d_tabs + o_forked, forked.data(), E, hipMemcpyHostToDevice, c->stream);
+    hipMemcpyAsync(h->tabs.p + o_forked, forked.data(), E, hipMemcpyHostToDevice, c->stream);
     D.fork = &fk;
   }
   const int dict0 = c->knob_lzma_dict;
@@ -236,7 +226,7 @@ static int tr_encode_group(Ctx *c, zada_trained *h, const std::vector<int> &grou
     const uint64_t w = n < ent[i].cap ? n : ent[i].cap;
     if (w) { TrGather x{}; x.c[0] = TrCopy{(uint64_t)(uintptr_t)(D.d_out + D.off[k] + drop), (uint64_t)(uintptr_t)ent[i].d_out, w}; d.push_back(x); }
   }
-  if ((rc = tr_gather(c, d, h->d_tabs))) return rc;
+  if ((rc = tr_gather(c, d, h->tabs.p))) return rc;
   if (hip_check(c, hipStreamSynchronize(c->stream), "trained encode out")) return ZADA_E_HIP;
   c->tmark("lzma:end"); c->tend();
   if (*refused) lzma_batch_refused(c, D);                          // (the error text)
@@ -319,19 +309,19 @@ int zada_trained_open_decoder(zada_ctx *z, const uint8_t *stub, uint64_t stub_le
   if (hipMalloc((void **)&h->d_snap, snap_bytes) != hipSuccess || hipMalloc((void **)&h->d_text, t_len + 16) != hipSuccess) {
     (void)hipGetLastError(); c->err = "hipMalloc (trained snapshot)"; return fail(ZADA_E_NOMEM);
   }
-  int rc = tr_grow(c, &h->d_tabs, &h->cap_tabs, sizeof(UlzTrainedJob) + 16 + sizeof(UlzResult), "hipMalloc (trained tables)");
+  int rc = dev_grow(c, h->tabs, sizeof(UlzTrainedJob) + 16 + sizeof(UlzResult), "hipMalloc (trained tables)");
   if (rc) return fail(rc);
   const UlzTrainedJob job{(uint64_t)(uintptr_t)h->d_stub, (uint64_t)(uintptr_t)h->d_text, skip, t_len};
   const uint32_t order0 = 0;
   const uint64_t o_order = sizeof(UlzTrainedJob), o_res = o_order + 16;
   hipMemsetAsync(h->d_snap, 0, snap_bytes, st);
-  hipMemcpyAsync(h->d_tabs, &job, sizeof job, hipMemcpyHostToDevice, st);
-  hipMemcpyAsync(h->d_tabs + o_order, &order0, 4, hipMemcpyHostToDevice, st);
-  rc = unlzma_trained_launch(c, (const UlzTrainedJob *)h->d_tabs, (const uint32_t *)(h->d_tabs + o_order), 1, (UlzResult *)(h->d_tabs + o_res), nullptr, h->d_snap, skip);
+  hipMemcpyAsync(h->tabs.p, &job, sizeof job, hipMemcpyHostToDevice, st);
+  hipMemcpyAsync(h->tabs.p + o_order, &order0, 4, hipMemcpyHostToDevice, st);
+  rc = unlzma_trained_launch(c, (const UlzTrainedJob *)h->tabs.p, (const uint32_t *)(h->tabs.p + o_order), 1, (UlzResult *)(h->tabs.p + o_res), nullptr, h->d_snap, skip);
   if (rc) return fail(rc);
   UlzResult R;
   std::vector<uint8_t> snap(snap_bytes);
-  hipMemcpyAsync(&R, h->d_tabs + o_res, sizeof R, hipMemcpyDeviceToHost, st);
+  hipMemcpyAsync(&R, h->tabs.p + o_res, sizeof R, hipMemcpyDeviceToHost, st);
   hipMemcpyAsync(snap.data(), h->d_snap, snap_bytes, hipMemcpyDeviceToHost, st);
   if (hip_check(c, hipStreamSynchronize(st), "trained: the stub")) return fail(ZADA_E_HIP);
   char buf[240];

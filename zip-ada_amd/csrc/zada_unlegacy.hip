@@ -26,6 +26,7 @@
 #include <vector>
 #include "../../include/zada.h"
 #include "zada_internal.h"
+#include "zada_reader_host.h"
 #include "zada_unlegacy_logic.h"
 #include "zada_unlegacy_wave.h"
 
@@ -126,12 +127,8 @@ __global__ void __launch_bounds__(ULG_WAVE) k_explode(const UlgJob *__restrict__
 }
 
 // ---- host side ----
-struct UlgBuf { uint8_t *p = nullptr; uint64_t cap = 0; };
-struct UlgState {
-  uint32_t *d_counter = nullptr;                       // one per launch of a call
-  UlgBuf tabs, arena;                                  // jobs, orders, results / a group's inputs and outputs
+struct UlgState : ReaderState {                       // (d_counter: one per launch of a call)
   int cus = 0;
-  std::vector<uint64_t> last_entries;
 };
 
 static UlgState *ulg_state(Ctx *c) {
@@ -151,21 +148,10 @@ static UlgState *ulg_state(Ctx *c) {
 void unlegacy_destroy(Ctx *c) {
   UlgState *S = (UlgState *)c->ulg;
   if (!S) return;
-  if (S->tabs.p) hipFree(S->tabs.p);
-  if (S->arena.p) hipFree(S->arena.p);
+  dev_free(S->tabs); dev_free(S->arena);
   hipFree(S->d_counter);
   delete S;
   c->ulg = nullptr;
-}
-static int ulg_grow(Ctx *c, UlgBuf &b, uint64_t bytes, const char *what) {
-  if (b.p && b.cap >= bytes) return 0;
-  hipStreamSynchronize(c->stream);
-  if (b.p) hipFree(b.p);
-  b.p = nullptr; b.cap = 0;
-  const uint64_t want = ((bytes < (1u << 20) ? (1u << 20) : bytes) + 65535) & ~65535ull;
-  if (hipMalloc((void **)&b.p, want) != hipSuccess) { (void)hipGetLastError(); c->err = what; return ZADA_E_NOMEM; }
-  b.cap = want;
-  return 0;
 }
 
 // E jobs (device addresses) through one launch per format present and one of k_inf_crc; res [E] receives the records
@@ -181,13 +167,10 @@ static int ulg_run(Ctx *c, UlgState *S, const std::vector<UlgJob> &jobs, const u
     begin[k] = (uint32_t)order.size();
     order.insert(order.end(), by[k].begin(), by[k].end());
   }
-  const uint64_t o_jobs = 0, o_order = o_jobs + (uint64_t)E * sizeof(UlgJob), o_res = (o_order + (uint64_t)E * 4 + 15) & ~15ull, total = o_res + (uint64_t)E * sizeof(UlgResult);
-  int rc = ulg_grow(c, S->tabs, total, "hipMalloc (unlegacy tables)");
+  ReaderTables<UlgJob, UlgResult> T;
+  int rc = reader_tables_send(c, S, "unlegacy", jobs, order, nullptr, ULG_NKERNELS, T);
   if (rc) return rc;
   hipStream_t st = c->stream;
-  hipMemcpyAsync(S->tabs.p + o_jobs, jobs.data(), (size_t)E * sizeof(UlgJob), hipMemcpyHostToDevice, st);
-  hipMemcpyAsync(S->tabs.p + o_order, order.data(), (size_t)E * 4, hipMemcpyHostToDevice, st);
-  hipMemsetAsync(S->d_counter, 0, ULG_NKERNELS * 4, st);
   c->tmark("unlegacy:begin");
   static const uint32_t per_cu[ULG_NKERNELS] = {4u, 9u, 16u};
   static const char *const mark[ULG_NKERNELS] = {"unlegacy:k_unshrink", "unlegacy:k_unreduce", "unlegacy:k_explode"};
@@ -196,16 +179,14 @@ static int ulg_run(Ctx *c, UlgState *S, const std::vector<UlgJob> &jobs, const u
     if (!n) continue;
     const uint32_t waves = (uint32_t)S->cus * per_cu[k];
     const uint32_t grid = n < waves ? n : waves;
-    const UlgJob *d_jobs = (const UlgJob *)(S->tabs.p + o_jobs);
-    const uint32_t *d_order = (const uint32_t *)(S->tabs.p + o_order) + begin[k];
-    UlgResult *d_res = (UlgResult *)(S->tabs.p + o_res);
-    if (k == ULG_K_SHRINK) hipLaunchKernelGGL(k_unshrink, dim3(grid), dim3(ULG_WAVE), 0, st, d_jobs, d_order, n, S->d_counter + k, d_res);
-    else if (k == ULG_K_REDUCE) hipLaunchKernelGGL(k_unreduce, dim3(grid), dim3(ULG_WAVE), 0, st, d_jobs, d_order, n, S->d_counter + k, d_res);
-    else hipLaunchKernelGGL(k_explode, dim3(grid), dim3(ULG_WAVE), 0, st, d_jobs, d_order, n, S->d_counter + k, d_res);
+    const uint32_t *d_order = T.order + begin[k];
+    if (k == ULG_K_SHRINK) hipLaunchKernelGGL(k_unshrink, dim3(grid), dim3(ULG_WAVE), 0, st, T.jobs, d_order, n, S->d_counter + k, T.res);
+    else if (k == ULG_K_REDUCE) hipLaunchKernelGGL(k_unreduce, dim3(grid), dim3(ULG_WAVE), 0, st, T.jobs, d_order, n, S->d_counter + k, T.res);
+    else hipLaunchKernelGGL(k_explode, dim3(grid), dim3(ULG_WAVE), 0, st, T.jobs, d_order, n, S->d_counter + k, T.res);
     c->tmark(mark[k]);
   }
-  hipMemcpyAsync(res.data(), S->tabs.p + o_res, (size_t)E * sizeof(UlgResult), hipMemcpyDeviceToHost, st);
-  if (hip_check(c, hipGetLastError(), "unlegacy launch") || hip_check(c, hipStreamSynchronize(st), "unlegacy")) return ZADA_E_HIP;
+  rc = reader_tables_fetch(c, "unlegacy", T, res);
+  if (rc) return rc;
   // the entries' Zip CRC-32 (k_inf_crc)
   std::vector<uint64_t> optr(E), olen(E);
   std::vector<uint32_t> regs(E);
@@ -226,23 +207,16 @@ static void ulg_describe(Ctx *c, const UlgResult &R, int entry) {
   c->err = buf;
 }
 
+struct UlgReader : ReaderTraits<UlgJob, UlgResult, UlgState> {
+  static constexpr const char *word = "unlegacy";
+  static UlgState *state(Ctx *c) { return ulg_state(c); }
+  static int run(Ctx *c, UlgState *S, std::vector<UlgJob> &jobs, const uint32_t *crc_in, std::vector<UlgResult> &res, uint32_t) { return ulg_run(c, S, jobs, crc_in, res); }
+  static void describe(Ctx *c, const UlgResult &R, int entry) { ulg_describe(c, R, entry); }
+};
+
 // ulg_run for zada_unzip_device (zada_internal.h): ReaderJob::format is the method (1 .. 6), eos the entry's general-purpose bits 1 and 2
 int unlegacy_run_jobs(Ctx *c, uint32_t E, const ReaderJob *rj, ReaderRes *rr, bool *described) {
-  if (E == 0) return 0;
-  UlgState *S = ulg_state(c);
-  if (!S) { c->err = "unlegacy: no memory for the tables"; return ZADA_E_NOMEM; }
-  std::vector<UlgJob> jobs(E);
-  std::vector<uint32_t> regs(E);
-  std::vector<UlgResult> res;
-  for (uint32_t k = 0; k < E; k++) { jobs[k] = UlgJob{rj[k].in, rj[k].out, rj[k].n_in, rj[k].cap, (uint32_t)rj[k].format, rj[k].eos & 6u}; regs[k] = rr[k].crc; }
-  S->last_entries.clear();
-  const int rc = ulg_run(c, S, jobs, regs.data(), res);
-  if (rc) return rc;
-  for (uint32_t k = 0; k < E; k++) {
-    if (res[k].rc) { rr[k] = ReaderRes{ZADA_E_DATA, regs[k], 0, 0}; if (!*described) { ulg_describe(c, res[k], rj[k].index); *described = true; } }
-    else rr[k] = ReaderRes{ZADA_OK, res[k].crc, res[k].out_len, res[k].in_used};
-  }
-  return 0;
+  return reader_run_jobs<UlgReader>(c, E, rj, rr, described, [](const ReaderJob &J) { return UlgJob{J.in, J.out, J.n_in, J.cap, (uint32_t)J.format, J.eos & 6u}; });
 }
 
 }  // namespace zada
@@ -259,25 +233,10 @@ int zada_unlegacy_device(zada_ctx *z, int method, int flags, const void *d_in, u
   if (method < 1 || method > 6) { c->err = "zada_unlegacy_device: method outside 1 .. 6 (1 Shrink, 2 .. 5 Reduce, 6 Implode)"; return ZADA_E_INVALID; }
   if ((n_in && !d_in) || (cap && !d_out)) { c->err = "zada_unlegacy_device: null buffer"; return ZADA_E_INVALID; }
   if (n_in >= ULG_MAX_BYTES || cap >= ULG_MAX_BYTES) { c->err = "zada_unlegacy_device: a stream or an output of 1 TiB or more"; return ZADA_E_TOO_LARGE; }
-  if (out_len) *out_len = 0;
-  if (in_used) *in_used = 0;
-  if (hipSetDevice(c->device) != hipSuccess) return ZADA_E_HIP;
-  UlgState *S = ulg_state(c);
-  if (!S) { c->err = "unlegacy: no memory for the tables"; return ZADA_E_NOMEM; }
-  std::vector<UlgJob> jobs(1);
-  jobs[0] = UlgJob{(uint64_t)(uintptr_t)d_in, (uint64_t)(uintptr_t)d_out, n_in, cap, (uint32_t)method, (uint32_t)flags & 6u};
-  std::vector<UlgResult> res;
-  const uint32_t reg = crc_inout ? *crc_inout : 0u;
-  S->last_entries.clear();
-  c->tbegin();
-  int rc = ulg_run(c, S, jobs, &reg, res);
-  c->tend();
-  if (rc) { hipStreamSynchronize(c->stream); (void)hipGetLastError(); return rc; }
-  if (res[0].rc) { ulg_describe(c, res[0], 0); return ZADA_E_DATA; }
-  if (out_len) *out_len = res[0].out_len;
-  if (in_used) *in_used = res[0].in_used;
-  if (crc_inout) *crc_inout = res[0].crc;
-  return ZADA_OK;
+  return reader_device_one<UlgReader>(c, out_len, in_used, crc_inout, [&](UlgJob &J) {
+    J = UlgJob{(uint64_t)(uintptr_t)d_in, (uint64_t)(uintptr_t)d_out, n_in, cap, (uint32_t)method, (uint32_t)flags & 6u};
+    return 0;
+  });
 }
 
 int zada_unlegacy_batch(zada_ctx *z, int count, const uint8_t *const *in, const uint64_t *n_in, uint8_t *const *out, const uint64_t *cap, const uint16_t *method,
@@ -292,65 +251,9 @@ int zada_unlegacy_batch(zada_ctx *z, int count, const uint8_t *const *in, const 
     if (n_in[i] >= ULG_MAX_BYTES || cap[i] >= ULG_MAX_BYTES) { c->err = "zada_unlegacy_batch: a stream or an output of 1 TiB or more"; return ZADA_E_TOO_LARGE; }
   }
   if (count == 0) return ZADA_OK;
-  if (hipSetDevice(c->device) != hipSuccess) return ZADA_E_HIP;
-  UlgState *S = ulg_state(c);
-  if (!S) { c->err = "unlegacy: no memory for the tables"; return ZADA_E_NOMEM; }
-  int worst = 0, worst_entry = -1;
-  UlgResult worst_rec{};
-  const uint64_t limit = (uint64_t)c->knob_batch_mib << 20;
-  std::vector<uint8_t> host;
-  std::vector<UlgJob> jobs;
-  std::vector<UlgResult> res;
-  std::vector<uint32_t> regs;
-  std::vector<uint64_t> ooff;
-  S->last_entries.clear();
-  c->tbegin();
-  for (int g0 = 0; g0 < count;) {
-    // a group: entries g0 .. g1 - 1, inputs then outputs in one arena, every buffer at a multiple of 16
-    uint64_t in_bytes = 0, out_bytes = 0;
-    int g1 = g0;
-    while (g1 < count) {
-      const uint64_t a = (n_in[g1] + 15) & ~15ull, b = (cap[g1] + 15) & ~15ull;
-      if (g1 > g0 && in_bytes + out_bytes + a + b > limit) break;
-      in_bytes += a; out_bytes += b; g1++;
-    }
-    const uint32_t E = (uint32_t)(g1 - g0);
-    int rc = ulg_grow(c, S->arena, in_bytes + out_bytes + 16, "hipMalloc (unlegacy arena)");
-    if (rc) { c->tend(); return rc; }
-    host.resize(in_bytes ? in_bytes : 1);
-    jobs.resize(E); regs.resize(E); ooff.resize(E);
-    uint64_t io = 0, oo = in_bytes;
-    for (uint32_t k = 0; k < E; k++) {
-      const int i = g0 + (int)k;
-      if (n_in[i]) memcpy(host.data() + io, in[i], n_in[i]);
-      jobs[k] = UlgJob{(uint64_t)(uintptr_t)(S->arena.p + io), (uint64_t)(uintptr_t)(S->arena.p + oo), n_in[i], cap[i], method[i], flags ? (uint32_t)flags[i] & 6u : 0u};
-      regs[k] = crc ? crc[i] : 0u;
-      ooff[k] = oo;
-      io += (n_in[i] + 15) & ~15ull; oo += (cap[i] + 15) & ~15ull;
-    }
-    if (in_bytes) hipMemcpyAsync(S->arena.p, host.data(), in_bytes, hipMemcpyHostToDevice, c->stream);
-    rc = ulg_run(c, S, jobs, regs.data(), res);
-    if (rc) { hipStreamSynchronize(c->stream); (void)hipGetLastError(); c->tend(); return rc; }
-    // the outputs come back in one piece up to the last byte any entry wrote
-    uint64_t hi = 0;
-    if (out) for (uint32_t k = 0; k < E; k++) if (res[k].rc == 0 && res[k].out_len) hi = ooff[k] + res[k].out_len - in_bytes;
-    host.resize(hi ? hi : 1);
-    if (hi && (hip_check(c, hipMemcpyAsync(host.data(), S->arena.p + in_bytes, hi, hipMemcpyDeviceToHost, c->stream), "unlegacy copy out") ||
-               hip_check(c, hipStreamSynchronize(c->stream), "unlegacy copy out"))) { c->tend(); return ZADA_E_HIP; }
-    for (uint32_t k = 0; k < E; k++) {
-      const int i = g0 + (int)k;
-      rc_out[i] = res[k].rc ? ZADA_E_DATA : ZADA_OK;
-      if (out_len) out_len[i] = res[k].out_len;
-      if (in_used) in_used[i] = res[k].in_used;
-      if (res[k].rc) { if (worst == 0) { worst = ZADA_E_DATA; worst_entry = i; worst_rec = res[k]; } continue; }
-      if (crc) crc[i] = res[k].crc;
-      if (out && res[k].out_len) memcpy(out[i], host.data() + (ooff[k] - in_bytes), res[k].out_len);
-    }
-    g0 = g1;
-  }
-  c->tend();
-  if (worst) ulg_describe(c, worst_rec, worst_entry);
-  return worst;
+  return reader_batch<UlgReader>(c, count, in, n_in, out, cap, out_len, in_used, crc, rc_out, [&](int i, uint64_t d_in, uint64_t d_out) {
+    return UlgJob{d_in, d_out, n_in[i], cap[i], method[i], flags ? (uint32_t)flags[i] & 6u : 0u};
+  });
 }
 
 int zada_unlegacy(zada_ctx *z, int method, int flags, const uint8_t *in, uint64_t n_in, uint8_t *out, uint64_t cap, uint64_t *out_len, uint64_t *in_used,
@@ -359,25 +262,14 @@ int zada_unlegacy(zada_ctx *z, int method, int flags, const uint8_t *in, uint64_
   z->c.lz_stopped = false;
   if (method < 1 || method > 6) { z->c.err = "zada_unlegacy: method outside 1 .. 6 (1 Shrink, 2 .. 5 Reduce, 6 Implode)"; return ZADA_E_INVALID; }
   if ((n_in && !in) || (cap && !out)) { z->c.err = "zada_unlegacy: null buffer"; return ZADA_E_INVALID; }
-  if (out_len) *out_len = 0;
-  if (in_used) *in_used = 0;
-  uint64_t ol = 0, iu = 0;
-  uint32_t reg = crc_inout ? *crc_inout : 0u;
-  int erc = 0;
   const uint16_t m = (uint16_t)method;
   const uint8_t f = (uint8_t)(flags & 6);
-  int rc = zada_unlegacy_batch(z, 1, &in, &n_in, &out, &cap, &m, &f, &ol, &iu, &reg, &erc);
-  if (rc) return rc;
-  if (out_len) *out_len = ol;
-  if (in_used) *in_used = iu;
-  if (crc_inout) *crc_inout = reg;
-  return ZADA_OK;
+  return reader_single(out_len, in_used, crc_inout, [&](uint64_t *ol, uint64_t *iu, uint32_t *reg, int *erc) {
+    return zada_unlegacy_batch(z, 1, &in, &n_in, &out, &cap, &m, &f, ol, iu, reg, erc);
+  });
 }
 
 uint64_t zada_unlegacy_last_records(zada_ctx *z, uint64_t *dst, uint64_t cap_items) {
   if (!z || !z->c.ulg || (cap_items && !dst)) return 0;
-  const std::vector<uint64_t> &v = ((const UlgState *)z->c.ulg)->last_entries;
-  const uint64_t n = v.size() < cap_items ? v.size() : cap_items;
-  if (n) memcpy(dst, v.data(), n * 8);
-  return v.size();
+  return reader_last_records(((const UlgState *)z->c.ulg)->last_entries, dst, cap_items);
 }

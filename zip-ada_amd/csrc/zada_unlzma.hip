@@ -31,6 +31,7 @@
 #include <vector>
 #include "../../include/zada.h"
 #include "zada_internal.h"
+#include "zada_reader_host.h"
 #include "zada_unlzma_logic.h"
 
 struct zada_ctx { zada::Ctx c; };
@@ -249,12 +250,9 @@ __global__ void __launch_bounds__(ULZ_WAVE) k_unlzma_trained(const UlzTrainedJob
 }
 
 // ---- host side ----
-struct UlzBuf { uint8_t *p = nullptr; uint64_t cap = 0; };
-struct UlzState {
-  uint32_t *d_counter = nullptr;                       // one per launch of a call
-  UlzBuf tabs, arena, lit;                             // jobs, orders, results / a group's inputs and outputs / the HBM literal tables of a launch group
+struct UlzState : ReaderState {                       // (d_counter: one per launch of a call)
+  DevBuf lit;                                          // the HBM literal tables of a launch group
   int cus = 0;
-  std::vector<uint64_t> last_entries;
 };
 constexpr uint32_t ULZ_MAX_LAUNCHES = 4096;
 
@@ -275,22 +273,10 @@ static UlzState *ulz_state(Ctx *c) {
 void unlzma_destroy(Ctx *c) {
   UlzState *S = (UlzState *)c->ulz;
   if (!S) return;
-  if (S->tabs.p) hipFree(S->tabs.p);
-  if (S->arena.p) hipFree(S->arena.p);
-  if (S->lit.p) hipFree(S->lit.p);
+  dev_free(S->tabs); dev_free(S->arena); dev_free(S->lit);
   hipFree(S->d_counter);
   delete S;
   c->ulz = nullptr;
-}
-static int ulz_grow(Ctx *c, UlzBuf &b, uint64_t bytes, const char *what) {
-  if (b.p && b.cap >= bytes) return 0;
-  hipStreamSynchronize(c->stream);
-  if (b.p) hipFree(b.p);
-  b.p = nullptr; b.cap = 0;
-  const uint64_t want = ((bytes < (1u << 20) ? (1u << 20) : bytes) + 65535) & ~65535ull;
-  if (hipMalloc((void **)&b.p, want) != hipSuccess) { (void)hipGetLastError(); c->err = what; return ZADA_E_NOMEM; }
-  b.cap = want;
-  return 0;
 }
 
 // the literal table an entry needs in HBM, in probabilities (0: it fits the LDS, or the header is refused anyway), from its first nine bytes
@@ -333,31 +319,25 @@ static int ulz_run(Ctx *c, UlzState *S, std::vector<UlzJob> &jobs, const uint32_
   if (l_begin.size() > ULZ_MAX_LAUNCHES) { c->err = "unlzma: more launch groups than 4096: raise the knob lzma_lit_mib"; return ZADA_E_INVALID; }
   int rc = 0;
   if (lit_max) {
-    rc = ulz_grow(c, S->lit, lit_max, "hipMalloc (unlzma literal tables)");
+    rc = dev_grow(c, S->lit, lit_max, "hipMalloc (unlzma literal tables)");
     if (rc) return rc;
     for (uint32_t i : hbm) jobs[i].lit += (uint64_t)(uintptr_t)S->lit.p;
   }
-  const uint64_t o_jobs = 0, o_order = o_jobs + (uint64_t)E * sizeof(UlzJob), o_res = (o_order + (uint64_t)E * 4 + 15) & ~15ull, total = o_res + (uint64_t)E * sizeof(UlzResult);
-  rc = ulz_grow(c, S->tabs, total, "hipMalloc (unlzma tables)");
+  ReaderTables<UlzJob, UlzResult> T;
+  rc = reader_tables_send(c, S, "unlzma", jobs, order, nullptr, (uint32_t)l_begin.size(), T);
   if (rc) return rc;
   hipStream_t st = c->stream;
-  hipMemcpyAsync(S->tabs.p + o_jobs, jobs.data(), (size_t)E * sizeof(UlzJob), hipMemcpyHostToDevice, st);
-  hipMemcpyAsync(S->tabs.p + o_order, order.data(), (size_t)E * 4, hipMemcpyHostToDevice, st);
-  hipMemsetAsync(S->d_counter, 0, l_begin.size() * 4, st);
   c->tmark("unlzma:begin");
   for (size_t l = 0; l < l_begin.size(); l++) {
     const uint32_t n = l_count[l];
     const uint32_t waves = (uint32_t)S->cus * (l_mode[l] == ULM_LDS ? 10u : 16u);
     const uint32_t grid = n < waves ? n : waves;
-    const uint32_t *d_order = (const uint32_t *)(S->tabs.p + o_order) + l_begin[l];
-    if (l_mode[l] == ULM_LDS)
-      hipLaunchKernelGGL(k_unlzma<ULM_LDS>, dim3(grid), dim3(ULZ_WAVE), 0, st, (const UlzJob *)(S->tabs.p + o_jobs), d_order, n, S->d_counter + l, (UlzResult *)(S->tabs.p + o_res));
-    else
-      hipLaunchKernelGGL(k_unlzma<ULM_HBM>, dim3(grid), dim3(ULZ_WAVE), 0, st, (const UlzJob *)(S->tabs.p + o_jobs), d_order, n, S->d_counter + l, (UlzResult *)(S->tabs.p + o_res));
+    if (l_mode[l] == ULM_LDS) hipLaunchKernelGGL(k_unlzma<ULM_LDS>, dim3(grid), dim3(ULZ_WAVE), 0, st, T.jobs, T.order + l_begin[l], n, S->d_counter + l, T.res);
+    else hipLaunchKernelGGL(k_unlzma<ULM_HBM>, dim3(grid), dim3(ULZ_WAVE), 0, st, T.jobs, T.order + l_begin[l], n, S->d_counter + l, T.res);
   }
   c->tmark("unlzma:k_unlzma");
-  hipMemcpyAsync(res.data(), S->tabs.p + o_res, (size_t)E * sizeof(UlzResult), hipMemcpyDeviceToHost, st);
-  if (hip_check(c, hipGetLastError(), "unlzma launch") || hip_check(c, hipStreamSynchronize(st), "unlzma")) return ZADA_E_HIP_;
+  rc = reader_tables_fetch(c, "unlzma", T, res);
+  if (rc) return rc;
   // the entries' Zip CRC-32 (k_inf_crc)
   std::vector<uint64_t> optr(E), olen(E);
   std::vector<uint32_t> regs(E);
@@ -378,24 +358,17 @@ static void ulz_describe(Ctx *c, const UlzResult &R, int entry) {
   c->err = buf;
 }
 
+struct UlzReader : ReaderTraits<UlzJob, UlzResult, UlzState> {
+  static constexpr const char *word = "unlzma";
+  static UlzState *state(Ctx *c) { return ulz_state(c); }
+  static int run(Ctx *c, UlzState *S, std::vector<UlzJob> &jobs, const uint32_t *crc_in, std::vector<UlzResult> &res, uint32_t) { return ulz_run(c, S, jobs, crc_in, res); }
+  static void describe(Ctx *c, const UlzResult &R, int entry) { ulz_describe(c, R, entry); }
+};
+
 // ulz_run for zada_unzip_device (zada_internal.h)
 uint64_t unlzma_hbm_elems(const uint8_t *h9, uint64_t n_in) { return ulz_hbm_elems(h9, n_in); }
 int unlzma_run_jobs(Ctx *c, uint32_t E, const ReaderJob *rj, ReaderRes *rr, bool *described) {
-  if (E == 0) return 0;
-  UlzState *S = ulz_state(c);
-  if (!S) { c->err = "unlzma: no memory for the tables"; return ZADA_E_NOMEM; }
-  std::vector<UlzJob> jobs(E);
-  std::vector<uint32_t> regs(E);
-  std::vector<UlzResult> res;
-  for (uint32_t k = 0; k < E; k++) { jobs[k] = UlzJob{rj[k].in, rj[k].out, rj[k].n_in, rj[k].cap, 0, rj[k].lit_elems, rj[k].eos ? 1u : 0u, 0}; regs[k] = rr[k].crc; }
-  S->last_entries.clear();
-  const int rc = ulz_run(c, S, jobs, regs.data(), res);
-  if (rc) return rc;
-  for (uint32_t k = 0; k < E; k++) {
-    if (res[k].rc) { rr[k] = ReaderRes{ZADA_E_DATA, regs[k], 0, 0}; if (!*described) { ulz_describe(c, res[k], rj[k].index); *described = true; } }
-    else rr[k] = ReaderRes{ZADA_OK, res[k].crc, res[k].out_len, res[k].in_used};
-  }
-  return 0;
+  return reader_run_jobs<UlzReader>(c, E, rj, rr, described, [](const ReaderJob &J) { return UlzJob{J.in, J.out, J.n_in, J.cap, 0, J.lit_elems, J.eos ? 1u : 0u, 0}; });
 }
 
 // k_unlzma_trained for zada_trained.hip (zada_internal.h)
@@ -432,27 +405,12 @@ int zada_unlzma_device(zada_ctx *z, const void *d_in, uint64_t n_in, void *d_out
   c->lz_stopped = false;
   if ((n_in && !d_in) || (cap && !d_out)) { c->err = "zada_unlzma_device: null buffer"; return ZADA_E_INVALID; }
   if (n_in >= ULZ_MAX_BYTES || cap >= ULZ_MAX_BYTES) { c->err = "zada_unlzma_device: a stream or an output of 1 TiB or more"; return ZADA_E_TOO_LARGE; }
-  if (out_len) *out_len = 0;
-  if (in_used) *in_used = 0;
-  if (hipSetDevice(c->device) != hipSuccess) return ZADA_E_HIP;
-  UlzState *S = ulz_state(c);
-  if (!S) { c->err = "unlzma: no memory for the tables"; return ZADA_E_NOMEM; }
-  uint8_t h9[9] = {0};
-  if (n_in && hip_check(c, hipMemcpy(h9, d_in, n_in < 9 ? n_in : 9, hipMemcpyDeviceToHost), "unlzma header")) return ZADA_E_HIP;
-  std::vector<UlzJob> jobs(1);
-  jobs[0] = UlzJob{(uint64_t)(uintptr_t)d_in, (uint64_t)(uintptr_t)d_out, n_in, cap, 0, ulz_hbm_elems(h9, n_in), eos ? 1u : 0u, 0};
-  std::vector<UlzResult> res;
-  const uint32_t reg = crc_inout ? *crc_inout : 0u;
-  S->last_entries.clear();
-  c->tbegin();
-  int rc = ulz_run(c, S, jobs, &reg, res);
-  c->tend();
-  if (rc) { hipStreamSynchronize(c->stream); (void)hipGetLastError(); return rc; }
-  if (res[0].rc) { ulz_describe(c, res[0], 0); return ZADA_E_DATA; }
-  if (out_len) *out_len = res[0].out_len;
-  if (in_used) *in_used = res[0].in_used;
-  if (crc_inout) *crc_inout = res[0].crc;
-  return ZADA_OK;
+  return reader_device_one<UlzReader>(c, out_len, in_used, crc_inout, [&](UlzJob &J) {
+    uint8_t h9[9] = {0};
+    if (n_in && hip_check(c, hipMemcpy(h9, d_in, n_in < 9 ? n_in : 9, hipMemcpyDeviceToHost), "unlzma header")) return (int)ZADA_E_HIP;
+    J = UlzJob{(uint64_t)(uintptr_t)d_in, (uint64_t)(uintptr_t)d_out, n_in, cap, 0, ulz_hbm_elems(h9, n_in), eos ? 1u : 0u, 0};
+    return 0;
+  });
 }
 
 int zada_unlzma_batch(zada_ctx *z, int count, const uint8_t *const *in, const uint64_t *n_in, uint8_t *const *out, const uint64_t *cap, const int *eos,
@@ -466,90 +424,23 @@ int zada_unlzma_batch(zada_ctx *z, int count, const uint8_t *const *in, const ui
     if (n_in[i] >= ULZ_MAX_BYTES || cap[i] >= ULZ_MAX_BYTES) { c->err = "zada_unlzma_batch: a stream or an output of 1 TiB or more"; return ZADA_E_TOO_LARGE; }
   }
   if (count == 0) return ZADA_OK;
-  if (hipSetDevice(c->device) != hipSuccess) return ZADA_E_HIP;
-  UlzState *S = ulz_state(c);
-  if (!S) { c->err = "unlzma: no memory for the tables"; return ZADA_E_NOMEM; }
-  int worst = 0, worst_entry = -1;
-  UlzResult worst_rec{};
-  const uint64_t limit = (uint64_t)c->knob_batch_mib << 20;
-  std::vector<uint8_t> host;
-  std::vector<UlzJob> jobs;
-  std::vector<UlzResult> res;
-  std::vector<uint32_t> regs;
-  std::vector<uint64_t> ooff;
-  S->last_entries.clear();
-  c->tbegin();
-  for (int g0 = 0; g0 < count;) {
-    // a group: entries g0 .. g1 - 1, inputs then outputs in one arena, every buffer at a multiple of 16
-    uint64_t in_bytes = 0, out_bytes = 0;
-    int g1 = g0;
-    while (g1 < count) {
-      const uint64_t a = (n_in[g1] + 15) & ~15ull, b = (cap[g1] + 15) & ~15ull;
-      if (g1 > g0 && in_bytes + out_bytes + a + b > limit) break;
-      in_bytes += a; out_bytes += b; g1++;
-    }
-    const uint32_t E = (uint32_t)(g1 - g0);
-    int rc = ulz_grow(c, S->arena, in_bytes + out_bytes + 16, "hipMalloc (unlzma arena)");
-    if (rc) { c->tend(); return rc; }
-    host.resize(in_bytes ? in_bytes : 1);
-    jobs.resize(E); regs.resize(E); ooff.resize(E);
-    uint64_t io = 0, oo = in_bytes;
-    for (uint32_t k = 0; k < E; k++) {
-      const int i = g0 + (int)k;
-      if (n_in[i]) memcpy(host.data() + io, in[i], n_in[i]);
-      uint8_t h9[9] = {0};
-      if (n_in[i]) memcpy(h9, in[i], n_in[i] < 9 ? n_in[i] : 9);
-      jobs[k] = UlzJob{(uint64_t)(uintptr_t)(S->arena.p + io), (uint64_t)(uintptr_t)(S->arena.p + oo), n_in[i], cap[i], 0, ulz_hbm_elems(h9, n_in[i]), eos[i] ? 1u : 0u, 0};
-      regs[k] = crc ? crc[i] : 0u;
-      ooff[k] = oo;
-      io += (n_in[i] + 15) & ~15ull; oo += (cap[i] + 15) & ~15ull;
-    }
-    if (in_bytes) hipMemcpyAsync(S->arena.p, host.data(), in_bytes, hipMemcpyHostToDevice, c->stream);
-    rc = ulz_run(c, S, jobs, regs.data(), res);
-    if (rc) { hipStreamSynchronize(c->stream); (void)hipGetLastError(); c->tend(); return rc; }
-    // the outputs come back in one piece up to the last byte any entry wrote
-    uint64_t hi = 0;
-    if (out) for (uint32_t k = 0; k < E; k++) if (res[k].rc == 0 && res[k].out_len) hi = ooff[k] + res[k].out_len - in_bytes;
-    host.resize(hi ? hi : 1);
-    if (hi && (hip_check(c, hipMemcpyAsync(host.data(), S->arena.p + in_bytes, hi, hipMemcpyDeviceToHost, c->stream), "unlzma copy out") ||
-               hip_check(c, hipStreamSynchronize(c->stream), "unlzma copy out"))) { c->tend(); return ZADA_E_HIP; }
-    for (uint32_t k = 0; k < E; k++) {
-      const int i = g0 + (int)k;
-      rc_out[i] = res[k].rc ? ZADA_E_DATA : ZADA_OK;
-      if (out_len) out_len[i] = res[k].out_len;
-      if (in_used) in_used[i] = res[k].in_used;
-      if (res[k].rc) { if (worst == 0) { worst = ZADA_E_DATA; worst_entry = i; worst_rec = res[k]; } continue; }
-      if (crc) crc[i] = res[k].crc;
-      if (out && res[k].out_len) memcpy(out[i], host.data() + (ooff[k] - in_bytes), res[k].out_len);
-    }
-    g0 = g1;
-  }
-  c->tend();
-  if (worst) ulz_describe(c, worst_rec, worst_entry);
-  return worst;
+  return reader_batch<UlzReader>(c, count, in, n_in, out, cap, out_len, in_used, crc, rc_out, [&](int i, uint64_t d_in, uint64_t d_out) {
+    uint8_t h9[9] = {0};
+    if (n_in[i]) memcpy(h9, in[i], n_in[i] < 9 ? n_in[i] : 9);
+    return UlzJob{d_in, d_out, n_in[i], cap[i], 0, ulz_hbm_elems(h9, n_in[i]), eos[i] ? 1u : 0u, 0};
+  });
 }
 
 int zada_unlzma(zada_ctx *z, const uint8_t *in, uint64_t n_in, uint8_t *out, uint64_t cap, int eos, uint64_t *out_len, uint64_t *in_used, uint32_t *crc_inout) {
   if (!z) return ZADA_E_INVALID;
   z->c.lz_stopped = false;
   if ((n_in && !in) || (cap && !out)) { z->c.err = "zada_unlzma: null buffer"; return ZADA_E_INVALID; }
-  if (out_len) *out_len = 0;
-  if (in_used) *in_used = 0;
-  uint64_t ol = 0, iu = 0;
-  uint32_t reg = crc_inout ? *crc_inout : 0u;
-  int erc = 0;
-  int rc = zada_unlzma_batch(z, 1, &in, &n_in, &out, &cap, &eos, &ol, &iu, &reg, &erc);
-  if (rc) return rc;
-  if (out_len) *out_len = ol;
-  if (in_used) *in_used = iu;
-  if (crc_inout) *crc_inout = reg;
-  return ZADA_OK;
+  return reader_single(out_len, in_used, crc_inout, [&](uint64_t *ol, uint64_t *iu, uint32_t *reg, int *erc) {
+    return zada_unlzma_batch(z, 1, &in, &n_in, &out, &cap, &eos, ol, iu, reg, erc);
+  });
 }
 
 uint64_t zada_unlzma_last_records(zada_ctx *z, uint64_t *dst, uint64_t cap_items) {
   if (!z || !z->c.ulz || (cap_items && !dst)) return 0;
-  const std::vector<uint64_t> &v = ((const UlzState *)z->c.ulz)->last_entries;
-  const uint64_t n = v.size() < cap_items ? v.size() : cap_items;
-  if (n) memcpy(dst, v.data(), n * 8);
-  return v.size();
+  return reader_last_records(((const UlzState *)z->c.ulz)->last_entries, dst, cap_items);
 }

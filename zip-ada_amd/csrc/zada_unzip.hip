@@ -233,10 +233,9 @@ __global__ void __launch_bounds__(UZ_WAVE) k_uz_fold(const UzStoreEnt *__restric
 }
 
 // ---- host side ----
-struct UzBuf { uint8_t *p = nullptr; uint64_t cap = 0; };
 struct UzState {
   UzOps *d_ops = nullptr;
-  UzBuf tabs, ptab, scratch, out;      // decode / gather tables; the stored entries' tables; the decoded copies of encrypted entries; the test-only form's outputs
+  DevBuf tabs, ptab, scratch, out;      // decode / gather tables; the stored entries' tables; the decoded copies of encrypted entries; the test-only form's outputs
 };
 
 static UzState *uz_state(Ctx *c) {
@@ -263,20 +262,10 @@ static UzState *uz_state(Ctx *c) {
 void unzip_destroy(Ctx *c) {
   UzState *S = (UzState *)c->uz;
   if (!S) return;
-  for (UzBuf *b : {&S->tabs, &S->ptab, &S->scratch, &S->out}) if (b->p) hipFree(b->p);
+  for (DevBuf *b : {&S->tabs, &S->ptab, &S->scratch, &S->out}) dev_free(*b);
   hipFree(S->d_ops);
   delete S;
   c->uz = nullptr;
-}
-static int uz_grow(Ctx *c, UzBuf &b, uint64_t bytes, const char *what) {
-  if (b.p && b.cap >= bytes) return 0;
-  hipStreamSynchronize(c->stream);
-  if (b.p) hipFree(b.p);
-  b.p = nullptr; b.cap = 0;
-  const uint64_t want = ((bytes < (1u << 20) ? (1u << 20) : bytes) + 65535) & ~65535ull;
-  if (hipMalloc((void **)&b.p, want) != hipSuccess) { (void)hipGetLastError(); c->err = what; return ZADA_E_NOMEM; }
-  b.cap = want;
-  return 0;
 }
 struct UzCarve {
   uint64_t at = 0;
@@ -309,7 +298,7 @@ static int uz_store_run(Ctx *c, UzState *S, std::vector<UzStoreEnt> &se, const s
   UzCarve pc;
   const uint64_t p_ent = pc.take((uint64_t)ns * sizeof(UzStoreEnt)), p_pc = pc.take((uint64_t)NP * sizeof(UzPiece)), p_fold = pc.take((uint64_t)nf * 4),
                  p_raw = pc.take((uint64_t)NP * 4), p_crc = pc.take((uint64_t)ns * 4);
-  const int rc = uz_grow(c, S->ptab, pc.at, zip ? "hipMalloc (zip piece tables)" : "hipMalloc (unzip piece tables)");
+  const int rc = dev_grow(c, S->ptab, pc.at, zip ? "hipMalloc (zip piece tables)" : "hipMalloc (unzip piece tables)");
   if (rc) return rc;
   uint8_t *T = S->ptab.p;
   hipMemcpyAsync(T + p_ent, se.data(), (size_t)ns * sizeof(UzStoreEnt), hipMemcpyHostToDevice, st);
@@ -393,7 +382,7 @@ static int uz_group(Ctx *c, UzState *S, const uint8_t *archive, const zada_unzip
   std::vector<uint8_t> h16((size_t)ng * 16, 0);
   c->tmark("unzip:begin");
   if (nc || ng) {
-    int rc = scratch ? uz_grow(c, S->scratch, scratch + 16, "hipMalloc (unzip decoded copies)") : 0;
+    int rc = scratch ? dev_grow(c, S->scratch, scratch + 16, "hipMalloc (unzip decoded copies)") : 0;
     if (rc) return rc;
     for (uint32_t k = 0; k < n; k++) {
       if (slot[k] == UZ_NONE) continue;
@@ -406,7 +395,7 @@ static int uz_group(Ctx *c, UzState *S, const uint8_t *archive, const zada_unzip
     UzCarve tc;
     const uint64_t o_cj = tc.take((uint64_t)nc * sizeof(UzCryptJob)), o_gj = tc.take((uint64_t)ng * sizeof(UzGatherJob)), o_back = tc.take(0),
                    o_ver = tc.take((uint64_t)nc * 4), o_h16 = tc.take((uint64_t)ng * 16);
-    rc = uz_grow(c, S->tabs, tc.at + 256, "hipMalloc (unzip tables)");
+    rc = dev_grow(c, S->tabs, tc.at + 256, "hipMalloc (unzip tables)");
     if (rc) return rc;
     uint8_t *T = S->tabs.p;
     if (nc) {
@@ -558,7 +547,7 @@ int zada_unzip_device(zada_ctx *z, const void *d_archive, uint64_t archive_len, 
     uint64_t bytes = 0;
     for (int i = g0; i < g1; i++) { idx.push_back(i); out.push_back(d_out ? ent[i].out_off : bytes); bytes += uz_slot(ent[i].cap); }
     if (!d_out) {
-      rc = uz_grow(c, S->out, bytes + 16, "hipMalloc (unzip test-only outputs)");
+      rc = dev_grow(c, S->out, bytes + 16, "hipMalloc (unzip test-only outputs)");
       if (rc) { c->tend(); return rc; }
     }
     const uint64_t base = (uint64_t)(uintptr_t)(d_out ? d_out : (void *)S->out.p);
