@@ -132,7 +132,9 @@ const char *zada_version(void);
  * "cd_list_cap" (test knob: entries of that pass's list of open walks, 0 = by size; a full list leaves the walks where they are),
  * "atoms_pct" (ZADA_ATOMS_PCT: the atom arrays of a stream start with room for this many atoms per 100 input bytes, default 50, and grow when the match finder
  * writes more -- one atom per byte is the worst case), "fix_stride" (test knob: token slots per 512-byte chunk the parse splice starts with, 0 = 128; a splice that
- * needs more gets the full 1152 and the parse starts again), "inner_budget" (ZADA_INNER_BUDGET), "shard_kib" (ZADA_SHARD_KIB: KiB of
+ * needs more gets the full 1152 and the parse starts again), "inner_budget" (ZADA_INNER_BUDGET), "match_first" (ZADA_MATCH_FIRST: 1 = the first pass of the
+ * match finder settles every search's first candidate where it takes its positions, with all lanes busy, default; 0 = the walker does, as in rounds 1-8;
+ * zada_last_timing counts them: "#match_first_seen", "#match_first_done"), "shard_kib" (ZADA_SHARD_KIB: KiB of
  * a stream the match finder takes at a time, multiple of 64), "span_mib" (MiB of a stream one pass takes; longer streams go span after
  * span, default 2048), "link_run" (segments of 32 KiB one workgroup of the link stage takes one after the other, making their cross links itself:
  * a power of two from 1 to 64, 0 = by size; anything else is ZADA_E_INVALID), "batch_mib" (MiB one batch of small entries may take), "unzip_piece" (test knob: log2 of the bytes of one piece of a stored entry in zada_unzip_device, 8 .. 14, default 14), "unzip_legacy" (1 = zada_unzip_device, zada_compzip_device, zada_findzip_device and, for its source entries, zada_rezip_device also know methods 1 .. 6, Shrink / Reduce / Implode; default 0), "zip_legacy" (1 = zada_zip_device_ex takes Shrink_1 and Reduce_1 .. _4, zada_rezip_device the approaches shrink and reduce_4; default 0: every call answers as without the knob),"bunzip_batch_mib" (MiB of HBM one group of zada_bunzip2_batch may take: streams, outputs, slots, tt arrays; 16 .. 262144, default 8192), "bz_batch_mib" / "bz_span_mib" / "bz_batch_melems" (BZip2

@@ -355,7 +355,8 @@ class Encoder:
         "zip_legacy" = 1: zip_device_ex takes Shrink_1 and Reduce_1 .. _4, rezip_device the approaches shrink and reduce_4 (legacy=True sets it around the calls).
         "lzma_dict" is the reference's dictionary_size parameter for LZMA_3 (0 = the entry's size, what Zip.Compress.LZMA_E passes).
         "trained_fork" = 0: TrainedCompression works through every entry's whole stream (the same bytes; for measurements).
-        "descr_lazy" = 0: Deflate_3's splitter builds every window's descriptor instead of only those a bound on the distance does not decide (the same bytes; for A/B and cross-checks)."""
+        "descr_lazy" = 0: Deflate_3's splitter builds every window's descriptor instead of only those a bound on the distance does not decide (the same bytes; for A/B and cross-checks).
+        "match_first" = 0: k_match leaves every search's first candidate to the walker instead of settling it in the fetch (the same bytes; for A/B)."""
         if self.lib.zada_set_knob(self.ctx, name.encode(), int(value)) != 0:
             raise ZadaError("unknown knob %r" % name)
         self.__dict__.setdefault("_knobs_set", {})[name] = int(value)          # (what a caller that sets a knob around a call puts back)

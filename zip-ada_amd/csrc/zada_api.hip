@@ -76,6 +76,8 @@ void Ctx::tend() {
   timing.push_back({"#descr_l3_points", (float)descr_l3});
   timing.push_back({"#descr_excluded", (float)descr_excluded});
   timing.push_back({"#descr_late", (float)descr_late});
+  timing.push_back({"#match_first_seen", (float)match_first_seen});
+  timing.push_back({"#match_first_done", (float)match_first_done});
 }
 
 #ifndef ZADA_COPY_LANES
@@ -554,7 +556,7 @@ int range_open(Ctx *c, int method, const uint8_t *rin, uint64_t stream_size, uin
   R.open = true; R.rin = rin; R.lo = lo; R.pre = pre; R.n = n; R.post = post;
   R.first = lo == 0; R.last = behind == 0; R.method = method; R.level = level;
   c->last_nblocks = 0;
-  c->demand_rounds = 0; c->parse_rounds = 0; c->descr_l3 = c->descr_excluded = c->descr_late = 0; c->atoms_grown = 0; c->fix_grown = 0;
+  c->demand_rounds = 0; c->parse_rounds = 0; c->descr_l3 = c->descr_excluded = c->descr_late = 0; c->match_first_seen = c->match_first_done = 0; c->atoms_grown = 0; c->fix_grown = 0;
   // the output bit stream is OR-ed together: zero it meanwhile, on the second stream
   Workspace &W = c->ws;
   const uint64_t zbytes = n + n / 8 + (1u << 20) < W.cap_out ? n + n / 8 + (1u << 20) : W.cap_out;
@@ -770,7 +772,7 @@ static int deflate_spans(Ctx *c, int method, const uint8_t *d_src, const uint8_t
   cc.last_type = BT_RESERVED; cc.cur_eob = 7u << 16;
   bool inefficient = false;
   int total_demand = 0, total_splice = 0, total_atoms_grown = 0, total_fix_grown = 0;
-  uint64_t total_l3 = 0, total_excluded = 0, total_late = 0;
+  uint64_t total_l3 = 0, total_excluded = 0, total_late = 0, total_first_seen = 0, total_first_done = 0;
   for (uint64_t lo = 0; lo < n; lo += span) {
     const uint64_t hi = lo + span < n ? lo + span : n;
     const bool last = hi == n;
@@ -795,6 +797,7 @@ static int deflate_spans(Ctx *c, int method, const uint8_t *d_src, const uint8_t
     rc = range_lz(c, lo > 0 ? &entry : nullptr, nullptr, nullptr);
     if (rc) return rc;
     total_demand += c->demand_rounds; total_splice += c->parse_rounds; total_atoms_grown += c->atoms_grown; total_fix_grown += c->fix_grown;
+    total_first_seen += c->match_first_seen; total_first_done += c->match_first_done;
     // what the entropy stage takes now: whole flushes (the stream's position on the flush grid is G, a multiple of 65 536)
     const uint64_t tview = last ? R.T : R.T / FLUSH * FLUSH;
     R.G = G; R.n_la = 0; R.T_view = tview; R.T_total = last ? G + R.T : ~0ull >> 2;
@@ -855,6 +858,7 @@ static int deflate_spans(Ctx *c, int method, const uint8_t *d_src, const uint8_t
   }
   c->demand_rounds = total_demand; c->parse_rounds = total_splice; c->atoms_grown = total_atoms_grown; c->fix_grown = total_fix_grown;      // (of all spans: range_open starts them at 0)
   c->descr_l3 = total_l3; c->descr_excluded = total_excluded; c->descr_late = total_late;
+  c->match_first_seen = total_first_seen; c->match_first_done = total_first_done;
   c->tmark("end"); c->tend();
   *out_len = inefficient ? base_bytes : (cc.pos + 7) / 8;
   if (crc_inout) *crc_inout = crc;
@@ -999,7 +1003,7 @@ int batch_launch(Ctx *c, int method, const BatchLayout &L, uint64_t *obytes, uin
   Range &R = c->rg;
   R = Range();
   R.open = true; R.batch = true; R.n_entries = E; R.rin = W.in; R.n = total; R.method = method; R.level = level;
-  c->last_nblocks = 0; c->demand_rounds = 0; c->parse_rounds = 0; c->descr_l3 = c->descr_excluded = c->descr_late = 0;
+  c->last_nblocks = 0; c->demand_rounds = 0; c->parse_rounds = 0; c->descr_l3 = c->descr_excluded = c->descr_late = 0; c->match_first_seen = c->match_first_done = 0;
   hipLaunchKernelGGL(k_batch_crc, dim3(E), dim3(64), 0, st, E, W.in, W.ent_start, W.ent_len, W.ent_crc);
   ShardJob job;
   job.nbuf = total; job.tok_lo = 0; job.tok_hi = (uint32_t)total; job.final = true; job.entry_known = true; job.entry = ExitState{0, SYNC_F};
@@ -1124,6 +1128,7 @@ zada_ctx *zada_create(int device) {
   // tuning knobs: read once per context
   if (const char *e = getenv("ZADA_BUDGET")) z->c.knob_budget = atoi(e);
   if (const char *e = getenv("ZADA_INNER_BUDGET")) z->c.knob_inner_budget = atoi(e);
+  if (const char *e = getenv("ZADA_MATCH_FIRST")) z->c.knob_match_first = atoi(e) != 0;
   if (const char *e = getenv("ZADA_LINK_RUN")) { const int v = atoi(e); if (v >= 0 && v <= 64 && !(v & (v - 1))) z->c.knob_link_run = v; }
   if (const char *e = getenv("ZADA_ATOMS_PCT")) { if (atoi(e) >= 1 && atoi(e) <= 100) z->c.knob_atoms_pct = atoi(e); }
   if (const char *e = getenv("ZADA_DESCR_LAZY")) z->c.knob_descr_lazy = atoi(e) != 0;
@@ -1146,6 +1151,7 @@ int zada_set_knob(zada_ctx *z, const char *name, int value) {
   if (!z || !name) return ZADA_E_INVALID;
   if (!strcmp(name, "budget")) z->c.knob_budget = value;
   else if (!strcmp(name, "inner_budget")) z->c.knob_inner_budget = value;
+  else if (!strcmp(name, "match_first")) { if (value < 0 || value > 1) return ZADA_E_INVALID; z->c.knob_match_first = value; }
   else if (!strcmp(name, "link_run")) { if (value < 0 || value > 64 || (value & (value - 1))) return ZADA_E_INVALID; z->c.knob_link_run = value; }
   else if (!strcmp(name, "span_mib")) { if (value < 1 || value > 3968) return ZADA_E_INVALID; z->c.knob_span_mib = value; }
   else if (!strcmp(name, "bunzip_batch_mib")) { if (value < 16 || value > 262144) return ZADA_E_INVALID; z->c.knob_bunzip_batch_mib = value; }
@@ -2302,7 +2308,7 @@ int lzma_batch_launch(Ctx *c, int method, DevBatch &D) {
       hipLaunchKernelGGL(k_pad_init, dim3(1), dim3(256), 0, st, pa);
     }
     c->rg = Range();
-    c->last_nblocks = 0; c->demand_rounds = 0; c->parse_rounds = 0; c->descr_l3 = c->descr_excluded = c->descr_late = 0;
+    c->last_nblocks = 0; c->demand_rounds = 0; c->parse_rounds = 0; c->descr_l3 = c->descr_excluded = c->descr_late = 0; c->match_first_seen = c->match_first_done = 0;
     hipLaunchKernelGGL(k_batch_crc, dim3(E), dim3(64), 0, st, E, W.in, W.ent_start, W.ent_len, W.ent_crc);
     ShardJob job;
     job.nbuf = total; job.tok_lo = 0; job.tok_hi = (uint32_t)total; job.final = true; job.entry_known = true; job.entry = ExitState{0, SYNC_F};

@@ -1198,6 +1198,7 @@ __global__ void __launch_bounds__(256) k_bucket_limits(Layout L, int kfull, int 
 #ifndef ZADA_CMP_TURNS
 #define ZADA_CMP_TURNS 2
 #endif
+constexpr int FIRST_TURNS = 2;                    // eight-byte turns of the compare the fetch gives a search's first candidate (1, 4, and two candidates: measured and rejected)
 static_assert(ZADA_FAST % 2 == 0, "the fast phase is unrolled in pairs of steps");
 constexpr int MB = 16384;
 constexpr int HALO = 32512;                       // >= MAX_DIST, multiple of 16
@@ -1214,6 +1215,11 @@ static_assert(MATCH_LDS <= 160 * 1024, "k_match: one workgroup per CU");
 // once.  Each round = ZADA_FAST "fast" steps (follow the link, test the two bytes a candidate must share to beat
 // `best`, :754-757) with no side paths, then one batched "slow" phase for everything rare: eight-byte compares of
 // the survivors, improvements, limits, results.
+// A search's FIRST candidate is settled where the wave takes its positions, in the fetch, by all 64 lanes at once
+// (knob "match_first"): with best = K-1 and chains of K hashed bytes it nearly always passes the filter, and a lane
+// would spend a whole round on that one compare.  Searches that end with it never enter the queue.
+// (MATCH_FIRST is a template parameter so that the knob's 0 runs the kernel without that step's code and registers.)
+template <bool MATCH_FIRST>
 __global__ void __launch_bounds__(1024) k_match(const uint8_t *__restrict__ in, Layout L,
                                                 const uint16_t *__restrict__ prevd,
                                                 DistPlanes dp,
@@ -1267,6 +1273,7 @@ __global__ void __launch_bounds__(1024) k_match(const uint8_t *__restrict__ in, 
   uint32_t *queue = next_pos + 4 + (threadIdx.x >> 6) * (2 * QCAP);
   const int lane = threadIdx.x & 63;
   uint32_t q_head = 0, q_tail = 0;                                 // (uniform over the wave)
+  uint32_t n_first_seen = 0, n_first_done = 0;                     // first candidates examined in the fetch / searches finished there (uniform over the wave)
   bool blk_done = false;                                           // the block has no positions left to take
   for (;;) {
     // ---- fetch ----
@@ -1285,7 +1292,7 @@ __global__ void __launch_bounds__(1024) k_match(const uint8_t *__restrict__ in, 
         if (k0 >= cnt) blk_done = true;
         else {
           const uint32_t k = k0 + (uint32_t)lane;
-          bool ok = false;
+          bool ok = false, first = false, fdone = false;
           uint32_t e_lo = 0, e_hi = 0;
           if (k < cnt) {
             const uint64_t rem = n - (B + k);
@@ -1328,10 +1335,49 @@ __global__ void __launch_bounds__(1024) k_match(const uint8_t *__restrict__ in, 
 #ifndef ZADA_NO_INNER
             if (ok && k >= 2 && short_budget > 0) { const uint32_t m1 = dp.d[NLEVELS - 1][B + k - 1], m2 = dp.d[NLEVELS - 1][B + k - 2]; inner = dl[NLEVELS - 1] == m1 && m1 == m2; }
 #endif
-            // (hq is recomputed at pick-up: for a queued position it is bd_ > lq)
-            e_lo = k | ((uint32_t)(b_ - 2) << 14) | ((uint32_t)inner << 16) | (bd_ << 17);
-            e_hi = lf | (lq << 15) | (qlev << 30);
+            // The first candidate of the chain, here, with every lane busy (knob "match_first"): a level-K chain holds the positions
+            // with the hash of the same K bytes, so nearly every first candidate passes the walker's filter at bytes best-1, best
+            // = K-1, K and would cost its lane a whole round for one compare.  Exactly the walker's steps, in its order: filter,
+            // compare up to la, improve if strictly longer (:812-817), finish at nice_match or at the chain's end (:815, :820),
+            // or where the successor lies beyond the limit (:819-822).  Only for positions without a quarter limit of their
+            // own (lq == lf: no snapshot can fall here), and only if the compare ends within FIRST_TURNS turns: everything
+            // else (zeros, periodic data, every 258-byte match) is queued as it was, its first candidate unexamined.
+            const bool flat = lq == lf;
+            if (MATCH_FIRST && ok && flat) {
+              const uint32_t w = woff + k, c1 = w - d0;
+              const uint32_t d1 = lnk[c1];                         // (0xFFFF = none: beyond every limit)
+              const bool pass = LDS_U16(win8, c1 + (uint32_t)b_ - 1u) == LDS_U16(win8, w + (uint32_t)b_ - 1u);
+              bool open = pass;
+              uint32_t off = 0;
+              int len = 0;
+#pragma unroll
+              for (int t = 0; t < FIRST_TURNS; t++) {
+                if (open) {
+                  const uint64_t x = lds_u64_at(win8, c1 + off) ^ lds_u64_at(win8, w + off);
+                  if (x) { len = (int)off + (int)(__builtin_ctzll(x) >> 3); open = false; }
+                  else { off += 8; if ((int)off >= la_) { len = la_; open = false; } }
+                }
+              }
+              if (!open) {                                         // settled
+                first = true;
+                len = len < la_ ? len : la_;
+                const bool improved = pass && len > b_;
+                if (improved) { b_ = len; bd_ = d0; }
+                if ((improved && len >= nice_) || d0 + d1 > lf) {  // (no quarter limit: the snapshot is the result)
+                  const uint32_t packed = ((uint32_t)b_ << 16) | bd_;
+                  MatchPair r; r.full = packed; r.quarter = packed;
+                  M[B + k] = r;
+                  fdone = true; ok = false;
+                }
+              }
+            }
+            // (hq is recomputed at pick-up: for a queued position it is bd_ > lq.  A queued position's best is K-1 from the planes, or,
+            // "flat", what its first candidate made of it: nine bits in place of the quarter limit it does not have, and one that says "settled")
+            e_lo = k | ((uint32_t)inner << 14) | (bd_ << 15) | ((uint32_t)flat << 30);
+            e_hi = flat ? lf | ((uint32_t)(b_ - 2) << 15) | ((uint32_t)first << 24) : lf | (lq << 15) | (qlev << 30);
           }
+          n_first_seen += (uint32_t)__popcll(__ballot(first));          // (per wave; added up once, at the kernel's end)
+          n_first_done += (uint32_t)__popcll(__ballot(fdone));
           const unsigned long long okm = __ballot(ok);
           if (ok) { uint32_t *e = queue + 2 * ((q_tail + (uint32_t)__popcll(okm & ((1ull << lane) - 1ull))) & (QCAP - 1)); e[0] = e_lo; e[1] = e_hi; }
           q_tail += (uint32_t)__popcll(okm);
@@ -1347,10 +1393,12 @@ __global__ void __launch_bounds__(1024) k_match(const uint8_t *__restrict__ in, 
           const uint64_t rem = n - (B + kpos);
           la = rem < 258 ? (int)rem : 258;
           nice = nice_cfg < la ? nice_cfg : la;
-          best = 2 + (int)((e_lo >> 14) & 3u); bdist = e_lo >> 17;
-          mybudget = ((e_lo >> 16) & 1u) ? short_budget : budget;
+          const bool flat = (e_lo >> 30) & 1u;
+          const bool settled = MATCH_FIRST && flat && ((e_hi >> 24) & 1u);
+          best = flat ? 2 + (int)((e_hi >> 15) & 0x1FFu) : 2 + NLEVELS; bdist = (e_lo >> 15) & 0x7FFFu;
+          mybudget = ((e_lo >> 14) & 1u) ? short_budget : budget;
           lim_full = e_hi & 0x7FFFu;
-          const uint32_t lim_q = (e_hi >> 15) & 0x7FFFu, qlev = e_hi >> 30;
+          const uint32_t lim_q = flat ? lim_full : (e_hi >> 15) & 0x7FFFu, qlev = flat ? 0u : e_hi >> 30;   // (flat: rq is only read after a snapshot has set it)
           have_q = bdist > lim_q;
           // quarter-chain result so far: the best level whose candidate lies within the quarter limit
           rq = 0;
@@ -1362,6 +1410,8 @@ __global__ void __launch_bounds__(1024) k_match(const uint8_t *__restrict__ in, 
           const uint32_t d0 = lnk[wi];
           if (!have_q && d0 > lim_q) { have_q = true; rq = ((uint32_t)best << 16) | bdist; lim_cur = lim_full; }
           cur = wi - d0;
+          // the fetch has settled the first candidate: on with the second (within the limit, or the search had ended there)
+          if (settled) cur -= lnk[cur];
           s_end = LDS_U16(win8, wi + (uint32_t)best - 1u);
           state = 1;
         } else if (blk_done) {
@@ -1478,6 +1528,12 @@ __global__ void __launch_bounds__(1024) k_match(const uint8_t *__restrict__ in, 
       resume[B + kpos] = (uint16_t)(wi - cur);
       state = 0;
     }
+  }
+  // counters of the fetch (last_timing: #match_first_seen, #match_first_done): a wave's totals into LDS, the block's into memory
+  if (MATCH_FIRST) {
+    if (lane == 0 && n_first_seen) { atomicAdd(&next_pos[2], n_first_seen); atomicAdd(&next_pos[3], n_first_done); }
+    __syncthreads();
+    if (tid == 0 && next_pos[2]) { atomicAdd(&dbg[32], (unsigned long long)next_pos[2]); atomicAdd(&dbg[33], (unsigned long long)next_pos[3]); }
   }
 #ifdef ZADA_MATCH_STATS
   {
@@ -2366,7 +2422,8 @@ int lz_shard(Ctx *c, int level, const ShardJob &job, ShardResult *res) {
     hipFuncSetAttribute((const void *)k_prev_links<true>, hipFuncAttributeMaxDynamicSharedMemorySize, PL_LDS_RUNS);
     hipFuncSetAttribute((const void *)k_prev_links<false>, hipFuncAttributeMaxDynamicSharedMemorySize, PL_LDS);
     hipFuncSetAttribute((const void *)k_cross_links, hipFuncAttributeMaxDynamicSharedMemorySize, CL_LDS_PLANE);
-    hipFuncSetAttribute((const void *)k_match, hipFuncAttributeMaxDynamicSharedMemorySize, MATCH_LDS);
+    hipFuncSetAttribute((const void *)k_match<true>, hipFuncAttributeMaxDynamicSharedMemorySize, MATCH_LDS);
+    hipFuncSetAttribute((const void *)k_match<false>, hipFuncAttributeMaxDynamicSharedMemorySize, MATCH_LDS);
     hipFuncSetAttribute((const void *)k_match_demand, hipFuncAttributeMaxDynamicSharedMemorySize, DM_LDS);
     c->lz_attrs_set = true;
   }
@@ -2504,8 +2561,18 @@ int lz_shard(Ctx *c, int level, const ShardJob &job, ShardResult *res) {
   hipMemsetAsync(W.blk_demand, 0, (size_t)nbd * 4, st);
   hipMemsetAsync(W.dbits, 0, (size_t)nbd * (DMB / 8), st);
   hipMemsetAsync(W.n_demand, 0, 4, st);
-  hipLaunchKernelGGL(k_match, dim3(nbm), dim3(1024), MATCH_LDS, st, W.in, L, W.lprev[NLEVELS - 1], dpl, W.M, cfg.nice,
-                     budget_env, (unsigned long long *)W.dbg, W.lprev[0], budget_env > c->knob_inner_budget ? c->knob_inner_budget : 0);
+  if (c->knob_match_first) hipMemsetAsync(W.dbg + 32, 0, 16, st);      // (k_match's counters of the fetch)
+  const int inner_budget = budget_env > c->knob_inner_budget ? c->knob_inner_budget : 0;
+  if (c->knob_match_first) hipLaunchKernelGGL(k_match<true>, dim3(nbm), dim3(1024), MATCH_LDS, st, W.in, L, W.lprev[NLEVELS - 1], dpl, W.M, cfg.nice,
+                                              budget_env, (unsigned long long *)W.dbg, W.lprev[0], inner_budget);
+  else hipLaunchKernelGGL(k_match<false>, dim3(nbm), dim3(1024), MATCH_LDS, st, W.in, L, W.lprev[NLEVELS - 1], dpl, W.M, cfg.nice,
+                          budget_env, (unsigned long long *)W.dbg, W.lprev[0], inner_budget);
+#ifdef ZADA_MATCH_STATS
+  { unsigned long long h[8]; hipStreamSynchronize(st); hipMemcpy(h, W.dbg, sizeof h, hipMemcpyDeviceToHost);
+    fprintf(stderr, "[k_match] %llu lane-iterations (chain steps + compare turns) in %llu wave-cycles of %llu waves: %.3f per wave-cycle; longest lane %llu cycles; wave-cycles behind the block's last position %.1f %%; %llu blocks of %.0f cycles\n",
+            h[0], h[2], h[3], (double)h[0] / (h[2] ? h[2] : 1), h[1], 100.0 * h[4] / (h[2] ? h[2] : 1), h[6], (double)h[5] / (h[6] ? h[6] : 1));
+    hipMemset(W.dbg, 0, sizeof h); }
+#endif
   c->tmark("match");
   ParseIO io; io.in = W.in; io.n = n; io.M = W.M; io.cfg = cfg; io.segend = job.segend;
   DemandMarker dm; dm.M = W.M; dm.blk_demand = W.blk_demand; dm.n_demand = W.n_demand; dm.by = M_BYSPEC; dm.dbits = W.dbits;
@@ -2624,11 +2691,14 @@ int lz_shard(Ctx *c, int level, const ShardJob &job, ShardResult *res) {
   hipLaunchKernelGGL(k_tok_count, dim3((nch + 255) / 256), dim3(256), 0, st, nch, W.spec_cnt, W.fix_cnt, W.take_from, W.counts);
   exclusive_scan_u32(st, W.counts + k0, W.offsets, W.scan_sums, W.n_changed, nk);
   struct { uint32_t total; ExitState ex, warm; } h;
+  uint64_t mfirst[2] = {0, 0};
+  if (c->knob_match_first) hipMemcpyAsync(mfirst, W.dbg + 32, 16, hipMemcpyDeviceToHost, st);
   h.ex = ExitState{(uint32_t)n, SYNC_F}; h.warm = ExitState{0, SYNC_F};
   hipMemcpyAsync(&h.total, W.n_changed, 4, hipMemcpyDeviceToHost, st);
   if (!job.final) hipMemcpyAsync(&h.ex, W.true_exits + (k1 - 1), sizeof(ExitState), hipMemcpyDeviceToHost, st);
   if (k0 > 0) hipMemcpyAsync(&h.warm, W.true_exits + (k0 - 1), sizeof(ExitState), hipMemcpyDeviceToHost, st);
   if (hip_check(c, hipStreamSynchronize(st), "tok_scan")) return ZADA_E_HIP_;
+  c->match_first_seen += mfirst[0]; c->match_first_done += mfirst[1];
   uint32_t *dst_atoms = job.dst_atoms, *dst_apos = job.dst_apos;
   if (h.total > job.cap_atoms) {                                     // more atoms than the caller guessed: it makes room, or it is an error
     if (!job.grow_atoms) { c->err = "atom array overflow"; return -2; }
